@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the molann forward path on MI355X: frames/s (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--frames F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--frames F] [--dump-outputs DIR]
 
 A "step" is one forward of the workload's model over one batch of synthetic frames that already sit in
 HBM.  Default workload C3 = the full MolANN forward on the 22-atom alanine dipeptide (Kabsch on the 7
@@ -32,6 +32,10 @@ One JSON line on rank 0; besides the contract's keys it carries
                 (MOLANN_ELIDE_INVARIANT_ALIGNMENT, MOLANN_DEBUG_*) makes the bench refuse to report a
                 value unless --diagnostic is given, and the line then says "diagnostic": true
   config.dist   world size, backend and the device of every rank, as torch.distributed reports them
+
+--dump-outputs DIR writes, after the timed region, what the K-th step returned (N > 1: the all-gathered outputs, or
+rank 0's shard under --no-gather) as DIR/y.npy, at most 64 MB: a larger output keeps a fixed, seeded sample of its rows.  Frames and weights are seeded, so
+the same arguments give the same inputs on every run, and two builds can be compared output for output.
 """
 
 import argparse
@@ -57,6 +61,9 @@ HBM_COPY_GBS = 6290.0       # measured float4 copy (same guide)
 # variables that change WHAT is computed (or skip part of it): a line measured under one is not a result
 RESULT_CHANGING_ENV = ("MOLANN_ELIDE_INVARIANT_ALIGNMENT", "MOLANN_DEBUG_", "MOLANN_DIAG_LIB", "MOLANN_JIT_EXTRA_FLAGS")
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000     # --dump-outputs: all files together, headers included
+DUMP_SAMPLE_SEED = 0
+
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
@@ -74,7 +81,13 @@ def parse_args(argv=None):
     ap.add_argument("--gather-chunks", type=int, default=4, help="overlap mode: pieces the last step is cut into")
     ap.add_argument("--diagnostic", action="store_true",
                     help="allow result-changing MOLANN_* switches; the line is then marked diagnostic")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (a fixed sample of rows above %d bytes)"
+                         % DUMP_MAX_BYTES)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -371,6 +384,30 @@ def pick_buffers(args, buf_bytes):
     return nbuf
 
 
+def dump_outputs(outdir, outputs, max_bytes=DUMP_MAX_BYTES):
+    """Write each output tensor as outdir/<name>.npy: float64 stays float64, any other dtype is written as float32.
+    An output larger than its share of `max_bytes` keeps a fixed sample of its rows (first dimension): the rows a
+    generator seeded with DUMP_SAMPLE_SEED picks for that row count, in ascending order.  Returns, per name, the
+    full shape and the number of rows written."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = max_bytes // max(1, len(outputs)) - 4096        # room for the .npy header
+    written = {}
+    with torch.no_grad():
+        for name, t in outputs.items():
+            dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+            n = t.shape[0]
+            row_bytes = (t[0].numel() if n else 0) * (8 if dt == torch.float64 else 4)
+            if n * row_bytes > share:
+                k = share // row_bytes
+                assert k > 0, (name, tuple(t.shape))
+                rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+                t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(outdir, name + ".npy"), t.to(dt).cpu().numpy())
+            written[name] = {"shape": list(outputs[name].shape), "rows_written": int(t.shape[0])}
+    return written
+
+
 def run_rank(args, side, world, rank, distributed, env=None, diagnostic=False, emit=print):
     """K timed steps of the workload on this rank's shard (+ the one all-gather when distributed) and, on rank 0, the
     JSON line.  `side` supplies device, model, frames, timers (HipSide on the command line; tests hand in a CPU
@@ -524,6 +561,9 @@ def run_rank(args, side, world, rank, distributed, env=None, diagnostic=False, e
         if world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(w, model, args.cpu_seconds)
             rec["gpu_over_cpu"] = value / rec["cpu_baseline"]["value"]
+        if args.dump_outputs:
+            # the K-th step's result as its caller receives it: the gathered outputs of all ranks, else this rank's own
+            rec["dumped_outputs"] = dump_outputs(args.dump_outputs, {"y": y_all if gather else y})
         emit(json.dumps(rec))
     return rec
 

@@ -85,6 +85,50 @@ def test_result_changing_switches_are_refused():
     assert diag is True and env == {"MOLANN_DEBUG_ABLATE": "64"}
 
 
+def test_steps_below_one_are_refused():
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_the_last_timed_steps_outputs(tmp_path):
+    """--dump-outputs: y.npy holds what the K-th timed step returned (its input is buffer (K-1) mod buffers), and the
+    model ran exactly warm-up + K timed + K individually synchronised steps."""
+    import numpy as np
+    from build_util import oracle_for_workload
+    from bench_standin import CpuStandIn
+    from molann_amd import workloads as wl
+    side = CpuStandIn()
+    args = bench.parse_args(["--steps", "3", "--warmup", "1", "--frames", "203", "--workload", "C3", "--no-cpu-baseline",
+                             "--dump-outputs", str(tmp_path)])
+    lines = []
+    rec = bench.run_rank(args, side, 1, 0, False, env={}, emit=lines.append)
+    assert side.calls == 1 + 3 + 3 and rec["steps"] == 3
+    assert json.loads(lines[0])["dumped_outputs"] == {"y": {"shape": [203, 8], "rows_written": 203}}
+    w = wl.get_workload("C3")
+    nbuf = rec["config"]["input_buffers"]
+    assert nbuf > 3
+    y = np.load(str(tmp_path / "y.npy"))
+    assert y.dtype == np.float32 and y.shape == (203, 8)
+    want = oracle_for_workload(w, side.build_model(w).module, w.make_frames(203, seed=w.seed + 2), torch.float32)
+    assert np.allclose(y, want.numpy(), atol=1e-6)
+    other = oracle_for_workload(w, side.build_model(w).module, w.make_frames(203, seed=w.seed + 1), torch.float32)
+    assert not np.allclose(y, other.numpy(), atol=1e-3)
+
+
+def test_dump_outputs_keeps_a_fixed_sample_of_a_large_output(tmp_path):
+    import numpy as np
+    big = torch.arange(1000 * 10, dtype=torch.float64).reshape(1000, 10)
+    info = bench.dump_outputs(str(tmp_path / "a"), {"y": big, "h": big[:, :3].to(torch.bfloat16)}, max_bytes=40000)
+    ya, ha = np.load(str(tmp_path / "a" / "y.npy")), np.load(str(tmp_path / "a" / "h.npy"))
+    assert ya.dtype == np.float64 and ha.dtype == np.float32 and ha.shape == (1000, 3)
+    assert info == {"y": {"shape": [1000, 10], "rows_written": (20000 - 4096) // 80}, "h": {"shape": [1000, 3], "rows_written": 1000}}
+    rows = ya[:, 0] / 10
+    assert np.all(np.diff(rows) > 0) and np.array_equal(ya, big.numpy()[rows.astype(int)])
+    assert sum(os.path.getsize(str(p)) for p in (tmp_path / "a").iterdir()) <= 40000
+    bench.dump_outputs(str(tmp_path / "b"), {"y": big}, max_bytes=20000)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "y.npy")), ya)          # the same rows from run to run
+
+
 def test_c1_cpu_baseline_runs_at_c1s_batch():
     from molann_amd import workloads as wl
     from bench_standin import CpuStandIn

@@ -38,6 +38,23 @@ def test_plain_run_prints_the_contract_line(hip_device):
     assert "molann_lane_jit" in d["config"]["kernels"]
 
 
+def test_dump_outputs_are_the_last_timed_steps(hip_device, tmp_path):
+    """--dump-outputs on the device path: y.npy is the K-th step's output, i.e. the model on input buffer (K-1) mod buffers."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from build_util import oracle_for_workload, workload_model
+    from molann_amd import workloads as wl
+    d = _line(_bench(["--steps", "3", "--warmup", "1", "--frames", "65536", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)]))
+    assert d["dumped_outputs"] == {"y": {"shape": [65536, 8], "rows_written": 65536}} and d["config"]["input_buffers"] > 3
+    y = np.load(str(tmp_path / "y.npy"))
+    assert y.dtype == np.float32 and y.shape == (65536, 8)
+    w = wl.get_workload("C3")
+    x = w.make_frames(65536, device=hip_device, seed=w.seed + 2)
+    want = oracle_for_workload(w, workload_model(w), x, torch.float64)
+    assert float(np.abs(y.astype(np.float64) - want.numpy()).max()) <= 1e-5
+
+
 def test_rccl_rehearsal_on_one_rank(hip_device):
     d = _line(_bench(["--steps", "4", "--warmup", "2", "--frames", "65536", "--no-cpu-baseline"],
                      {"MOLANN_BENCH_FORCE_DIST": "1"}))

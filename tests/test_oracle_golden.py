@@ -21,9 +21,11 @@ def test_oracle_matches_reference_fp32(name):
     with torch.no_grad():
         got = c.oracle(torch.float32)
     assert got.shape == c.out_f32.shape and got.dtype == torch.float32
-    # same ATen ops in the same order: equal up to LAPACK/BLAS threading differences
+    # same ATen ops in the same order, but the fp32 rounding depends on the BLAS/LAPACK kernels the host CPU gets (MKL's
+    # AVX-512 path wrote the golden outputs; its generic path, taken on other CPUs, differs by up to ~20 ulp at the
+    # outputs' scale): equal within the reference's own fp32 error.  The fp64 check below pins the op sequence.
     err = float((got - c.out_f32).abs().max()) if got.numel() else 0.0
-    assert err <= 2e-6, err
+    assert err <= c.tolerance_vs_f32(floor=2e-6), err
 
 
 @pytest.mark.parametrize("name", ALL)

@@ -15,6 +15,9 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang"
 
 
 def test_host_half_under_asan_ubsan():
+    if os.path.exists("/dev/kfd"):
+        # where a GPU is present, the HIP runtime in the sanitized child would open it and allocate device memory
+        pytest.skip("a GPU is present: the sanitized host half runs only on machines without one")
     if not os.path.exists(CLANG):
         pytest.skip("no ROCm clang")
     rt = subprocess.run([CLANG, "-print-file-name=libclang_rt.asan-x86_64.so"], capture_output=True, text=True).stdout.strip()

@@ -1,5 +1,5 @@
-import sys, torch
-sys.path.insert(0,'/root/repo')
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from molann_amd import workloads as wl
 from molann_amd.ann import AlignmentLayer, FeatureLayer, PreprocessingANN, last_launch_info
 from molann_amd.atomgroup import Universe
