@@ -339,10 +339,14 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
     if (d->n_align > 0) {
         std::vector<float> refc(3 * (size_t)d->n_align + 8, 0.f);
         std::vector<double> refd(3 * (size_t)d->n_align + 8, 0.);
-        double s[4] = {0, 0, 0, 0};
+        // centred here whatever the caller passes (pack_ref_kernel: the alignment does not depend on it)
+        double mean[3] = {0, 0, 0}, s[4] = {0, 0, 0, 0};
+        for (int i = 0; i < d->n_align; ++i)
+            for (int c = 0; c < 3; ++c) mean[c] += d->ref_x[3 * i + c];
+        for (int c = 0; c < 3; ++c) mean[c] /= (double)d->n_align;
         for (int i = 0; i < d->n_align; ++i) {
             for (int c = 0; c < 3; ++c) {
-                const float r = d->ref_x[3 * i + c];
+                const float r = (float)((double)d->ref_x[3 * i + c] - mean[c]);
                 refc[3 * i + c] = r;
                 refd[3 * i + c] = r;
                 s[c] += r;

@@ -300,19 +300,42 @@ __global__ void pack_chain_kernel(unsigned char* __restrict__ dst, ChainPackArgs
     }
 }
 
-// ref_x (device, centred) -> plan copy + the constants the kernels need after it
+// ref_x (device, as the module holds it: centred by __init__, or anything assigned to the buffer since) -> plan copy,
+// centred here, + the constants the kernels need after it.  The alignment does not depend on where ref_x sits
+// (sum_a (x_a - x_c) = 0 in prod, ann.py:187), so centring is exact; it makes the sums s_r = sum r (3a .. 3a + 2)
+// vanish up to rounding, so the backward kernels that leave out the centroid term -G_H s_r / n stay right.
+// fp32 buffers: dst = fp32(r - mean), dst64 = dst exactly (the kernels' fp32 and fp64 copies agree, as before).
 template <typename S> // S = float: the module's buffer as the reference builds it; double: a `.double()` model's buffer
 __global__ void pack_ref_kernel(float* __restrict__ dst, double* __restrict__ dst64, const S* __restrict__ ref,
                                 int n_align) {
     if (blockIdx.x != 0) return;
     __shared__ double red[4][256];
+    __shared__ double mean[3];
     double s[4] = {0., 0., 0., 0.};
+    for (int i = threadIdx.x; i < n_align; i += blockDim.x)
+        for (int c = 0; c < 3; ++c) s[c] += (double)ref[3 * i + c];
+    for (int c = 0; c < 3; ++c) red[c][threadIdx.x] = s[c];
+    __syncthreads();
+    for (int w = blockDim.x >> 1; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        for (int c = 0; c < 3; ++c) mean[c] = red[c][0] / (double)n_align;
+    __syncthreads();
+    for (int c = 0; c < 4; ++c) s[c] = 0.;
     for (int i = threadIdx.x; i < n_align; i += blockDim.x) {
-        const S rx = ref[3 * i], ry = ref[3 * i + 1], rz = ref[3 * i + 2];
-        dst[3 * i] = (float)rx; dst[3 * i + 1] = (float)ry; dst[3 * i + 2] = (float)rz;
-        dst64[3 * i] = rx; dst64[3 * i + 1] = ry; dst64[3 * i + 2] = rz;
-        s[0] += rx; s[1] += ry; s[2] += rz;
-        s[3] += (double)rx * rx + (double)ry * ry + (double)rz * rz;
+        double r[3];
+        for (int c = 0; c < 3; ++c) {
+            const double v = (double)ref[3 * i + c] - mean[c];
+            const float f = (float)v;
+            r[c] = sizeof(S) == sizeof(float) ? (double)f : v;
+            dst[3 * i + c] = f;
+            dst64[3 * i + c] = r[c];
+        }
+        s[0] += r[0]; s[1] += r[1]; s[2] += r[2];
+        s[3] += r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
     }
     for (int c = 0; c < 4; ++c) red[c][threadIdx.x] = s[c];
     __syncthreads();

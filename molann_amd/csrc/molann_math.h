@@ -160,7 +160,7 @@ MOLANN_HD float apply_activation(int act, float v) {
 
 // ---- Kabsch rotation --------------------------------------------------------------------------
 // Input: H[a][b] = sum_i p_i[a] * ref_i[b] over the align atoms (p centred frame coordinates, ref the
-// centred reference) = `prod` of ann.py:187, accumulated in fp64 by the callers (the products of fp32
+// reference as the plan packs it, centred whatever the buffer holds) = `prod` of ann.py:187, accumulated in fp64 by the callers (the products of fp32
 // coordinates are exact in fp64, so H carries no rounding of its own), and
 // e0 >= (sum|p|^2 + sum|ref|^2)/2, an upper bound on the largest eigenvalue used as the Newton start.
 // Output: R (row-major) with aligned_row = p_row . R, equal to U diag(1,1,sign det(U Vh)) Vh of

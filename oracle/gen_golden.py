@@ -71,10 +71,12 @@ def build_reference_model(u, input_numbers, features, align, mlp_dims, use_angle
 
 
 def run_case(name, u, x, input_numbers, features=(), align=None, mlp_dims=None, use_angle_value=False,
-             kind="forward", weight_transform=None, extra=None, x_recipe=None, store_weights=True):
-    """Run the reference on x (fp32) and on x.double(); save everything needed to replay."""
+             kind="forward", weight_transform=None, extra=None, x_recipe=None, store_weights=True, ref_x=None):
+    """Run the reference on x (fp32) and on x.double(); save everything needed to replay.  ``ref_x``: coordinates assigned to
+    the reference's AlignmentLayer buffer after __init__ (not centred: the reference does not centre it again)."""
     input_ag, feats, flayer, alayer, nn = build_reference_model(u, input_numbers, list(features), align,
                                                                 mlp_dims, use_angle_value)
+    assigned = _assign_ref_x(alayer, ref_x)
     if nn is not None and weight_transform is not None:
         with torch.no_grad():
             for p in nn.parameters():
@@ -113,6 +115,7 @@ def run_case(name, u, x, input_numbers, features=(), align=None, mlp_dims=None, 
         rec["align_local"] = np.asarray(alayer._local_align_atom_indices, dtype=np.int64)
         rec["ref_pos"] = np.asarray(u.atoms_by_number(align).positions, dtype=np.float32)
         rec["ref_x"] = alayer.ref_x.numpy()
+        rec.update(assigned)
     if flayer is not None:
         rec["feat_types"] = np.asarray([t for t, _ in features], dtype=np.int64)
         flat, ptr = csr([atoms for _, atoms in features])
@@ -137,6 +140,14 @@ def run_case(name, u, x, input_numbers, features=(), align=None, mlp_dims=None, 
     return out32
 
 
+def _assign_ref_x(alayer, ref_x):
+    """Replace the reference AlignmentLayer's (centred) ref_x buffer, as a user may after __init__; the record marks it."""
+    if ref_x is None:
+        return {}
+    alayer.ref_x = torch.as_tensor(np.asarray(ref_x, dtype=np.float32)).clone()
+    return {"ref_x_assigned": np.bool_(True)}
+
+
 def noisy(ref_xyz, n, sigma, seed, rigid=False, translation=3.0, reflect_every=0):
     g = torch.Generator().manual_seed(seed)
     ref = torch.from_numpy(np.asarray(ref_xyz, dtype=np.float32))
@@ -150,11 +161,16 @@ def noisy(ref_xyz, n, sigma, seed, rigid=False, translation=3.0, reflect_every=0
     return x
 
 
-def grad_case(name, u, x, input_numbers, features, align, mlp_dims, use_angle_value=False, seed=11, extra=None):
-    """Gradients of sum(out * G) from the REFERENCE's autograd (fp32 and its .double() copy)."""
+def grad_case(name, u, x, input_numbers, features, align, mlp_dims, use_angle_value=False, seed=11, extra=None, ref_x=None):
+    """Gradients of sum(out * G) from the REFERENCE's autograd (fp32 and its .double() copy).  No features and no MLP: the
+    AlignmentLayer alone.  ``ref_x``: as in run_case (stored with the case, flagged ref_x_assigned)."""
     import copy
     input_ag, feats, flayer, alayer, nn = build_reference_model(u, input_numbers, list(features), align, mlp_dims, use_angle_value)
-    model = MolANN(PreprocessingANN(alayer, flayer), nn) if nn is not None else PreprocessingANN(alayer, flayer)
+    assigned = _assign_ref_x(alayer, ref_x)
+    if flayer is None and nn is None:
+        model = alayer
+    else:
+        model = MolANN(PreprocessingANN(alayer, flayer), nn) if nn is not None else PreprocessingANN(alayer, flayer)
     g = torch.Generator().manual_seed(seed)
     x = torch.as_tensor(x, dtype=torch.float32)
     rec = {}
@@ -175,6 +191,9 @@ def grad_case(name, u, x, input_numbers, features, align, mlp_dims, use_angle_va
     rec["feat_numbers"], rec["feat_ptr"] = flat, ptr
     if align is not None:
         rec["align_numbers"] = np.asarray(align, dtype=np.int64)
+        if assigned:
+            rec["ref_x"] = alayer.ref_x.numpy()
+            rec.update(assigned)
     if nn is not None:
         rec["mlp_dims"] = np.asarray(mlp_dims, dtype=np.int64)
         for i, lin in enumerate([m for m in nn if isinstance(m, torch.nn.Linear)]):
@@ -378,11 +397,12 @@ def main():
     print(json.dumps(meta, indent=1))
 
 
-def grad2_case(name, u, x, input_numbers, features, align, mlp_dims, use_angle_value=False, seed=13):
+def grad2_case(name, u, x, input_numbers, features, align, mlp_dims, use_angle_value=False, seed=13, ref_x=None):
     """Second-order golden vectors from the REFERENCE's autograd: E = sum(out * G), forces F = dE/dx with create_graph=True,
     L = sum(F * F); stored: dL/dx and dL/d(parameters) (float64 model; the float32 model's dL/dx as well)."""
     import copy
     input_ag, feats, flayer, alayer, nn = build_reference_model(u, input_numbers, list(features), align, mlp_dims, use_angle_value)
+    assigned = _assign_ref_x(alayer, ref_x)
     model = MolANN(PreprocessingANN(alayer, flayer), nn) if nn is not None else PreprocessingANN(alayer, flayer)
     g = torch.Generator().manual_seed(seed)
     x = torch.as_tensor(x, dtype=torch.float32)
@@ -406,6 +426,9 @@ def grad2_case(name, u, x, input_numbers, features, align, mlp_dims, use_angle_v
     rec["feat_numbers"], rec["feat_ptr"] = flat, ptr
     if align is not None:
         rec["align_numbers"] = np.asarray(align, dtype=np.int64)
+        if assigned:
+            rec["ref_x"] = alayer.ref_x.numpy()
+            rec.update(assigned)
     if nn is not None:
         rec["mlp_dims"] = np.asarray(mlp_dims, dtype=np.int64)
         for i, lin in enumerate([m_ for m_ in nn if isinstance(m_, torch.nn.Linear)]):
@@ -474,7 +497,59 @@ def round3c_main():
     grad_case("grad_features_P1", u, w.make_frames(33, seed=22), alln, w.features, list(w.align), None, extra={"ref_xyz": w.ref_xyz})
 
 
+def uncentred_main():
+    """Reference states assigned after __init__ (the other files are left untouched): the reference's alignment does not depend on
+    where ref_x sits (sum_a (x_a - x_c) = 0 in prod, ann.py:187), and neither do its gradients, so a shifted or raw ref_x must
+    give what the centred one gives.  Gradients through every backward family with position items or the AlignmentLayer alone,
+    and forward cases with the raw coordinates of another conformation."""
+    os.makedirs(OUT, exist_ok=True)
+    pdb = read_pdb_xyz("/root/reference/test/alanine-dipeptide-vacuum.pdb")
+    u = Universe(pdb)
+    all22 = list(range(1, 23))
+    shift = np.asarray([3.0, -2.0, 5.0], dtype=np.float32)
+    bb = list(wl.ALA_BACKBONE)
+    bb_centred = pdb[[a - 1 for a in bb]] - pdb[[a - 1 for a in bb]].mean(axis=0, keepdims=True)
+    wp = wl.get_workload("C3p")
+    grad_case("grad_features_C3p_shift", u, wp.make_frames(40, seed=41), all22, wp.features, wp.align, None, ref_x=bb_centred + shift)
+    grad2_case("grad2_features_C3p_shift", u, wp.make_frames(20, seed=42), all22, wp.features, wp.align, None, ref_x=bb_centred + shift)
+    # L1: positions of the 7 backbone atoms + one dihedral (d = 23) behind a small head, the raw PDB coordinates as the reference
+    l1_feats = [(wl.POSITION, tuple(bb)), (wl.DIHEDRAL, (5, 7, 9, 15))]
+    grad_case("grad_molann_L1_raw", u, wl.get_workload("C3").make_frames(40, seed=43), all22, l1_feats, bb, [23, 16, 4],
+              ref_x=pdb[[a - 1 for a in bb]])
+    # the 166-atom chain: the AlignmentLayer alone (shift of about 30 A), P2's features (centred and raw + offset), P2 with its head
+    w5 = wl.get_workload("A5")
+    uc = Universe(w5.ref_xyz)
+    alln = list(range(1, w5.n_atoms + 1))
+    al5 = [a - 1 for a in w5.align]
+    c5 = w5.ref_xyz[al5] - w5.ref_xyz[al5].mean(axis=0, keepdims=True)
+    grad_case("grad_align_A5_shift", uc, w5.make_frames(20, seed=44), alln, [], list(w5.align), None,
+              ref_x=c5 + np.asarray([17.0, -21.0, 13.0], dtype=np.float32), extra={"ref_xyz": w5.ref_xyz})
+    w2 = wl.get_workload("P2")
+    al2 = [a - 1 for a in w2.align]
+    grad_case("grad_features_P2", uc, w2.make_frames(33, seed=45), alln, w2.features, list(w2.align), None, extra={"ref_xyz": w2.ref_xyz})
+    grad_case("grad_features_P2_raw", uc, w2.make_frames(33, seed=46), alln, w2.features, list(w2.align), None,
+              ref_x=w2.ref_xyz[al2] + np.asarray([12.0, -7.0, 25.0], dtype=np.float32), extra={"ref_xyz": w2.ref_xyz})
+    grad_case("grad_molann_P2", uc, w2.make_frames(34, seed=47), alln, w2.features, list(w2.align), w2.mlp_dims, extra={"ref_xyz": w2.ref_xyz})
+    # forward: the raw coordinates of another seeded conformation (rigidly moved, tens of A from the origin)
+    w1 = wl.get_workload("P1")
+    other = noisy(w1.ref_xyz, 1, 0.3, 501, rigid=True, translation=30.0)[0].numpy()
+    run_case("align_P1_raw", uc, w1.make_frames(41, seed=48), alln, align=list(w1.align), kind="align",
+             extra={"ref_xyz": w1.ref_xyz}, ref_x=other[[a - 1 for a in w1.align]])
+    xyz = wl.synthetic_chain(n_atoms=300, step=1.4, seed=13)
+    u3 = Universe(xyz)
+    rng = np.random.default_rng(8)
+    align = sorted((rng.choice(300, size=200, replace=False) + 1).tolist())
+    feats = wl.chain_features(300, 30, 9)
+    other = noisy(xyz, 1, 0.3, 502, rigid=True, translation=30.0)[0].numpy()
+    run_case("molann_chain300_raw", u3, noisy(xyz, 51, 0.1, 303, rigid=True), list(range(1, 301)), feats, align=align,
+             mlp_dims=[sum(1 if t in (wl.BOND, wl.ANGLE) else 2 for t, _ in feats), 32, 8], extra={"ref_xyz": xyz},
+             ref_x=other[[a - 1 for a in align]])
+
+
 if __name__ == "__main__":
+    if "--uncentred" in sys.argv:
+        uncentred_main()
+        sys.exit(0)
     if "--round3c" in sys.argv:
         round3c_main()
         sys.exit(0)

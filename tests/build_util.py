@@ -28,6 +28,9 @@ def build_modules(case, device=None, mlp_precision="f32"):
     u = universe_for(case)
     input_ag = u.atoms_by_number([i + 1 for i in case.input_ix])
     alayer = AlignmentLayer(u.atoms_by_number(case.align_numbers), input_ag) if case.has_align else None
+    if alayer is not None and case.ref_x_assigned:     # the reference's ref_x was replaced after __init__: the same here
+        with torch.no_grad():
+            alayer.ref_x.copy_(case.ref_x)
     flayer = None
     if case.features_numbers:
         feats = [Feature("f%d" % i, wl.TYPE_NAMES[t], u.atoms_by_number(nums))

@@ -47,6 +47,7 @@ class Case(object):
             self.align_local = d["align_local"].tolist()
             self.ref_pos = torch.from_numpy(d["ref_pos"])
             self.ref_x = torch.from_numpy(d["ref_x"])
+            self.ref_x_assigned = bool(d["ref_x_assigned"]) if "ref_x_assigned" in d else False   # not the centred ref_pos: assigned after __init__
         self.features = []
         self.features_numbers = []
         if "feat_types" in d:
