@@ -241,9 +241,15 @@ int molann_features_backward_f32(molann_plan* plan, const float* x, const float*
 
 /* Backward of molann_mlp_packed_f32 (create_sequential_nn's Sequential, ann.py:60-65) for the same f[N, layer_dims[0]]:
  * grad_out[N, out_dim] -> grad_f[N, layer_dims[0]] (written; may be NULL) and grad_params (accumulated; may be NULL;
- * layout of molann_plan_grad_params_size).  fp32 matrix cores; plans for which molann_plan_supports_backward is 1. */
+ * layout of molann_plan_grad_params_size).  fp32 matrix cores; plans for which molann_plan_supports_mlp_backward is 1. */
 int molann_mlp_backward_f32(molann_plan* plan, const float* f, const float* grad_out, int64_t n_frames, float* grad_f,
                             float* grad_params, molann_stream_t stream);
+
+/* 1 when molann_mlp_backward_f32 serves the plan's head: every plan with an MLP for which molann_plan_supports_backward is 1,
+ * and fp32 heads wider than 32 whose chain weight stream is resident in LDS (tanh, ReLU, sigmoid, identity, SiLU,
+ * LeakyReLU; hipRTC present, MOLANN_NO_JIT unset).  The latter leave molann_plan_supports_backward / _backward_kind as
+ * they are: the whole-model backward still runs the preprocessing and the head as two nodes.  Builds the kernel it reports. */
+int molann_plan_supports_mlp_backward(molann_plan* plan);
 
 /* -- misc ------------------------------------------------------------------------------------- */
 int molann_abi_version(void);

@@ -97,6 +97,7 @@ def lib():
             "molann_plan_grad_params_size": (i32, [vp]),
             "molann_plan_supports_backward": (i32, [vp]),
             "molann_plan_backward_kind": (i32, [vp]),
+            "molann_plan_supports_mlp_backward": (i32, [vp]),
             "molann_backward_f32": (i32, [vp, vp, vp, i64, vp, vp, vp]),
             "molann_value_and_vjp_f32": (i32, [vp, vp, vp, i64, vp, vp, vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
@@ -273,6 +274,10 @@ class Plan(object):
 
     def supports_backward(self):
         return lib().molann_plan_supports_backward(self._handle) == 1
+
+    def supports_mlp_backward(self):
+        """True when `mlp_backward` serves this plan's head (the fused family's kernel, or the wide fp32 head's)."""
+        return lib().molann_plan_supports_mlp_backward(self._handle) == 1
 
     def backward_kind(self):
         """2: `backward` is one pass over x; 1: several launches (keep the features of the forward: `forward_train`); 0: none."""

@@ -217,6 +217,69 @@ class _PlanFunction(torch.autograd.Function):
         return (gx, None, None) + tuple(grads)
 
 
+class _HeadFunction(torch.autograd.Function):
+    """The head of a model whose backward is two nodes: the preprocessing's (its own HIP backward), then this one.  For wide fp32
+    heads that `Plan.supports_mlp_backward()` accepts where `supports_backward()` does not: forward = `mlp_packed` on the
+    features, backward = `mlp_backward` (molann_chain_bwd: grad_f and the parameter gradients on the matrix cores).
+    `params` are the Linear weights/biases in layer order; `linears` the modules, repacked before each launch (`sync_mlp`)."""
+
+    @staticmethod
+    def forward(ctx, feat, entry, linears, *params):
+        plan = entry.plan
+        entry.sync_mlp(linears)
+        out = torch.empty((feat.shape[0], plan.out_dim), dtype=torch.float32, device=feat.device)
+        if feat.shape[0] > 0:
+            plan.mlp_packed(feat, out)
+        ctx.save_for_backward(feat)
+        ctx.entry, ctx.linears, ctx.params = entry, linears, params
+        ctx.shapes = [tuple(p.shape) for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        feat = ctx.saved_tensors[0]
+        params = list(ctx.params)
+        if torch.is_grad_enabled():
+            # create_graph=True: the head rebuilt as ATen ops on the live parameters, differentiated with a graph
+            act = _ACT_FNS[ctx.entry.plan.activation]
+            wanted = [(0, feat)] if ctx.needs_input_grad[0] else []
+            wanted += [(3 + i, p) for i, p in enumerate(params) if ctx.needs_input_grad[3 + i]]
+            out = [None] * (3 + len(params))
+            if not wanted:
+                return tuple(out)
+            y, n = feat, len(params) // 2
+            for l in range(n):
+                y = torch.nn.functional.linear(y, params[2 * l], params[2 * l + 1])
+                if l + 1 < n:
+                    y = act(y)
+            got = torch.autograd.grad(y, [t for _, t in wanted], grad_out, create_graph=True, allow_unused=True)
+            for (i, _), gi in zip(wanted, got):
+                out[i] = gi
+            return tuple(out)
+        plan = ctx.entry.plan
+        need_f = ctx.needs_input_grad[0]
+        need_p = any(ctx.needs_input_grad[3:])
+        gf = torch.empty_like(feat) if need_f else None
+        gp = torch.zeros(plan.grad_params_size(), dtype=torch.float32, device=feat.device) if need_p else None
+        g = grad_out.contiguous()
+        if g.dtype != torch.float32:
+            g = g.float()
+        if feat.shape[0] > 0 and (need_f or need_p):
+            with torch.cuda.device(feat.device):
+                ctx.entry.sync_mlp(ctx.linears)
+                plan.mlp_backward(feat, g, gf, gp)
+        elif need_f:
+            gf.zero_()
+        grads, off = [], 0
+        for i, shp in enumerate(ctx.shapes):
+            n = 1
+            for d in shp:
+                n *= d
+            grads.append(gp[off:off + n].view(shp) if (need_p and ctx.needs_input_grad[3 + i]) else None)
+            off += n
+        return (gf, None, None) + tuple(grads)
+
+
 class _PlanFunction64(torch.autograd.Function):
     """The float64 features of a plan (`model.double()`): forward = molann_features_f64, backward =
     molann_features_backward_f64 (everything recomputed in double from x).  The MLP of a float64 model is torch's."""
@@ -872,7 +935,27 @@ class MolANN(_PlanOwner, torch.nn.Module):
                         entry.sync_ref(_device_buffer(al.ref_x, x))
                     entry.sync_mlp(st["linears"])
                     return _PlanFunction.apply(x, entry, True, *st["params"])
-            # No fused backward kernel (MLP wider than 32 / ELU, GELU, Softplus).  Training still works when the
+            if st.get("head_bwd") is None:            # asked once, like fused_bwd
+                with torch.cuda.device(x.device):
+                    if st["op"] is not None:
+                        st["head_bwd"] = bool(torch.ops.molann.supports_mlp_backward(
+                            x, st["desc"], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"]))
+                    else:
+                        st["head_bwd"] = bool(st["entry"]().plan.supports_mlp_backward())
+            if st["head_bwd"]:
+                # A wide fp32 head with a HIP backward (molann_chain_bwd): the preprocessing layer's node, then the head's.  Through
+                # the dispatcher operator where that library is built (the plan its launch info reports), else the Function above.
+                feat = self.preprocessing_layer(x)
+                if feat.dtype != torch.float32 or not feat.is_contiguous():
+                    feat = feat.float().contiguous()
+                lins = st["linears"]
+                if st["op"] is not None:
+                    return torch.ops.molann.run_head(feat, st["desc"], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"],
+                                                     [lin.weight for lin in lins], [lin.bias for lin in lins])
+                entry = st["entry"]()
+                with torch.cuda.device(x.device):
+                    return _HeadFunction.apply(feat, entry, lins, *st["params"])
+            # No HIP backward for the head (ELU, GELU, Softplus; bf16 or streaming heads; no hipRTC).  Training still works when the
             # preprocessing has one (small frames): features and their gradient from the HIP kernels, the MLP and
             # its gradient as the user's own torch module on the device - what already happens for ann_layers
             # this file does not recognise.  Large frames raise inside the preprocessing layer.

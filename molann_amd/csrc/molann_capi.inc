@@ -524,6 +524,17 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
         }
         if (!p->chain_fn) snprintf(p->chain_note, sizeof(p->chain_note), "chain: unavailable (rc=%d), mlp_mfma_kernel", rc);
     }
+    // ---- backward of a wide fp32 head whose chain stream is resident (molann_chain_bwd.inc), built at its first use: where it
+    // serves the head, the parameter-gradient buffer has the head's layout (molann_mlp_backward_f32)
+    if (chain_fb > 0 && chain_resident(cg) && !bf16 && !p->fused_mlp && !p->lane_mlp && rtc_api()->ok && !(nojit && nojit[0] == '1')) {
+        const int act = d->activation;
+        std::vector<int> kp(p->kp, p->kp + d->n_layers), jp(p->jp, p->jp + d->n_layers);
+        if (act == 0 || act == 1 || act == 2 || act == 3 || act == 5 || act == 7) p->cbwd_waves = chain_bwd_waves(kp, jp);
+        if (p->cbwd_waves > 0) {
+            p->n_grad_params = 0;
+            for (int l = 0; l < d->n_layers; ++l) p->n_grad_params += p->dims[l + 1] * p->dims[l] + p->dims[l + 1];
+        }
+    }
     // ---- the whole forward of a WIDE head in one lane kernel (round 3) ----------------------------------------------------
     // Hidden widths 33 .. ~128 behind a lane-per-frame preprocessing: features kernel + chain MLP kernel cost a launch, a
     // round trip of the features through the workspace and - the feature kernel holds every CU - no overlap.  Where the
@@ -580,6 +591,7 @@ int molann_plan_destroy(molann_plan* p) {
     if (p->jit_mod) (void)hipModuleUnload(p->jit_mod);
     if (p->bwd_mod) (void)hipModuleUnload(p->bwd_mod);
     if (p->mbwd_mod) (void)hipModuleUnload(p->mbwd_mod);
+    if (p->cbwd_mod) (void)hipModuleUnload(p->cbwd_mod);
     if (p->rbwd_mod) (void)hipModuleUnload(p->rbwd_mod);
     if (p->vjp_mod) (void)hipModuleUnload(p->vjp_mod);
     if (p->wide_mod) (void)hipModuleUnload(p->wide_mod);
@@ -982,6 +994,33 @@ int ensure_mlp_bwd(molann_plan* p) {
     return p->mbwd_state == 1 ? MOLANN_OK : MOLANN_E_UNSUPPORTED;
 }
 
+int ensure_chain_bwd(molann_plan* p) {
+    if (p->cbwd_waves <= 0) return MOLANN_E_UNSUPPORTED;
+    if (p->cbwd_state == 0 || !p->d_gpart) {
+        std::lock_guard<std::mutex> lock(*p->jit_mu);
+        if (p->cbwd_state == 0) {
+            const int nl = p->n_layers;
+            std::vector<int> dims(p->dims, p->dims + nl + 1), kp(p->kp, p->kp + nl), jp(p->jp, p->jp + nl);
+            std::vector<long> woff(p->moff, p->moff + nl);
+            std::vector<char> code;
+            std::string log;
+            const int rc = jit_compile(jit_source_chain_bwd(dims, kp, jp, woff, p->act, p->cbwd_waves), code, log);
+            if (rc == 0 && hipModuleLoadData(&p->cbwd_mod, code.data()) == hipSuccess &&
+                hipModuleGetFunction(&p->cbwd_fn, p->cbwd_mod, "molann_chain_bwd") == hipSuccess) {
+                p->cbwd_state = 1;
+            } else {
+                p->cbwd_state = -1;
+                if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann chain backward jit failed rc=%d\n%s\n", rc, log.c_str());
+            }
+        }
+        if (p->cbwd_state == 1 && !p->d_gpart) {
+            { const int er = ensure_bwd_event(p); if (er != MOLANN_OK) return er; }
+            HIP_TRY(hipMalloc((void**)&p->d_gpart, (size_t)p->num_cus * std::max(1, p->n_grad_params) * 4));
+        }
+    }
+    return p->cbwd_state == 1 ? MOLANN_OK : MOLANN_E_UNSUPPORTED;
+}
+
 int ensure_features_bwd(molann_plan* p, molann_plan::LaneGeom& g) {
     lane_geometry(g, 64 * p->n_inp * 12, 1); // the dense frame tile (reused for the gradient rows)
     if (!g.ok) return MOLANN_E_UNSUPPORTED;
@@ -1085,6 +1124,28 @@ int launch_features_bwd(molann_plan* p, const molann_plan::LaneGeom& g, const fl
                                                 nullptr, cfg);
     snprintf(p->last_info, sizeof(p->last_info), "molann_lane_bwd (plan-specialised) grid=%d block=%d", grid, 64 * g.wpb);
     return (int)le;
+}
+
+// molann_chain_bwd (+ reduce_rows_kernel when parameter gradients are wanted); the caller holds the workspace (BwdGuard).
+// One block per CU at most (its weight copy fills the LDS), tiles of 16 WAVES frames handed out statically: the grid, and with it
+// every block's partial sums, depend on n alone.
+int launch_chain_bwd(molann_plan* p, const float* f, const float* grad_out, long n, float* grad_f, float* grad_params, hipStream_t stream) {
+    const long n_tiles = (n + 16 * p->cbwd_waves - 1) / (16 * p->cbwd_waves);
+    const int grid = (int)std::max<long>(1, std::min<long>(p->num_cus, n_tiles));
+    struct { const float* f; const float* gout; const float* wnat; float* gf; float* gp; long n; } ka =
+        {f, grad_out, (const float*)p->d_wmfma, grad_f, grad_params ? p->d_gpart : nullptr, n};
+    size_t ksz = sizeof(ka);
+    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ka, HIP_LAUNCH_PARAM_BUFFER_SIZE, &ksz, HIP_LAUNCH_PARAM_END};
+    const hipError_t le = hipModuleLaunchKernel(p->cbwd_fn, grid, 1, 1, 64 * p->cbwd_waves, 1, 1, 0, stream, nullptr, cfg);
+    if (le != hipSuccess) return (int)le;
+    if (grad_params) {
+        hipLaunchKernelGGL(reduce_rows_kernel, dim3((p->n_grad_params + 63) / 64), dim3(1024), 0, stream, p->d_gpart, grid, p->n_grad_params,
+                           grad_params);
+        HIP_TRY(hipGetLastError());
+    }
+    snprintf(p->last_info, sizeof(p->last_info), "molann_chain_bwd (plan-specialised) grid=%d block=%d%s", grid, 64 * p->cbwd_waves,
+             grad_params ? " + reduce_rows_kernel" : "");
+    return MOLANN_OK;
 }
 
 // molann_mlp_bwd (+ reduce_rows_kernel when parameter gradients are wanted); the caller holds the workspace (BwdGuard)
@@ -1370,7 +1431,17 @@ int molann_features_backward_f32(molann_plan* p, const float* x, const float* gr
     return launch_features_bwd(p, g, x, grad_f, (long)n, grad_x, (hipStream_t)stream);
 }
 
-// dL/df and dL/d(parameters) of molann_mlp_packed_f32 for the same f (the fused family: every width <= 32)
+// 1 when molann_mlp_backward_f32 serves the plan's head: the fused family's kernel (molann_mlp_bwd.inc) or, for a wide fp32 head
+// whose chain stream is resident, molann_chain_bwd.inc.  Builds the kernel it reports.
+int molann_plan_supports_mlp_backward(molann_plan* p) {
+    if (!p) return MOLANN_E_NULL;
+    if (p->n_layers <= 0) return 0;
+    if (mlp_box(p) && molann_plan_supports_backward(p)) return 1;
+    return ensure_chain_bwd(p) == MOLANN_OK ? 1 : 0;
+}
+
+// dL/df and dL/d(parameters) of molann_mlp_packed_f32 for the same f (the fused family: every width <= 32; a wide fp32 head
+// with a resident chain stream)
 int molann_mlp_backward_f32(molann_plan* p, const float* f, const float* grad_out, int64_t n, float* grad_f, float* grad_params,
                             molann_stream_t stream) {
     if (!p) return MOLANN_E_NULL;
@@ -1378,10 +1449,19 @@ int molann_mlp_backward_f32(molann_plan* p, const float* f, const float* grad_ou
     if (n == 0) return MOLANN_OK;
     if (!f || !grad_out) return MOLANN_E_NULL;
     if (p->n_layers <= 0) return MOLANN_E_STAGE;
-    if (!mlp_box(p) || !molann_plan_supports_backward(p)) return MOLANN_E_UNSUPPORTED;
+    const bool chain = !(mlp_box(p) && molann_plan_supports_backward(p));
+    if (chain && p->cbwd_waves <= 0) return MOLANN_E_UNSUPPORTED;
     if (!p->mlp_packed) return MOLANN_E_NOT_PACKED;
     if ((((uintptr_t)f) & 3) || (((uintptr_t)grad_out) & 3) || (((uintptr_t)grad_f) & 3) || (((uintptr_t)grad_params) & 3)) return MOLANN_E_ALIGNMENT;
     if (!grad_f && !grad_params) return MOLANN_OK;
+    if (chain) {
+        const int rc = ensure_chain_bwd(p);
+        if (rc != MOLANN_OK) return rc;
+        if (!grad_params) return launch_chain_bwd(p, f, grad_out, (long)n, grad_f, nullptr, (hipStream_t)stream);
+        BwdGuard guard(p, (hipStream_t)stream);
+        if (guard.rc != 0) return guard.rc;
+        return launch_chain_bwd(p, f, grad_out, (long)n, grad_f, grad_params, (hipStream_t)stream);
+    }
     const int rc = ensure_mlp_bwd(p);
     if (rc != MOLANN_OK) return rc;
     if (!grad_params) return launch_mlp_bwd(p, f, grad_out, (long)n, grad_f, nullptr, (hipStream_t)stream); // no workspace involved
@@ -1395,6 +1475,39 @@ int molann_mlp_backward_f32(molann_plan* p, const float* f, const float* grad_ou
 int molann_debug_jit(const molann_plan_desc* d, int do_compile, char* buf, int cap) {
     const int v = validate_desc(d);
     if (v != MOLANN_OK) return v;
+    if (do_compile & 256) { // the backward of a wide fp32 head (molann_chain_bwd.inc), as plan creation would specialise it
+        if (d->n_layers <= 0) return MOLANN_E_STAGE;
+        if (d->mlp_precision != MOLANN_MLP_F32) return MOLANN_E_UNSUPPORTED;
+        const int act = d->activation;
+        if (!(act == 0 || act == 1 || act == 2 || act == 3 || act == 5 || act == 7)) return MOLANN_E_UNSUPPORTED;
+        ChainGeom cg;
+        memset(&cg, 0, sizeof(cg));
+        cg.nl = d->n_layers;
+        for (int i = 0; i <= d->n_layers; ++i) cg.dims[i] = d->layer_dims[i];
+        if (!chain_resident(cg)) return MOLANN_E_UNSUPPORTED;
+        std::vector<int> dims(d->layer_dims, d->layer_dims + d->n_layers + 1), kp, jp;
+        std::vector<long> woff;
+        long off = 0;
+        for (int l = 0; l < d->n_layers; ++l) {   // the plan's fp32 MFMA copy: Wp[Jp][Kp] then bias[Jp], 16-byte aligned
+            kp.push_back(ceil_to(dims[l], 16)); jp.push_back(ceil_to(dims[l + 1], 16)); woff.push_back(off);
+            off += (long)jp.back() * kp.back() + jp.back();
+            off = (off + 3) & ~3l;
+        }
+        const int waves = chain_bwd_waves(kp, jp);
+        if (waves <= 0) return MOLANN_E_UNSUPPORTED;
+        const std::string csrc = jit_source_chain_bwd(dims, kp, jp, woff, act, waves);
+        if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", csrc.c_str());
+        if (do_compile & 1) {
+            std::vector<char> code;
+            std::string log;
+            const int rc = jit_compile(csrc, code, log);
+            if (rc != 0) {
+                if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", log.c_str());
+                return rc > 0 ? rc : MOLANN_E_UNSUPPORTED;
+            }
+        }
+        return (int)csrc.size();
+    }
     if (do_compile & 4) { // the wide bf16 MLP kernel of the same plan (FB as plan creation would choose it)
         if (d->n_layers <= 0) return MOLANN_E_STAGE;
         ChainGeom cg;

@@ -227,6 +227,43 @@ std::string jit_source_mlp_bwd(const JitSpecBox& b, int wpb) {
     return s;
 }
 
+// backward of a wide fp32 head (molann_chain_bwd.inc): LDS floats of the kernel text's LDS_FLOATS - the weight copy at row
+// stride Kp + 4 with its biases, and the block's [unit][frame] tile of 16 WAVES frames (row stride + 4)
+long chain_bwd_lds_floats(const std::vector<int>& kp, const std::vector<int>& jp, int waves) {
+    long w = 0;
+    int rows = 0;
+    for (size_t l = 0; l < kp.size(); ++l) { w += (long)jp[l] * (kp[l] + 4) + jp[l]; rows = std::max(rows, jp[l] + kp[l]); }
+    return w + (long)rows * (16 * waves + 4);
+}
+// waves per block: four (a 64-frame tile) where weights and tile fit the CU's LDS, else fewer; 0 when not even one does
+int chain_bwd_waves(const std::vector<int>& kp, const std::vector<int>& jp) {
+    for (int w : {4, 2, 1})
+        if (chain_bwd_lds_floats(kp, jp, w) * 4 <= 163840) return w;
+    return 0;
+}
+
+std::string jit_source_chain_bwd(const std::vector<int>& dims, const std::vector<int>& kp, const std::vector<int>& jp,
+                                 const std::vector<long>& woff, int act, int waves) {
+    std::string s = "// preamble generated from the plan\n";
+    char t[128];
+    const int nl = (int)dims.size() - 1;
+    auto K = [&](const char* name, long v) { snprintf(t, sizeof(t), "constexpr int %s = %ld;\n", name, v); s += t; };
+    auto arr = [&](const char* name, const std::vector<long>& v) {
+        s += std::string("constexpr int ") + name + "[] = {";
+        for (size_t i = 0; i < v.size(); ++i) { snprintf(t, sizeof(t), "%s%ld", i ? ", " : "", v[i]); s += t; }
+        s += "};\n";
+    };
+    K("NL", nl); K("ACT", act); K("WAVES", waves);
+    std::vector<long> d(dims.begin(), dims.end()), k(kp.begin(), kp.end()), j(jp.begin(), jp.end()), goff;
+    long g = 0;
+    for (int l = 0; l < nl; ++l) { goff.push_back(g); g += (long)dims[l + 1] * dims[l] + dims[l + 1]; }
+    arr("DIMS", d); arr("KP", k); arr("JP", j); arr("WOFF", woff); arr("GOFF", goff);
+    K("N_PARAMS", g);
+    s += "#line 1 \"molann_chain_bwd.inc\"\n";
+    s += join_chunks(k_src_molann_chain_bwd_inc);
+    return s;
+}
+
 // One-pass backward (molann_bwd_ring.inc): loaders + consumers around the ring of compact tiles; every consumer owns a
 // buffer that is MLP scratch, gradient tile and parameter sums in turn.  Two waves per SIMD (256 VGPRs each).
 // fragments of the weights the one-pass backward keeps per lane (molann_bwd_ring.inc: frag_ids())

@@ -96,6 +96,9 @@ struct molann_plan {
     hipModule_t mbwd_mod;
     hipFunction_t mbwd_fn;     // backward of the fused family's MLP (molann_mlp_bwd.inc), compiled at the first backward
     int mbwd_state, mbwd_wpb;
+    hipModule_t cbwd_mod;
+    hipFunction_t cbwd_fn;     // backward of a wide fp32 head (molann_chain_bwd.inc), compiled at the first backward
+    int cbwd_state, cbwd_waves; // state: 0 not tried, 1 ready, -1 unavailable; waves: 0 when the plan's head is not one it serves
     // features-only twin of a forward kernel that has the MLP fused in (what molann_features_f32 and the backward's
     // recompute launch on such a plan), compiled at the first use
     struct JitSpecBox* align_spec;  // AlignmentLayer.forward as alignment + one position item per atom through the specialised kernel

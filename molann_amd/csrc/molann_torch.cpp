@@ -813,6 +813,116 @@ struct RunFunction : public torch::autograd::Function<RunFunction> {
     }
 };
 
+// The head of a forward plan whose backward is two nodes - the preprocessing's, then this one: a wide fp32 head that
+// molann_mlp_backward_f32 serves (molann_plan_supports_mlp_backward) where molann_plan_supports_backward does not.  Forward
+// molann_mlp_packed_f32 on the features, backward molann_mlp_backward_f32 on the same features; the parameters are repacked
+// whenever the live tensors changed (sync_live), so an optimiser's in-place step is seen by the next forward.
+at::Tensor activation(int64_t code, const at::Tensor& t);
+struct HeadFunction : public torch::autograd::Function<HeadFunction> {
+    static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& feat, std::vector<int64_t> desc, const at::Tensor& ref_x,
+                              at::TensorList weights, at::TensorList biases) {
+        at::AutoDispatchBelowADInplaceOrView below;
+        TORCH_CHECK(feat.dim() == 2 && feat.scalar_type() == at::kFloat && feat.is_cuda(), "molann::run_head: float32 device features [N, D] only");
+        const at::Tensor f = feat.contiguous();
+        const c10::DeviceGuard guard(f.device());
+        auto e = entry_for(desc, f, ref_x);
+        TORCH_CHECK(e->kind == KIND_FORWARD && f.size(1) == e->feature_dim, "molann::run_head: features are [*, ", e->feature_dim, "], got ", f.sizes());
+        const int64_t n = f.size(0);
+        at::Tensor out = at::empty({n, e->out_dim}, f.options());
+        {
+            hipStream_t stream = c10::hip::getCurrentHIPStream(f.get_device()).stream();
+            std::lock_guard<std::mutex> lock(e->mu);
+            sync_live(*e, f, ref_x, weights.vec(), biases.vec(), stream);
+            if (n > 0) check(molann_mlp_packed_f32(e->plan, f.data_ptr<float>(), n, out.data_ptr<float>(), stream), "molann_mlp_packed_f32");
+        }
+        std::vector<at::Tensor> saved = {feat, ref_x};
+        for (auto& w : weights) saved.push_back(w);
+        for (auto& b : biases) saved.push_back(b);
+        ctx->save_for_backward(saved);
+        ctx->saved_data["desc"] = desc;
+        ctx->saved_data["n_layers"] = (int64_t)weights.size();
+        return out;
+    }
+
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grad_outputs) {
+        const auto sv = ctx->get_saved_variables();
+        const std::vector<int64_t> desc = ctx->saved_data["desc"].toIntVector();
+        const int64_t nl = ctx->saved_data["n_layers"].toInt();
+        const at::Tensor& f = sv[0];
+        const at::Tensor& ref_x = sv[1];
+        std::vector<at::Tensor> weights(sv.begin() + 2, sv.begin() + 2 + nl), biases(sv.begin() + 2 + nl, sv.begin() + 2 + 2 * nl);
+        // graph edges: feat, ref_x, weights..., biases...; returned list (all inputs): feat, desc, ref_x, weights..., biases...
+        torch::autograd::variable_list out(3 + 2 * nl);
+        const bool need_f = ctx->needs_input_grad(0);
+        bool need_p = false;
+        for (int64_t i = 0; i < 2 * nl; ++i) need_p = need_p || ctx->needs_input_grad(2 + i);
+        if (at::GradMode::is_enabled()) {
+            // create_graph=True: the head rebuilt as ATen ops on the live parameters (and the features with their own graph),
+            // differentiated with a graph
+            std::vector<at::Tensor> inputs;
+            std::vector<size_t> slot;
+            if (need_f) { inputs.push_back(f); slot.push_back(0); }
+            for (int64_t l = 0; l < 2 * nl; ++l)
+                if (ctx->needs_input_grad(2 + l)) { inputs.push_back(l < nl ? weights[l] : biases[l - nl]); slot.push_back(3 + l); }
+            if (inputs.empty()) return out;
+            at::Tensor h = f;
+            for (int64_t l = 0; l < nl; ++l) {
+                h = at::linear(h, weights[l], biases[l]);
+                if (l + 1 < nl) h = activation(desc[7], h);
+            }
+            const auto g = torch::autograd::grad({h}, inputs, {grad_outputs[0]}, /*retain_graph=*/true, /*create_graph=*/true, /*allow_unused=*/true);
+            for (size_t i = 0; i < g.size(); ++i) out[slot[i]] = g[i];
+            return out;
+        }
+        if (!need_f && !need_p) return out;
+        const at::Tensor fc = f.contiguous();
+        const int64_t n = fc.size(0);
+        const c10::DeviceGuard guard(fc.device());
+        auto e = entry_for(desc, fc, ref_x);
+        at::Tensor g = grad_outputs[0].to(at::kFloat).reshape({n, e->out_dim}).contiguous();
+        at::Tensor gf = need_f ? at::empty_like(fc) : at::Tensor();
+        at::Tensor gp = need_p ? at::zeros({molann_plan_grad_params_size(e->plan)}, fc.options()) : at::Tensor();
+        if (n > 0) {
+            hipStream_t stream = c10::hip::getCurrentHIPStream(fc.get_device()).stream();
+            std::lock_guard<std::mutex> lock(e->mu);
+            sync_live(*e, fc, ref_x, weights, biases, stream);
+            check(molann_mlp_backward_f32(e->plan, fc.data_ptr<float>(), g.data_ptr<float>(), n, need_f ? gf.data_ptr<float>() : nullptr,
+                                          need_p ? gp.data_ptr<float>() : nullptr, stream),
+                  "molann_mlp_backward_f32");
+        }
+        if (need_f) out[0] = gf;
+        if (need_p) {
+            int64_t off = 0;
+            for (int64_t l = 0; l < nl; ++l) { // flat layout: dW_l[J][K] then db_l[J], layer after layer
+                const int64_t nw = weights[l].numel(), nb = biases[l].numel();
+                if (ctx->needs_input_grad(2 + l)) out[3 + l] = gp.narrow(0, off, nw).view(weights[l].sizes());
+                if (ctx->needs_input_grad(2 + nl + l)) out[3 + nl + l] = gp.narrow(0, off + nw, nb).view(biases[l].sizes());
+                off += nw + nb;
+            }
+        }
+        return out;
+    }
+};
+
+// whether the head of `desc` runs as HeadFunction under autograd (float32 device input, a forward plan)
+bool head_node(const std::vector<int64_t>& desc, const at::Tensor& x, const at::Tensor& ref_x) {
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    return molann_plan_supports_mlp_backward(e->plan) == 1;
+}
+
+// molann::run_head: the head node on features the caller computed (MolANN.forward: its preprocessing layer's output)
+at::Tensor run_head(const at::Tensor& feat, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                    std::vector<at::Tensor> biases) {
+    TORCH_CHECK(desc.size() >= DESC_HEAD && desc[1] == KIND_FORWARD, "molann::run_head: a forward descriptor");
+    return HeadFunction::apply(feat, desc, ref_x, at::TensorList(weights), at::TensorList(biases));
+}
+
+int64_t supports_mlp_backward(const at::Tensor& x, std::vector<int64_t> desc, const at::Tensor& ref_x) {
+    TORCH_CHECK(x.is_cuda(), "molann::supports_mlp_backward: x must be a device tensor");
+    return head_node(desc, x, ref_x) ? 1 : 0;
+}
+
 // the plan of `desc` without its MLP (what PreprocessingANN.forward launches)
 std::vector<int64_t> features_only(const std::vector<int64_t>& desc) {
     const int64_t n_layers = desc[6];
@@ -873,6 +983,11 @@ at::Tensor run_autograd(const at::Tensor& x, std::vector<int64_t> desc, const at
                 const c10::DeviceGuard guard(x.device());
                 fused_backward = molann_plan_supports_backward(entry_for(desc, x, ref_x)->plan) == 1;
             }
+            if (!fused_backward && x.scalar_type() == at::kFloat && head_node(desc, x, ref_x)) {
+                // the preprocessing's node (its HIP backward), then the head's (molann_chain_bwd)
+                at::Tensor f = call_run(x, features_only(desc), ref_x, {}, {});
+                return HeadFunction::apply(f, desc, ref_x, at::TensorList(weights), at::TensorList(biases));
+            }
             if (!fused_backward) {
                 at::Tensor h = call_run(x, features_only(desc), ref_x, {}, {});
                 for (size_t l = 0; l < weights.size(); ++l) {
@@ -902,6 +1017,8 @@ TORCH_LIBRARY(molann, m) {
     m.def("value_and_vjp_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor grad_out, Tensor[] into) -> Tensor[]");
     m.def("value_and_vjp(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor grad_out, Tensor[] into) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
+    m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
+    m.def("run_head(Tensor feat, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases) -> Tensor", run_head);
     m.def("launch_info(int[] desc, int device) -> str", launch_info);
     m.def("invalidate(int[] desc, int device) -> ()", invalidate);
     m.def("release(int[] desc, int device) -> ()", release);
