@@ -1306,7 +1306,8 @@ int molann_backward_f32(molann_plan* p, const float* x, const float* grad_out, i
             if (grad_x && (rc = launch_wave_bwd(p, xs, wg, m, grad_x + s * (long)p->n_inp * 3, main)) != 0) break;
             if (s == 0 && grad_x) snprintf(info[2], sizeof(info[2]), "%.95s", p->last_info);
         }
-        if (rc == MOLANN_OK) snprintf(p->last_info, sizeof(p->last_info), "%.80s || %.80s || %.80s", info[0], info[1], info[2]);
+        if (rc == MOLANN_OK)
+            snprintf(p->last_info, sizeof(p->last_info), "%.72s || %.72s || %.72s || chunks of %ld frames", info[0], info[1], info[2], p->bwork_frames);
         return rc;
     }
     if (!p->spec || p->n_items <= 0) return MOLANN_E_UNSUPPORTED;
@@ -1352,7 +1353,8 @@ int molann_backward_f32(molann_plan* p, const float* x, const float* grad_out, i
         if (grad_x && (rc = launch_features_bwd(p, g, xs, wg, m, grad_x + s * (long)p->n_inp * 3, main)) != 0) break;
         if (s == 0 && grad_x) snprintf(info[2], sizeof(info[2]), "%.95s", p->last_info);
     }
-    if (rc == MOLANN_OK) snprintf(p->last_info, sizeof(p->last_info), "%.80s || %.80s || %.80s", info[0], info[1], info[2]);
+    if (rc == MOLANN_OK)
+        snprintf(p->last_info, sizeof(p->last_info), "%.72s || %.72s || %.72s || chunks of %ld frames", info[0], info[1], info[2], p->bwork_frames);
     return rc;
 }
 

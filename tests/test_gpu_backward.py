@@ -163,18 +163,31 @@ def test_alignment_layer_gradient(hip_device):
     assert float((x.grad.cpu().double() - xx.grad).abs().max()) <= 2e-4 * scale
 
 
-@pytest.mark.parametrize("cfg", ["C4", "C5"])
-def test_large_frames_gradients(cfg, hip_device):
+def _dihedral_poles(x, w):
+    """Per frame: a dihedral of the workload with a bond angle whose sine is below 0.05 (within ~3 degrees of 0 or 180)."""
+    bad = torch.zeros(x.shape[0], dtype=torch.bool)
+    for t, atoms in w.features:
+        if t == wl.DIHEDRAL:
+            i = [a - 1 for a in atoms]
+            for a, b, c in (i[:3], i[1:]):
+                u, v = x[:, a] - x[:, b], x[:, c] - x[:, b]
+                bad |= torch.linalg.cross(u, v).norm(dim=1) < 0.05 * u.norm(dim=1) * v.norm(dim=1)
+    return bad
+
+
+@pytest.mark.parametrize("cfg,n", [("C4", 6), ("C5", 6), ("C4", 1000), ("C5", 1000)], ids=["C4", "C5", "C4-1000", "C5-1000"])
+def test_large_frames_gradients(cfg, n, hip_device):
     """Wave-per-frame plans: dL/dx from frames_wave_bwd_gather_kernel (features) chained with the torch MLP, parameter
     gradients from torch; against autograd through the fp64 oracle."""
     big = wl.get_workload(cfg)
     model = wl.build_model(big, hip_device)
     if cfg == "C5":
         model.mlp_precision = "f32"                 # compare like with like: the oracle is not a bf16 model
-    n = 6
     x = big.make_frames(n, seed=3)
     xg = x.to(hip_device).requires_grad_(True)
     G = torch.randn((n, big.out_dim()), generator=torch.Generator().manual_seed(4))
+    if n > 6:                                       # a dihedral's bond angle within ~3 degrees of 0 or 180: ill-conditioned in fp32
+        G[_dihedral_poles(x, big)] = 0.0
     y = model(xg)
     (y * G.to(hip_device)).sum().backward()
     from molann_amd.ann import last_launch_info
