@@ -221,9 +221,17 @@ int molann_backward_f32(molann_plan* plan, const float* x, const float* grad_out
  * backward recomputes the forward per frame anyway; this build of it also stores the outputs.  For a host that differentiates a
  * small batch at every step (a collective variable and its forces inside an MD engine, README.rst:49): one launch instead of a
  * forward and a backward.  The Jacobian of one frame: a batch of out_dim copies of it with the identity as grad_out.  Parameters
- * are data (no parameter gradients).  Plans with molann_plan_backward_kind == 2, else MOLANN_E_UNSUPPORTED.  First call: hipRTC. */
+ * are data (no parameter gradients).  Served: plans with molann_plan_backward_kind == 2, and frames too large for the lane
+ * kernels (mid-size and large frames, backward kind 1) whose head is within the fused MLP's limits - every width and the feature
+ * dimension <= 32, <= 4 layers, fp32, tanh / ReLU / sigmoid / identity / SiLU / LeakyReLU - or that have no head: one
+ * plan-specialised kernel (molann_group_vjp) for forward_train + mlp_backward + features_backward.  MOLANN_E_UNSUPPORTED otherwise
+ * (see molann_plan_supports_value_and_vjp).  First call: hipRTC, outside a capture; after that the call only enqueues on
+ * `stream` (no workspace, no event): thread-safe and capturable. */
 int molann_value_and_vjp_f32(molann_plan* plan, const float* x, const float* grad_out, int64_t n_frames, float* out,
                              float* grad_x, molann_stream_t stream);
+
+/* 1 when molann_value_and_vjp_f32 serves the plan, 0 otherwise.  Builds the kernel it reports (call it before a capture). */
+int molann_plan_supports_value_and_vjp(molann_plan* plan);
 
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
@@ -264,7 +272,8 @@ int molann_plan_last_launch_info(const molann_plan* plan, char* buf, int cap);
 
 /* Diagnostic / test hook: the source of the plan-specialised lane kernel for a description (copied to
  * buf, NUL-terminated, at most cap bytes) and, if do_compile != 0, a hipRTC compile of it for gfx950 (no
- * GPU needed).  do_compile bit 0: compile; bit 1: the backward kernel instead of the forward one.
+ * GPU needed).  do_compile bit 0: compile; bit 1: the backward kernel instead of the forward one; bit 9 (512): the one-launch
+ * values + vector-Jacobian product of frames the lane kernels do not take (molann_group_vjp), as a plan would specialise it.
  * Returns the source length; on a compile failure a positive hiprtcResult and the log in buf. */
 int molann_debug_jit(const molann_plan_desc* desc, int do_compile, char* buf, int cap);
 

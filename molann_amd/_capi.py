@@ -98,6 +98,7 @@ def lib():
             "molann_plan_supports_backward": (i32, [vp]),
             "molann_plan_backward_kind": (i32, [vp]),
             "molann_plan_supports_mlp_backward": (i32, [vp]),
+            "molann_plan_supports_value_and_vjp": (i32, [vp]),
             "molann_backward_f32": (i32, [vp, vp, vp, i64, vp, vp, vp]),
             "molann_value_and_vjp_f32": (i32, [vp, vp, vp, i64, vp, vp, vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
@@ -279,6 +280,10 @@ class Plan(object):
         """True when `mlp_backward` serves this plan's head (the fused family's kernel, or the wide fp32 head's)."""
         return lib().molann_plan_supports_mlp_backward(self._handle) == 1
 
+    def supports_value_and_vjp(self):
+        """True when `value_and_vjp` serves this plan (one launch); builds that kernel, so call it before a graph capture."""
+        return lib().molann_plan_supports_value_and_vjp(self._handle) == 1
+
     def backward_kind(self):
         """2: `backward` is one pass over x; 1: several launches (keep the features of the forward: `forward_train`); 0: none."""
         return lib().molann_plan_backward_kind(self._handle)
@@ -296,7 +301,8 @@ class Plan(object):
             raise MolannHipError(code, "molann_backward_f32")
 
     def value_and_vjp(self, x, grad_out, out, grad_x):
-        """out = forward(x) and grad_x = the vector-Jacobian product for `grad_out`, one launch (plans with backward_kind() == 2)."""
+        """out = forward(x) and grad_x = the vector-Jacobian product for `grad_out`, one launch (plans for which
+        `supports_value_and_vjp()` holds)."""
         code = _lib.molann_value_and_vjp_f32(self._handle, x.data_ptr(), grad_out.data_ptr(), x.shape[0], out.data_ptr(), grad_x.data_ptr(),
                                              torch.cuda.current_stream().cuda_stream)
         if code != 0:

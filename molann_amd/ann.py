@@ -772,10 +772,12 @@ class MolANN(_PlanOwner, torch.nn.Module):
         For a caller that needs a collective variable and its forces at every step (`README.rst:49`): ~half the host time of a
         forward plus a backward.  The Jacobian of one frame: ``x.expand(d_out, -1, -1)`` with ``torch.eye(d_out)`` as cotangent.
         No autograd graph is recorded (parameters are data); ``into=(y, dx)`` reuses the caller's buffers.  Models served by one
-        fused plan whose backward is the one-pass kernel, float32."""
+        fused plan whose backward is the one-pass kernel, and models on larger frames (molann_group_vjp) with no head or a head of
+        at most 4 layers, every width <= 32, fp32, tanh / ReLU / sigmoid / identity / SiLU / LeakyReLU; float32."""
         st = self._fast_state(x) if isinstance(x, torch.Tensor) and x.is_cuda else None
         if st is None or not st["fused"]:
-            raise NotImplementedError("value_and_vjp needs a model served by one fused plan on a HIP device")
+            raise NotImplementedError("value_and_vjp needs a model served by one fused plan on a HIP device (a feature layer and a "
+                                      "Linear / activation head, float32, on a HIP tensor)")
         al, fl = st["al"], st["fl"]
         _check_input(x, fl.input_atom_num)
         if x.dtype != torch.float32:
@@ -787,12 +789,29 @@ class MolANN(_PlanOwner, torch.nn.Module):
             y, dx = st["op_vjp"](x, st["handle"], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"],
                                  [lin.weight for lin in lins], [lin.bias for lin in lins], grad_out, list(into) if into is not None else [])
             return y, dx
+        n, out_dim = x.shape[0], st["out_dim"]
+        if not isinstance(grad_out, torch.Tensor) or grad_out.numel() != n * out_dim or grad_out.device != x.device:
+            raise ValueError("value_and_vjp: grad_out must hold [%d, %d] values on %s" % (n, out_dim, x.device))
+        if into is not None:
+            if len(into) != 2 or not all(isinstance(t, torch.Tensor) for t in into):
+                raise TypeError("value_and_vjp: `into` must be a pair of tensors (y, dx)")
+            y, dx = into
+            if y.dtype != torch.float32 or dx.dtype != torch.float32:
+                raise TypeError("value_and_vjp: `into` must be float32; got %s, %s" % (y.dtype, dx.dtype))
+            if not (y.is_contiguous() and dx.is_contiguous()) or y.numel() != n * out_dim or dx.numel() != x.numel() \
+                    or y.device != x.device or dx.device != x.device:
+                raise ValueError("value_and_vjp: `into` must be contiguous {[%d, %d], %s} on %s" % (n, out_dim, tuple(x.shape), x.device))
         entry = st["entry"]()
         with torch.cuda.device(x.device):
             if al is not None:
                 entry.sync_ref(_device_buffer(al.ref_x, x))
             entry.sync_mlp(lins)
-            y, dx = into if into is not None else (torch.empty((x.shape[0], st["out_dim"]), dtype=torch.float32, device=x.device), torch.empty_like(x))
+            if not entry.plan.supports_value_and_vjp():
+                raise NotImplementedError("value_and_vjp: no single-launch kernel for this model: it serves the one-pass backward's plans "
+                                          "and larger frames with no head or a head of at most 4 layers, every width <= 32, fp32, "
+                                          "tanh / ReLU / sigmoid / identity / SiLU / LeakyReLU")
+            if into is None:
+                y, dx = torch.empty((n, out_dim), dtype=torch.float32, device=x.device), torch.empty_like(x)
             g = grad_out if (grad_out.dtype == torch.float32 and grad_out.is_contiguous()) else grad_out.float().contiguous()
             entry.plan.value_and_vjp(x, g, y, dx)
         return y, dx

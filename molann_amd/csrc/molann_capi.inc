@@ -39,30 +39,7 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
 
     // ---- expand the feature list into items (column order = list order, ann.py:473) ------------
     std::vector<ItemDev> items;
-    int col = 0;
-    for (int f = 0; f < d->n_features; ++f) {
-        const int* idx = d->feat_idx + d->feat_ptr[f];
-        const int cnt = d->feat_ptr[f + 1] - d->feat_ptr[f];
-        const int t = d->feat_type[f];
-        if (t == MOLANN_FEAT_POSITION) {
-            for (int i = 0; i < cnt; ++i) {
-                ItemDev it = {IT_POSITION, col, {idx[i], idx[i], idx[i], idx[i]}, {0, 0}};
-                items.push_back(it);
-                col += 3;
-            }
-        } else {
-            ItemDev it;
-            it.type = t == MOLANN_FEAT_ANGLE ? (d->use_angle_value ? IT_ANGLE_VAL : IT_ANGLE_COS)
-                      : t == MOLANN_FEAT_BOND ? IT_BOND
-                                              : (d->use_angle_value ? IT_DIHEDRAL_VAL : IT_DIHEDRAL_CS);
-            it.col = col;
-            for (int i = 0; i < 4; ++i) it.idx[i] = idx[i < cnt ? i : 0];
-            it.pad[0] = it.pad[1] = 0;
-            items.push_back(it);
-            col += item_width(it.type);
-        }
-    }
-    const int d_feat = col;
+    const int d_feat = expand_items(d, items);
     if (d->n_layers > 0 && d->n_features > 0 && d->layer_dims[0] != d_feat) return MOLANN_E_DESC;
 
     int dev = 0;
@@ -214,6 +191,14 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
     }
     p->bw_touched = (int)bw_atoms.size();
     p->bw_list_len = (int)bw_list.size();
+    // values + vjp in one launch (molann_group_vjp.inc): the same lists for every alignment set, rows named twice included
+    std::vector<int> va_atoms, va_ptr, va_list;
+    if (!p->geom[0].ok && p->n_items > 0) group_vjp_tables(d->n_inp, items, d->align_idx, d->n_align, va_atoms, va_ptr, va_list);
+    p->va_touched = (int)va_atoms.size();
+    p->va_list_len = (int)va_list.size();
+    const size_t o_va_atoms = carve(sizeof(int) * std::max<size_t>(1, va_atoms.size()));
+    const size_t o_va_ptr = carve(sizeof(int) * std::max<size_t>(1, va_ptr.size()));
+    const size_t o_va_list = carve(sizeof(int) * std::max<size_t>(1, va_list.size()));
     // AlignmentLayer.forward under autograd arrives as a feature plan with ONE position item per atom, in atom order: its
     // feature rows are the aligned frame, its backward the dense gradient of the alignment (frames_align_bwd_regs_kernel)
     std::vector<int> align_slot;
@@ -330,6 +315,7 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
     p->d_bw_atoms = (int*)(p->blob + o_bw_atoms); p->d_bw_ptr = (int*)(p->blob + o_bw_ptr);
     p->d_bw_list = (int*)(p->blob + o_bw_list); p->d_bw_align = (int*)(p->blob + o_bw_align);
     p->d_align_slot = (int*)(p->blob + o_align_slot);
+    p->d_va_atoms = (int*)(p->blob + o_va_atoms); p->d_va_ptr = (int*)(p->blob + o_va_ptr); p->d_va_list = (int*)(p->blob + o_va_list);
     p->d_wlane = (float*)(p->blob + o_wlane);
     p->d_wmfma = (void*)(p->blob + o_wmfma);
     p->d_work = (float*)(p->blob + o_work);
@@ -383,6 +369,11 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
         if (e == hipSuccess && !bw_list.empty()) e = hipMemcpy(p->d_bw_list, bw_list.data(), sizeof(int) * bw_list.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess && !align_slot.empty()) e = hipMemcpy(p->d_align_slot, align_slot.data(), sizeof(int) * align_slot.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(p->d_bw_align, bw_align.data(), sizeof(int) * bw_align.size(), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && p->va_touched > 0) {
+        e = hipMemcpy(p->d_va_atoms, va_atoms.data(), sizeof(int) * va_atoms.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(p->d_va_ptr, va_ptr.data(), sizeof(int) * va_ptr.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(p->d_va_list, va_list.data(), sizeof(int) * va_list.size(), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) { (void)hipFree(p->blob); delete p; return (int)e; }
     snprintf(p->last_info, sizeof(p->last_info), "(no launch yet)");
@@ -594,6 +585,7 @@ int molann_plan_destroy(molann_plan* p) {
     if (p->cbwd_mod) (void)hipModuleUnload(p->cbwd_mod);
     if (p->rbwd_mod) (void)hipModuleUnload(p->rbwd_mod);
     if (p->vjp_mod) (void)hipModuleUnload(p->vjp_mod);
+    if (p->gvjp_mod) (void)hipModuleUnload(p->gvjp_mod);
     if (p->wide_mod) (void)hipModuleUnload(p->wide_mod);
     if (p->feat_mod) (void)hipModuleUnload(p->feat_mod);
     if (p->train_mod) (void)hipModuleUnload(p->train_mod);
@@ -1358,21 +1350,9 @@ int molann_backward_f32(molann_plan* p, const float* x, const float* grad_out, i
     return rc;
 }
 
-// The forward's outputs AND the vector-Jacobian product of a batch in ONE launch: the one-pass backward recomputes the forward per
-// frame anyway, so a build of it that also stores the outputs (WITH_VALUES: one more product on the matrix cores, from the
-// activations already in its scratch) returns both.  For callers that differentiate a small batch at every step with a cotangent
-// they know up front - or want the Jacobian: a batch of d_out copies of a frame with the identity as cotangent (README.rst:49's
-// use, a collective variable inside an MD engine).  Parameters are data here (no parameter gradients).  Plans the one-pass
-// backward serves (molann_plan_backward_kind == 2); E_UNSUPPORTED otherwise.  The first call builds the kernel: outside a capture.
-int molann_value_and_vjp_f32(molann_plan* p, const float* x, const float* grad_out, int64_t n, float* out, float* grad_x, molann_stream_t stream) {
-    if (!p) return MOLANN_E_NULL;
-    if (n < 0) return MOLANN_E_DESC;
-    if (n == 0) return MOLANN_OK;
-    if (!x || !grad_out || !out || !grad_x) return MOLANN_E_NULL;
-    if ((((uintptr_t)x) & 3) || (((uintptr_t)grad_out) & 3) || (((uintptr_t)grad_x) & 3) || (((uintptr_t)out) & 3)) return MOLANN_E_ALIGNMENT;
-    if (!p->spec || p->n_items <= 0 || !p->geom[0].ok) return MOLANN_E_UNSUPPORTED;
-    if (p->n_layers > 0 && (!molann_plan_supports_backward(p) || !p->fused_mlp)) return MOLANN_E_UNSUPPORTED;
-    if (p->n_layers > 0 && !p->mlp_packed) return MOLANN_E_NOT_PACKED;
+namespace {
+// the one-pass backward's build that also stores the forward's outputs (molann_bwd_ring.inc, WITH_VALUES), built at the first use
+int ensure_ring_vjp(molann_plan* p) {
     const int er = ensure_ring_bwd(p);       // the geometry is the one-pass backward's
     if (er != MOLANN_OK) return er;
     if (p->vjp_state == 0) {
@@ -1401,8 +1381,118 @@ int molann_value_and_vjp_f32(molann_plan* p, const float* x, const float* grad_o
             p->vjp_state = st;
         }
     }
-    if (p->vjp_state != 1) return MOLANN_E_UNSUPPORTED;
+    return p->vjp_state == 1 ? MOLANN_OK : MOLANN_E_UNSUPPORTED;
+}
+
+// Frames the lane kernels do not take (mid-size and large): molann_group_vjp.inc, for heads within the fused MLP's limits (every
+// width and the feature dimension <= 32, <= 4 layers, fp32; tanh, ReLU, sigmoid, identity, SiLU, LeakyReLU - the fp32 MFMA
+// copy of the weights is packed for every plan) and for features-only plans.  Built at the first use; E_UNSUPPORTED where the
+// tables do not fit the LDS at B >= 2 or hipRTC is missing.
+bool group_vjp_serves(const molann_plan* p) {
+    if (p->geom[0].ok || p->n_items <= 0 || p->va_touched <= 0 || !rtc_api()->ok) return false;
+    if (p->n_layers == 0) return true;
+    const int act = p->act;
+    if (p->mlp_prec != MOLANN_MLP_F32 || p->n_layers > LANE_MLP_MAX_LAYERS || p->d_feat > LANE_MLP_MAX_WIDTH) return false;
+    for (int l = 1; l <= p->n_layers; ++l)
+        if (p->dims[l] > LANE_MLP_MAX_WIDTH) return false;
+    return act == 0 || act == 1 || act == 2 || act == 3 || act == 5 || act == 7;
+}
+
+int ensure_group_vjp(molann_plan* p) {
+    if (!group_vjp_serves(p)) return MOLANN_E_UNSUPPORTED;
+    if (p->gvjp_state == 0) {
+        std::lock_guard<std::mutex> lock(*p->jit_mu);
+        if (p->gvjp_state == 0) {
+            int st = -1;
+            const int nl = p->n_layers;
+            std::vector<int> dims, kp, jp;
+            std::vector<long> woff;
+            if (nl > 0) {
+                dims.assign(p->dims, p->dims + nl + 1); kp.assign(p->kp, p->kp + nl); jp.assign(p->jp, p->jp + nl); woff.assign(p->moff, p->moff + nl);
+            }
+            GroupVjpGeom g;
+            if (group_vjp_geometry(dims, p->act, p->d_feat, p->n_align, p->n_items, p->va_touched, p->va_list_len, g)) {
+                std::vector<char> code;
+                std::string log;
+                hipModule_t mod = nullptr;
+                hipFunction_t fn = nullptr;
+                const int rc = jit_compile(jit_source_group_vjp(dims, kp, jp, woff, p->act, p->d_feat, p->n_inp, p->n_align, p->n_items, p->va_touched,
+                                                                p->va_list_len, g), code, log);
+                if (rc == 0 && hipModuleLoadData(&mod, code.data()) == hipSuccess && hipModuleGetFunction(&fn, mod, "molann_group_vjp") == hipSuccess) {
+                    // blocks per CU at the launch's block size: all WPB waves (batches of at most one tile per CU), or half of them
+                    const int waves = g.wpb > 1 ? g.wpb / 2 : 1;
+                    int occ = 0;
+                    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64 * waves, 0) != hipSuccess || occ < 1)
+                        occ = std::max(1, std::min(163840 / g.lds, 32 / waves));
+                    p->gvjp_mod = mod; p->gvjp_fn = fn;
+                    p->gvjp_b = g.b; p->gvjp_wpb = g.wpb; p->gvjp_lds = g.lds; p->gvjp_bpc = occ;
+                    st = 1;
+                } else {
+                    if (mod) (void)hipModuleUnload(mod);
+                    if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann group value + vjp build failed rc=%d\n%s\n", rc, log.c_str());
+                }
+            }
+            p->gvjp_state = st;
+        }
+    }
+    return p->gvjp_state == 1 ? MOLANN_OK : MOLANN_E_UNSUPPORTED;
+}
+
+// one block per 64-frame tile (tiles strided over the blocks): WPB waves per block while the batch has at most one tile per CU
+// (latency: a round per wave), else half of them and as many blocks as the CUs hold.  No workspace, nothing but the enqueue.
+int launch_group_vjp(molann_plan* p, const float* x, const float* grad_out, long n, float* out, float* grad_x, hipStream_t stream) {
+    const long n_tiles = (n + 63) / 64;
+    const bool wide = n_tiles <= p->num_cus || p->gvjp_wpb == 1;
+    const int waves = wide ? p->gvjp_wpb : p->gvjp_wpb / 2;
+    const int grid = (int)std::max<long>(1, std::min<long>((long)p->num_cus * (wide ? 1 : p->gvjp_bpc), n_tiles));
+    struct { const float* x; const float* gout; const double* ref64; const float* ref32; const int* align; const int* items; const int* atoms;
+             const int* ptr; const int* list; const float* wnat; float* out; float* gx; long n; } ka =
+        {x, grad_out, p->d_ref64, p->d_ref, p->d_align_idx, (const int*)p->d_items, p->d_va_atoms, p->d_va_ptr, p->d_va_list,
+         (const float*)p->d_wmfma, out, grad_x, n};
+    size_t ksz = sizeof(ka);
+    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ka, HIP_LAUNCH_PARAM_BUFFER_SIZE, &ksz, HIP_LAUNCH_PARAM_END};
+    const hipError_t le = hipModuleLaunchKernel(p->gvjp_fn, grid, 1, 1, 64 * waves, 1, 1, 0, stream, nullptr, cfg);
+    if (le != hipSuccess) return (int)le;
+    snprintf(p->last_info, sizeof(p->last_info), "molann_group_vjp<B=%d> (values + vjp in one launch; %d waves per 64-frame tile) grid=%d block=%d lds=%d",
+             p->gvjp_b, waves, grid, 64 * waves, p->gvjp_lds);
+    return MOLANN_OK;
+}
+} // namespace
+
+// The forward's outputs AND the vector-Jacobian product of a batch in ONE launch: the one-pass backward recomputes the forward per
+// frame anyway, so a build of it that also stores the outputs (WITH_VALUES: one more product on the matrix cores, from the
+// activations already in its scratch) returns both.  For callers that differentiate a small batch at every step with a cotangent
+// they know up front - or want the Jacobian: a batch of d_out copies of a frame with the identity as cotangent (README.rst:49's
+// use, a collective variable inside an MD engine).  Parameters are data here (no parameter gradients).  Plans the one-pass
+// backward serves (molann_plan_backward_kind == 2), and frames the lane kernels do not take (molann_group_vjp.inc: the three
+// launches of their backward as one); E_UNSUPPORTED otherwise.  The first call builds the kernel: outside a capture.
+int molann_value_and_vjp_f32(molann_plan* p, const float* x, const float* grad_out, int64_t n, float* out, float* grad_x, molann_stream_t stream) {
+    if (!p) return MOLANN_E_NULL;
+    if (n < 0) return MOLANN_E_DESC;
+    if (n == 0) return MOLANN_OK;
+    if (!x || !grad_out || !out || !grad_x) return MOLANN_E_NULL;
+    if ((((uintptr_t)x) & 3) || (((uintptr_t)grad_out) & 3) || (((uintptr_t)grad_x) & 3) || (((uintptr_t)out) & 3)) return MOLANN_E_ALIGNMENT;
+    if (!p->geom[0].ok) {
+        const int er = ensure_group_vjp(p);
+        if (er != MOLANN_OK) return er;
+        if (p->n_layers > 0 && !p->mlp_packed) return MOLANN_E_NOT_PACKED;
+        return launch_group_vjp(p, x, grad_out, (long)n, out, grad_x, (hipStream_t)stream);
+    }
+    if (!p->spec || p->n_items <= 0) return MOLANN_E_UNSUPPORTED;
+    if (p->n_layers > 0 && (!molann_plan_supports_backward(p) || !p->fused_mlp)) return MOLANN_E_UNSUPPORTED;
+    if (p->n_layers > 0 && !p->mlp_packed) return MOLANN_E_NOT_PACKED;
+    const int er = ensure_ring_vjp(p);
+    if (er != MOLANN_OK) return er;
     return launch_ring_bwd(p, x, grad_out, (long)n, grad_x, nullptr, (hipStream_t)stream, out);
+}
+
+// 1 when molann_value_and_vjp_f32 serves the plan, 0 otherwise.  Builds the kernel it reports.
+int molann_plan_supports_value_and_vjp(molann_plan* p) {
+    if (!p) return MOLANN_E_NULL;
+    if (!p->geom[0].ok) return ensure_group_vjp(p) == MOLANN_OK ? 1 : 0;
+    if (!p->spec || p->n_items <= 0) return 0;
+    if (p->n_layers > 0 && (!molann_plan_supports_backward(p) || !p->fused_mlp)) return 0;
+    return ensure_ring_vjp(p) == MOLANN_OK ? 1 : 0;
 }
 
 // how molann_backward_f32 will serve this plan: 2 one pass over x (nothing worth saving from the forward), 1 two kernels
@@ -1477,6 +1567,43 @@ int molann_mlp_backward_f32(molann_plan* p, const float* f, const float* grad_ou
 int molann_debug_jit(const molann_plan_desc* d, int do_compile, char* buf, int cap) {
     const int v = validate_desc(d);
     if (v != MOLANN_OK) return v;
+    if (do_compile & 512) { // values + vjp in one launch for frames the lane kernels do not take (molann_group_vjp.inc), as the plan would build it
+        std::vector<ItemDev> items;
+        const int d_feat = expand_items(d, items);
+        if (items.empty()) return MOLANN_E_UNSUPPORTED;
+        std::vector<int> dims, kp, jp;
+        std::vector<long> woff;
+        if (d->n_layers > 0) {   // the heads the plan's mlp_spec describes (the fused MLP's limits), with a served activation
+            const int act = d->activation;
+            if (d->mlp_precision != MOLANN_MLP_F32 || d->n_layers > LANE_MLP_MAX_LAYERS || d_feat > LANE_MLP_MAX_WIDTH) return MOLANN_E_UNSUPPORTED;
+            if (!(act == 0 || act == 1 || act == 2 || act == 3 || act == 5 || act == 7)) return MOLANN_E_UNSUPPORTED;
+            dims.assign(d->layer_dims, d->layer_dims + d->n_layers + 1);
+            for (int v : dims) if (v > LANE_MLP_MAX_WIDTH) return MOLANN_E_UNSUPPORTED;
+            long off = 0;
+            for (int l = 0; l < d->n_layers; ++l) {   // the plan's fp32 MFMA copy: Wp[Jp][Kp] then bias[Jp], 16-byte aligned
+                kp.push_back(ceil_to(dims[l], 16)); jp.push_back(ceil_to(dims[l + 1], 16)); woff.push_back(off);
+                off += (long)jp.back() * kp.back() + jp.back();
+                off = (off + 3) & ~3l;
+            }
+        }
+        std::vector<int> atoms, ptr, list;
+        group_vjp_tables(d->n_inp, items, d->align_idx, d->n_align, atoms, ptr, list);
+        GroupVjpGeom g;
+        if (!group_vjp_geometry(dims, d->activation, d_feat, d->n_align, (int)items.size(), (int)atoms.size(), (int)list.size(), g)) return MOLANN_E_UNSUPPORTED;
+        const std::string src = jit_source_group_vjp(dims, kp, jp, woff, d->activation, d_feat, d->n_inp, d->n_align, (int)items.size(), (int)atoms.size(),
+                                                     (int)list.size(), g);
+        if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", src.c_str());
+        if (do_compile & 1) {
+            std::vector<char> code;
+            std::string log;
+            const int rc = jit_compile(src, code, log);
+            if (rc != 0) {
+                if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", log.c_str());
+                return rc > 0 ? rc : MOLANN_E_UNSUPPORTED;
+            }
+        }
+        return (int)src.size();
+    }
     if (do_compile & 256) { // the backward of a wide fp32 head (molann_chain_bwd.inc), as plan creation would specialise it
         if (d->n_layers <= 0) return MOLANN_E_STAGE;
         if (d->mlp_precision != MOLANN_MLP_F32) return MOLANN_E_UNSUPPORTED;

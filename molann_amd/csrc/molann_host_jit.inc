@@ -341,6 +341,119 @@ std::string jit_source_bwd_ring(const JitSpecBox& b) {
     return s;
 }
 
+// ---- values + vector-Jacobian product of frames the lane kernels do not take, in one launch (molann_group_vjp.inc) ----------
+// The description's feature list as items (column order = list order, ann.py:473); returns the feature dimension.
+int expand_items(const molann_plan_desc* d, std::vector<ItemDev>& items) {
+    int col = 0;
+    for (int f = 0; f < d->n_features; ++f) {
+        const int* idx = d->feat_idx + d->feat_ptr[f];
+        const int cnt = d->feat_ptr[f + 1] - d->feat_ptr[f];
+        const int t = d->feat_type[f];
+        if (t == MOLANN_FEAT_POSITION) {
+            for (int i = 0; i < cnt; ++i) {
+                ItemDev it = {IT_POSITION, col, {idx[i], idx[i], idx[i], idx[i]}, {0, 0}};
+                items.push_back(it);
+                col += 3;
+            }
+        } else {
+            ItemDev it;
+            it.type = t == MOLANN_FEAT_ANGLE ? (d->use_angle_value ? IT_ANGLE_VAL : IT_ANGLE_COS)
+                      : t == MOLANN_FEAT_BOND ? IT_BOND
+                                              : (d->use_angle_value ? IT_DIHEDRAL_VAL : IT_DIHEDRAL_CS);
+            it.col = col;
+            for (int i = 0; i < 4; ++i) it.idx[i] = idx[i < cnt ? i : 0];
+            it.pad[0] = it.pad[1] = 0;
+            items.push_back(it);
+            col += item_width(it.type);
+        }
+    }
+    return col;
+}
+
+// Touched atoms in atom order and, per atom (CSR: ptr / list), what its gradient gathers: entries >= 0 are the g_y slots
+// 4 it + j of the item atoms it is, entries < 0 the alignment rows -1 - i it has (twice for an atom named twice).
+void group_vjp_tables(int n_inp, const std::vector<ItemDev>& items, const int* align_idx, int n_align, std::vector<int>& atoms,
+                      std::vector<int>& ptr, std::vector<int>& list) {
+    std::vector<std::vector<int>> contrib(n_inp);
+    for (size_t it = 0; it < items.size(); ++it)
+        for (int j = 0; j < item_atoms(items[it].type); ++j) contrib[items[it].idx[j]].push_back((int)(4 * it + j));
+    for (int i = 0; i < n_align; ++i) contrib[align_idx[i]].push_back(-1 - i);
+    atoms.clear(); list.clear();
+    ptr.assign(1, 0);
+    for (int a = 0; a < n_inp; ++a)
+        if (!contrib[a].empty()) {
+            atoms.push_back(a);
+            list.insert(list.end(), contrib[a].begin(), contrib[a].end());
+            ptr.push_back((int)list.size());
+        }
+}
+
+// LDS of one block (one 64-frame tile): the tables, the head's fragment image (heads of more than 40 fragments), the tile's
+// [unit][frame] scratch, 64 frame states (H, R, c0, dl: 136 bytes) and a g_y buffer per wave and frame of a round.
+// B frames per round as frames_group_bwd_kernel chooses them (<= 256 items per round), at least 2; eight waves per block where
+// they fit 160 KiB, then fewer, then smaller rounds.
+struct GroupVjpGeom { int b, wpb, s_rows, lds, off_ref32, off_align, off_items, off_atoms, off_ptr, off_list, off_img, off_s, off_st, off_gy; bool frag_lds; };
+constexpr int GROUP_VJP_STATE_BYTES = 136;
+bool group_vjp_geometry(const std::vector<int>& dims, int act, int d_feat, int n_align, int n_items, int n_touched, int n_list, GroupVjpGeom& g) {
+    memset(&g, 0, sizeof(g));
+    JitSpec j;
+    j.n_layers = dims.empty() ? 0 : (int)dims.size() - 1;
+    j.dims = dims;
+    const int frags = bwd_ring_frags(j);
+    g.frag_lds = frags > 40;      // (as molann_bwd_ring.inc: the fragments of up to the C3 class in registers)
+    g.s_rows = std::max(j.n_layers > 0 ? mlp_bwd_rows(dims, act) : 0, d_feat);
+    int b0 = 8;
+    while (b0 > 2 && (long)b0 * n_items > 256) b0 /= 2;
+    for (int b = b0; b >= 2; b /= 2)
+        for (int w : {8, 4, 2, 1}) {
+            long off = ceil_to(8 * (3 * n_align + 8), 16);
+            g.off_ref32 = (int)off; off += ceil_to(4 * (3 * n_align + 8), 16);
+            g.off_align = (int)off; off += ceil_to(4 * n_align, 16);
+            g.off_items = (int)off; off += 32l * n_items;
+            g.off_atoms = (int)off; off += ceil_to(4 * n_touched, 16);
+            g.off_ptr = (int)off; off += ceil_to(4 * (n_touched + 1), 16);
+            g.off_list = (int)off; off += ceil_to(4 * n_list, 16);
+            g.off_img = (int)off; off += g.frag_lds ? (long)frags * 256 : 0;
+            g.off_s = (int)off; off += (long)g.s_rows * 68 * 4;
+            g.off_st = (int)off; off += 64l * GROUP_VJP_STATE_BYTES;
+            g.off_gy = (int)off; off += (long)w * b * 48 * n_items;
+            if (off <= 163840) { g.b = b; g.wpb = w; g.lds = (int)off; return true; }
+        }
+    return false;
+}
+
+std::string jit_source_group_vjp(const std::vector<int>& dims, const std::vector<int>& kp, const std::vector<int>& jp, const std::vector<long>& woff,
+                                 int act, int d_feat, int n_inp, int n_align, int n_items, int n_touched, int n_list, const GroupVjpGeom& g) {
+    std::string s = "// preamble generated from the plan\n";
+    char t[128];
+    const int nl = dims.empty() ? 0 : (int)dims.size() - 1;
+    auto K = [&](const char* name, long v) { snprintf(t, sizeof(t), "constexpr int %s = %ld;\n", name, v); s += t; };
+    auto arr = [&](const char* name, const std::vector<long>& v) {
+        s += std::string("constexpr int ") + name + "[] = {";
+        for (size_t i = 0; i < v.size(); ++i) { snprintf(t, sizeof(t), "%s%ld", i ? ", " : "", v[i]); s += t; }
+        s += "};\n";
+    };
+    K("NL", nl); K("ACT", act);
+    std::vector<long> d(dims.begin(), dims.end()), k(kp.begin(), kp.end()), jj(jp.begin(), jp.end()), wo = woff, goff;
+    long np = 0;
+    for (int l = 0; l < nl; ++l) { goff.push_back(np); np += (long)dims[l + 1] * dims[l] + dims[l + 1]; }
+    if (nl == 0) { d = {d_feat, 1}; k = {1}; jj = {1}; wo = {0}; goff = {0}; }   // (the tile code names DIMS[1], KP[0], ...)
+    arr("DIMS", d); arr("KP", k); arr("JP", jj); arr("WOFF", wo); arr("GOFF", goff);
+    K("N_PARAMS", np);
+    s += g.frag_lds ? "constexpr bool FRAG_LDS = true;\n" : "constexpr bool FRAG_LDS = false;\n";
+    s += "constexpr bool WITH_VALUES = true;\n";
+    K("B", g.b); K("WPB", g.wpb); K("N_ALIGN", n_align); K("N_ITEMS", n_items); K("D_FEAT", d_feat); K("FRAME_DW", 3l * n_inp);
+    K("N_TOUCHED", n_touched); K("N_LIST", n_list); K("S_ROWS", g.s_rows); K("FRAME_STATE_BYTES", GROUP_VJP_STATE_BYTES);
+    K("OFF_REF32", g.off_ref32); K("OFF_ALIGN", g.off_align); K("OFF_ITEMS", g.off_items); K("OFF_ATOMS", g.off_atoms);
+    K("OFF_PTR", g.off_ptr); K("OFF_LIST", g.off_list); K("OFF_IMG", g.off_img); K("OFF_S", g.off_s); K("OFF_ST", g.off_st);
+    K("OFF_GY", g.off_gy); K("LDS_BYTES", g.lds);
+    s += "#line 1 \"molann_mlp_tile.inc\"\n";
+    s += join_chunks(k_src_molann_mlp_tile_inc);
+    s += "#line 1 \"molann_group_vjp.inc\"\n";
+    s += join_chunks(k_src_molann_group_vjp_inc);
+    return s;
+}
+
 std::string jit_preamble(const JitSpec& j) {
     std::string s = "// preamble generated from the plan\n";
     char b[256];

@@ -93,6 +93,11 @@ struct molann_plan {
     hipModule_t vjp_mod;
     hipFunction_t vjp_fn;      // the one-pass backward that also stores the forward's outputs (molann_value_and_vjp_f32), same geometry
     int vjp_state;
+    hipModule_t gvjp_mod;
+    hipFunction_t gvjp_fn;     // values + vjp in one launch for frames the lane kernels do not take (molann_group_vjp.inc), built at the first use
+    int gvjp_state, gvjp_b, gvjp_wpb, gvjp_lds, gvjp_bpc;
+    int* d_va_atoms; int* d_va_ptr; int* d_va_list;   // ... its touched atoms and what each gathers (group_vjp_tables)
+    int va_touched, va_list_len;
     hipModule_t mbwd_mod;
     hipFunction_t mbwd_fn;     // backward of the fused family's MLP (molann_mlp_bwd.inc), compiled at the first backward
     int mbwd_state, mbwd_wpb;

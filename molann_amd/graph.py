@@ -81,7 +81,8 @@ class GraphedForces(GraphedForward):
     The backward graph holds one launch of `molann_backward_f32` (the one-pass kernel recomputes the forward from the static x:
     nothing else links the two graphs), built and warmed before capture.  Models on frames of a few hundred atoms with a small
     head (no one-pass kernel: wave-per-frame preprocessing) are captured as forward-with-kept-features and the two-launch backward
-    on them (`_recapture_kept_features`).  `recapture()` after changing parameters."""
+    on them (`_recapture_kept_features`); their `value_and_vjp` is one launch of molann_group_vjp where the plan has it.
+    `recapture()` after changing parameters."""
 
     def recapture(self):
         super(GraphedForces, self).recapture()
@@ -128,6 +129,11 @@ class GraphedForces(GraphedForward):
         self.static_gf = torch.empty_like(self.static_f)
         self.static_dy = torch.zeros_like(self.static_y)
         self.static_dx = torch.empty_like(x)
+        # value_and_vjp is one launch of molann_group_vjp where the plan has it: built here, before anything is captured
+        self._single = plan.supports_value_and_vjp()
+        if self._single:
+            with torch.cuda.device(x.device):
+                self.model.value_and_vjp(x, self.static_dy, into=(self.static_y, self.static_dx))
 
         def fwd():
             plan.forward_train(x, self.static_y, self.static_f)
@@ -160,7 +166,7 @@ class GraphedForces(GraphedForward):
         if x.shape != self.static_x.shape or dy.shape != self.static_dy.shape:
             raise ValueError("GraphedForces was captured for %s / %s, got %s / %s" % (tuple(self.static_x.shape), tuple(self.static_dy.shape),
                                                                                     tuple(x.shape), tuple(dy.shape)))
-        if self._kept:       # no single launch for these plans: the two replays
+        if self._kept and not self._single:       # no single launch for this plan: the two replays
             self.static_x.copy_(x)
             self.static_dy.copy_(dy)
             self.graph.replay()
