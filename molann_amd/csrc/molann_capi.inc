@@ -510,7 +510,7 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
             int scratch = 0;
             (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, fn);
             if (scratch > 0 && fb > 1) { (void)hipModuleUnload(mod); continue; }
-            p->chain_mod = mod; p->chain_fn = fn; p->chain_fb = fb; p->chain_waves = chain_waves(cg);
+            p->chain_mod = mod; p->chain_fn = fn; p->chain_fb = fb; p->chain_waves = chain_waves(cg); p->chain_nslab = chain_nslab(cg);
             snprintf(p->chain_note, sizeof(p->chain_note), "chain: specialised kernel, FB=%d, %zu bytes", fb, code.size());
         }
         if (!p->chain_fn) snprintf(p->chain_note, sizeof(p->chain_note), "chain: unavailable (rc=%d), mlp_mfma_kernel", rc);

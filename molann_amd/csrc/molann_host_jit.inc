@@ -157,6 +157,13 @@ std::string jit_source(const JitSpec& j) {
 // the whole weight stream resident in LDS (molann_mlp_jit.inc: RESIDENT): no streaming, eight waves per block
 inline bool chain_resident(const ChainGeom& g) { return g.total_frags() * 1024 <= 150 * 1024; }
 inline int chain_waves(const ChainGeom& g) { return chain_resident(g) ? 8 : 4; }
+// streaming: LDS slab buffers of the ring (NSLAB - 1 slabs in flight), as many as 160 KB less 2 KB hold, 2 to 4; resident: 1.
+// The kernel takes this number from its preamble and the launch info reports it.
+inline int chain_nslab(const ChainGeom& g) {
+    if (chain_resident(g)) return 1;
+    const int fit = (160 * 1024 - 2048) / (g.slab_max() * 1024);
+    return fit >= 4 ? 4 : (fit >= 3 ? 3 : 2);
+}
 
 std::string jit_source_chain(const ChainGeom& g, int act, int fb) {
     std::string s = "// preamble generated from the plan\n";
@@ -166,7 +173,8 @@ std::string jit_source_chain(const ChainGeom& g, int act, int fb) {
     for (int i = 0; i <= g.nl; ++i) { snprintf(t, sizeof(t), "%s%d", i ? ", " : "", g.dims[i]); s += t; }
     s += "};\n";
     snprintf(t, sizeof(t), "constexpr int ACT = %d;\nconstexpr int FB = %d;\nconstexpr bool BF16 = %s;\n", act, fb, g.bf16 ? "true" : "false"); s += t;
-    snprintf(t, sizeof(t), "constexpr bool RESIDENT = %s;\nconstexpr int WAVES = %d;\n", chain_resident(g) ? "true" : "false", chain_waves(g)); s += t;
+    snprintf(t, sizeof(t), "constexpr bool RESIDENT = %s;\nconstexpr int WAVES = %d;\nconstexpr int NSLAB = %d;\n", chain_resident(g) ? "true" : "false",
+             chain_waves(g), chain_nslab(g)); s += t;
     { const char* e = diag_env("MOLANN_DEBUG_CHAIN"); snprintf(t, sizeof(t), "constexpr int CHAIN_DIAG = %d;\n", e ? atoi(e) : 0); s += t; }   // diagnostics build: timing ablations (wrong results)
     s += "#line 1 \"molann_mlp_jit.inc\"\n";
     s += join_chunks(k_src_molann_mlp_jit_inc);

@@ -303,8 +303,10 @@ int launch_mlp(molann_plan* p, const float* feat, long n_frames, int in_stride, 
             {feat, out, p->d_wchain, (const float*)(p->d_wchain + p->chain_stream_bytes), n_frames, in_stride};
         size_t ksz = sizeof(ka);
         void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ka, HIP_LAUNCH_PARAM_BUFFER_SIZE, &ksz, HIP_LAUNCH_PARAM_END};
-        snprintf(p->mlp_info, sizeof(p->mlp_info), "molann_mlp_chain<%s,FB=%d%s> (plan-specialised) grid=%d block=%d",
-                 p->mlp_prec == MOLANN_MLP_BF16 ? "bf16" : "f32", p->chain_fb, cw == 8 ? ",resident" : "", grid, 64 * cw);
+        char ring[24] = "";
+        if (cw != 8) snprintf(ring, sizeof(ring), "; %d slab buffers", p->chain_nslab);
+        snprintf(p->mlp_info, sizeof(p->mlp_info), "molann_mlp_chain<%s,FB=%d%s> (plan-specialised%s) grid=%d block=%d",
+                 p->mlp_prec == MOLANN_MLP_BF16 ? "bf16" : "f32", p->chain_fb, cw == 8 ? ",resident" : "", ring, grid, 64 * cw);
         return (int)hipModuleLaunchKernel(p->chain_fn, grid, 1, 1, 64 * cw, 1, 1, 0, stream, nullptr, cfg);
     }
     MlpArgs a;

@@ -135,6 +135,7 @@ struct molann_plan {
     long chain_stream_bytes;
     int chain_fb;              // 16-frame blocks per wave
     int chain_waves;           // waves per block: 4 (weights streamed through LDS slabs) or 8 (weight stream resident in LDS)
+    int chain_nslab;           // LDS slab buffers of the streamed weights (2 to 4; 1: resident)
     char chain_note[96];
     char mlp_info[96];         // name + geometry of the last MLP kernel launch
     // large frames through frames_ring_kernel: per-frame window list, LDS positions of the alignment atoms and of the

@@ -27,7 +27,8 @@
 // the loop over the tiles - with eight waves per block (two per SIMD: one wave's dependent MFMA chains and activations
 // run under the other's).  Streaming, [6, 64, 64, 8] met five barriers per 256 frames and ran at 58 TFLOP/s.
 //
-// Preamble (generated from the plan): NL, DIMS[NL+1], ACT, FB (16-frame blocks per wave), BF16, RESIDENT, WAVES.
+// Preamble (generated from the plan): NL, DIMS[NL+1], ACT, FB (16-frame blocks per wave), BF16, RESIDENT, WAVES, NSLAB (slab buffers,
+// chain_nslab in molann_host_jit.inc).
 // Compiled a second way (round 3): behind molann_ring.inc inside molann_lane_jit.inc with MOLANN_CHAIN_CORE_ONLY defined, where
 // the chain's arithmetic (run_pair on an LDS-resident stream) is the MLP stage of the lane kernel's consumer waves (WIDE_MLP).
 #ifndef MOLANN_RING_INC
@@ -45,7 +46,7 @@ typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 #ifdef MOLANN_CHAIN_CORE_ONLY
 constexpr int FB = 4;                 // the lane kernel's tile: four blocks of 16 frames
 constexpr bool BF16 = false, RESIDENT = true;
-constexpr int WAVES = NCONS;
+constexpr int WAVES = NCONS, NSLAB = 1;
 constexpr int CHAIN_DIAG = 0;
 #endif
 constexpr int CB = BF16 ? 2 : 1;                                     // 16-unit blocks per chunk = per k-step of the next layer
@@ -82,8 +83,9 @@ constexpr long PAIR_BASE(int p) {     // stream offset of pair p's first slab
 }
 // streaming: a ring of NSLAB slab buffers, NSLAB - 1 slabs in flight ahead of the one being consumed (round 3: with two
 // buffers the DMA of slab g + 1 had only slab g's MFMAs to hide under - C5's chunk is 0.9 us of MFMA, a fragment's trip from L2
-// 2-3 us - and the kernel ran at the DMA's latency: 20 % of the bf16 MFMA rate)
-constexpr int NSLAB = RESIDENT ? 1 : ((160 * 1024 - 2048) / SLAB_BYTES >= 4 ? 4 : ((160 * 1024 - 2048) / SLAB_BYTES >= 3 ? 3 : 2));
+// 2-3 us - and the kernel ran at the DMA's latency: 20 % of the bf16 MFMA rate).  NSLAB comes from the preamble: as many buffers,
+// up to four, as fit 160 KB less 2 KB.
+static_assert(RESIDENT ? NSLAB == 1 : (NSLAB >= 2 && NSLAB <= 4 && (long)NSLAB * SLAB_BYTES <= 160 * 1024 - 2048), "NSLAB");
 constexpr int PD = NSLAB - 1;                                        // prefetch distance, in slabs
 constexpr int SLAB_SHARE(int p) { return cdiv(SLAB_FRAGS(p), WAVES); }   // DMA instructions per wave and slab (the same for every wave)
 constexpr int share_min() {

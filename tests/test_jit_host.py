@@ -128,3 +128,21 @@ def test_wide_fused_forward_compiles(dims, act):
     big = (ctypes.c_int32 * 4)(6, 256, 256, 8)
     d.n_layers, d.layer_dims = 3, big
     assert _capi.lib().molann_debug_jit(ctypes.byref(d), 129, buf, 1 << 22) == _capi.E_UNSUPPORTED
+
+
+@pytest.mark.parametrize("dims,precision,nslab", [([341, 512, 256, 16], _capi.MLP_BF16, 4), ([341, 512, 256, 16], _capi.MLP_F32, 4),
+                                                  ([700, 64, 8], _capi.MLP_F32, 3), ([960, 64, 8], _capi.MLP_F32, 2),
+                                                  ([960, 40], _capi.MLP_F32, 2), ([960, 128, 8], _capi.MLP_BF16, 2),
+                                                  ([960, 64, 8], _capi.MLP_BF16, 1), ([126, 64, 32, 2], _capi.MLP_F32, 1)])
+def test_chain_kernel_slab_buffers(dims, precision, nslab):
+    """The chain MLP kernel's ring of LDS slab buffers is sized on the host (as many as fit 158 KB, 2 to 4; 1 when the stream is
+    resident) and handed to the kernel in its preamble, whose static_assert holds it to the LDS: the kernel cross-compiles."""
+    d, keep = _desc(wl.get_workload("C3"))
+    ld = (ctypes.c_int32 * len(dims))(*dims)
+    d.n_layers, d.layer_dims, d.mlp_precision = len(dims) - 1, ld, precision
+    buf = ctypes.create_string_buffer(1 << 21)
+    rc = _capi.lib().molann_debug_jit(ctypes.byref(d), 5, buf, 1 << 21)
+    assert rc > 1000, (rc, buf.value.decode()[:3000])
+    src = buf.value.decode()
+    assert "constexpr int NSLAB = %d;" % nslab in src
+    assert ("constexpr bool RESIDENT = true;" in src) == (nslab == 1)
