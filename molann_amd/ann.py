@@ -306,14 +306,27 @@ class _PlanFunction64(torch.autograd.Function):
         return gx, None
 
 
+def _difference_points(x, v):
+    """``(x + h v, x - h v, 1 / 2h)`` of the central differences in `_FeatBackward64.backward`, per frame, with the step
+    ``h = 6e-6 / |v|_max`` (``h = 0`` and ``1 / 2h = 0`` on a frame where v is zero: its rows stay exactly zero).  A move of
+    6e-6 in the coordinates' own unit: the optimum of a second-order formula in double (truncation ~ (h / l)^2, rounding ~
+    1e-16 / h) for the length scale l of the geometry - bonds, angles, dihedrals, the aligned set - which is where the
+    curvature comes from, not where the frame sits in the box.  (A step that grew with |x|_max gave truncation errors that
+    grow like |x|^2: 1e-5 of scale at 100 A from the origin.)  csrc/molann_torch.cpp: FeatBackward64Fn takes the same step."""
+    vmax = v.abs().amax(dim=(1, 2), keepdim=True)
+    h = torch.where(vmax > 0, 6e-6 / vmax.clamp(min=1e-300), torch.zeros_like(vmax))
+    inv = torch.where(h > 0, 0.5 / h.clamp(min=1e-300), torch.zeros_like(h))
+    return (x + h * v).contiguous(), (x - h * v).contiguous(), inv
+
+
 class _FeatBackward64(torch.autograd.Function):
     """``gx = J(x)^T g`` of the float64 features (`molann_features_backward_f64`) as a node that can itself be differentiated -
     what ``create_graph=True`` needs (second-order terms of a loss on forces; the reference gets them from autograd through its
     SVD, `ann.py:188-197`).  For a cotangent ``v`` on ``gx`` its backward needs ``d/dx [v . J(x)^T g]`` and ``d/dg [v . J(x)^T g] = J(x) v``:
     both are directional derivatives along ``v`` - of the first-order kernel's own output and of the features - taken as CENTRAL
-    DIFFERENCES of the float64 kernels, per frame with step ``h = 6e-6 * max(1, |x|_max) / |v|_max`` (the optimum for a
-    second-order formula in double: truncation ~ h^2, rounding ~ 1e-16 / h; agreement with the reference's analytic double
-    backward ~1e-9 of scale, `tests/test_gpu_backward.py::test_double_backward_*`).  Four launches; itself first-order."""
+    DIFFERENCES of the float64 kernels at the points `_difference_points` gives.  Four launches; itself first-order: under
+    ``create_graph=True`` its backward raises, as FeatBackward64Fn's does (``once_differentiable`` would not: the error node it
+    leaves hangs off detached copies, so ``torch.autograd.grad`` with respect to x prunes it and drops the term in silence)."""
 
     @staticmethod
     def forward(ctx, x, g, entry):
@@ -325,16 +338,12 @@ class _FeatBackward64(torch.autograd.Function):
         return gx
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
     def backward(ctx, v):
+        if torch.is_grad_enabled():
+            raise RuntimeError("molann_amd: gradients of order three are not available (the double backward is first-order itself)")
         x, g = ctx.saved_tensors
         plan = ctx.entry.plan
-        v = v.contiguous().double()
-        vmax = v.abs().amax(dim=(1, 2), keepdim=True)
-        xmax = x.abs().amax(dim=(1, 2), keepdim=True).clamp_(min=1.0)
-        h = torch.where(vmax > 0, 6e-6 * xmax / vmax.clamp(min=1e-300), torch.zeros_like(vmax))
-        xp, xm = (x + h * v).contiguous(), (x - h * v).contiguous()
-        inv = torch.where(h > 0, 0.5 / h.clamp(min=1e-300), torch.zeros_like(h))
+        xp, xm, inv = _difference_points(x, v.contiguous().double())
         gxp, gxm = torch.empty_like(x), torch.empty_like(x)
         fp = torch.empty((x.shape[0], plan.feature_dim), dtype=torch.float64, device=x.device)
         fm = torch.empty_like(fp)

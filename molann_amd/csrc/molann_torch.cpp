@@ -660,7 +660,9 @@ at::Tensor activation(int64_t code, const at::Tensor& t);
 // kernel - is itself a node (FeatBackward64Fn) with a backward of its own, and the MLP as ATen ops on the live parameters.
 // FeatBackward64Fn's backward needs, for a cotangent v on J^T g, d/dx [v . J(x)^T g] and d/dg [..] = J(x) v: directional
 // derivatives along v of the first-order kernel's output and of the features, taken as central differences of the float64
-// kernels, per frame with h = 6e-6 max(1, |x|_max) / |v|_max (molann_amd/ann.py: _FeatBackward64 is the same in Python).
+// kernels, per frame with h = 6e-6 / |v|_max: a move of 6e-6 in the coordinates' own unit, set by the length scale of the geometry
+// (bonds, angles, dihedrals, the aligned set) and not by where the frame sits in the box (molann_amd/ann.py: _difference_points
+// is the same step in Python and says why).
 struct FeatBackward64Fn : public torch::autograd::Function<FeatBackward64Fn> {
     static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& x, const at::Tensor& g, std::vector<int64_t> desc,
                               const at::Tensor& ref_x) {
@@ -676,8 +678,8 @@ struct FeatBackward64Fn : public torch::autograd::Function<FeatBackward64Fn> {
         const std::vector<int64_t> desc = ctx->saved_data["desc"].toIntVector();
         at::AutoDispatchBelowADInplaceOrView below;
         const at::Tensor v = grad_outputs[0].to(at::kDouble).contiguous();
-        const at::Tensor vmax = v.abs().amax({1, 2}, true), xmax = x.abs().amax({1, 2}, true).clamp_min(1.0);
-        const at::Tensor h = at::where(vmax > 0, 6e-6 * xmax / vmax.clamp_min(1e-300), at::zeros_like(vmax));
+        const at::Tensor vmax = v.abs().amax({1, 2}, true);
+        const at::Tensor h = at::where(vmax > 0, 6e-6 / vmax.clamp_min(1e-300), at::zeros_like(vmax));
         const at::Tensor inv = at::where(h > 0, 0.5 / h.clamp_min(1e-300), at::zeros_like(h));
         const at::Tensor xp = (x + h * v).contiguous(), xm = (x - h * v).contiguous();
         at::Tensor gx, gg;

@@ -561,8 +561,10 @@ def test_value_and_vjp_latency_and_jacobian(hip_device):
 def test_double_backward_matches_reference_autograd(name, dtype, hip_device):
     """create_graph=True (round 3): a loss on forces.  E = sum(model(x) * G), F = dE/dx with create_graph=True, L = sum(F * F);
     dL/dx and dL/d(parameters) against the REFERENCE's autograd through its SVD (tests/golden/grad2_*.npz, written by
-    oracle/gen_golden.py --round3).  The second-order terms are central differences of the float64 kernels along the cotangent
-    (molann_amd/ann.py: _FeatBackward64; csrc/molann_torch.cpp: FeatBackward64Fn): 1e-6 of scale in float64, and no further from
+    oracle/gen_golden.py --round3).  The second-order terms are central differences of the float64 kernels along the cotangent v,
+    per frame with step h = 6e-6 / |v|_max whatever the frame's distance from the origin (molann_amd/ann.py: _FeatBackward64,
+    _difference_points; csrc/molann_torch.cpp: FeatBackward64Fn; tests/test_gpu_double_backward.py covers the other plan
+    families and frames far from the origin): 1e-6 of scale in float64, and no further from
     the float64 reference than a few times the reference's own float32 run in float32.  Eager float32 (the operator's autograd
     node), eager float64 (the Python functions) and a scripted model."""
     d = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
