@@ -177,6 +177,21 @@ int molann_features_f64(const molann_plan* plan, const double* x, int64_t n_fram
 int molann_features_backward_f64(const molann_plan* plan, const double* x, const double* grad_f, int64_t n_frames, double* grad_x,
                                  molann_stream_t stream);
 
+/* -- forward mode ----------------------------------------------------------------------------- */
+/* Directional derivatives of the feature stage (what torch.autograd.forward_ad, torch.func.jvp and torch.func.jacfwd ask
+ * the reference's autograd for): tangent_out[t] = J(x) v[t], the Jacobian of molann_features_f32 / _f64 at x applied to
+ * each of n_tangents >= 1 tangents.  v is [n_tangents, n_frames, n_inp, 3] and tangent_out [n_tangents, n_frames,
+ * feature_dim], contiguous; out[n_frames, feature_dim] receives the features themselves (nullable: then not written).  The
+ * tangents of a frame share one read of x, one rotation solve and one evaluation of the features: a frame's Jacobian
+ * (3 n_inp tangents) costs one solve.  Every plan with feature items, any frame size, with or without a head (the feature
+ * stage only, like molann_features_f32).  Everything is computed in double and rounded on the store (frames_jvp_kernel;
+ * lane groups of 8..64 per frame; no atomics, so the results are identical run to run).  Pointers 4-byte (f32) / 8-byte
+ * (f64) aligned; n_tangents < 1: MOLANN_E_DESC. */
+int molann_features_jvp_f32(const molann_plan* plan, const float* x, const float* v, int64_t n_frames, int n_tangents, float* out,
+                            float* tangent_out, molann_stream_t stream);
+int molann_features_jvp_f64(const molann_plan* plan, const double* x, const double* v, int64_t n_frames, int n_tangents, double* out,
+                            double* tangent_out, molann_stream_t stream);
+
 /* ann_layers ann.py:60-65 in float64 on features f[N, layer_dims[0]]: W, b HOST arrays of n_layers device pointers. */
 int molann_mlp_f64(const molann_plan* plan, const double* f, int64_t n_frames, const double* const* W, const double* const* b,
                    double* out, molann_stream_t stream);
@@ -291,6 +306,15 @@ float molann_selftest_activation(int act, float v);
 int molann_selftest_feature_backward(int type, int use_angle_value, const float* atoms_xyz, const float* g3, float* ga12);
 int molann_selftest_kabsch_backward(const double* H9, const float* R9, const float* GR9, float* GH9);
 float molann_selftest_act_derivative(int act, float z);
+/* forward mode: the item's values and their derivatives along the atoms' tangents (t12: 4 atoms x xyz); return the width */
+int molann_selftest_feature_tangent_f32(int type, int use_angle_value, const float* atoms_xyz, const float* t12, float* out3,
+                                        float* dout3);
+int molann_selftest_feature_tangent_f64(int type, int use_angle_value, const double* atoms_xyz, const double* t12, double* out3,
+                                        double* dout3);
+/* the rotation in double, the tangent dR of the rotation for a covariance direction dH, and the backward in double */
+int molann_selftest_kabsch_rotation_f64(const double* H9, double e0, double* R9);
+int molann_selftest_kabsch_tangent(const double* H9, const double* R9, const double* dH9, double* dR9);
+int molann_selftest_kabsch_backward_f64(const double* H9, const double* R9, const double* GR9, double* GH9);
 
 #ifdef __cplusplus
 }

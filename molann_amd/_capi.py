@@ -114,6 +114,13 @@ def lib():
             "molann_selftest_feature_backward": (i32, [i32, i32, vp, vp, vp]),
             "molann_selftest_kabsch_backward": (i32, [vp, vp, vp, vp]),
             "molann_selftest_act_derivative": (f32, [i32, f32]),
+            "molann_features_jvp_f32": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
+            "molann_features_jvp_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
+            "molann_selftest_feature_tangent_f32": (i32, [i32, i32, vp, vp, vp, vp]),
+            "molann_selftest_feature_tangent_f64": (i32, [i32, i32, vp, vp, vp, vp]),
+            "molann_selftest_kabsch_rotation_f64": (i32, [vp, ctypes.c_double, vp]),
+            "molann_selftest_kabsch_tangent": (i32, [vp, vp, vp, vp]),
+            "molann_selftest_kabsch_backward_f64": (i32, [vp, vp, vp, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -240,6 +247,24 @@ class Plan(object):
                                                  torch.cuda.current_stream().cuda_stream)
         if code != 0:
             raise MolannHipError(code, "molann_features_backward_f64")
+
+    def _jvp(self, fn_name, x, v, out, tangent_out):
+        n_t = v.shape[0]
+        code = getattr(_lib, fn_name)(self._handle, x.data_ptr(), v.data_ptr(), x.shape[0], n_t,
+                                      out.data_ptr() if out is not None else None, tangent_out.data_ptr(),
+                                      torch.cuda.current_stream().cuda_stream)
+        if code != 0:
+            raise MolannHipError(code, fn_name)
+        return tangent_out
+
+    def features_jvp(self, x, v, out, tangent_out):
+        """tangent_out[t] = J(x) v[t] of `features` (float32): x [N, n_inp, 3], v [T, N, n_inp, 3] and tangent_out
+        [T, N, feature_dim] contiguous; `out` [N, feature_dim] receives the features too unless None."""
+        return self._jvp("molann_features_jvp_f32", x, v, out, tangent_out)
+
+    def features_jvp_f64(self, x, v, out, tangent_out):
+        """`features_jvp` in float64."""
+        return self._jvp("molann_features_jvp_f64", x, v, out, tangent_out)
 
     def mlp_f64(self, f, weights, biases, out):
         n = len(weights)

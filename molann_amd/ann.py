@@ -16,11 +16,15 @@ modules follow x.dtype) runs the `molann_*_f64` kernels; under grad mode its fea
 kernels: fused with the MLP for the plans the lane-per-frame kernel serves (22-atom class, MLP widths <= 32),
 features only on large frames (one wave per frame).  With an MLP outside the fused kernel (wider, ELU / GELU /
 Softplus, or any MLP on large frames) a forward under grad mode takes features and their gradient from the
-kernels and runs ``ann_layers`` as the torch module it is.
+kernels and runs ``ann_layers`` as the torch module it is.  Forward mode (``torch.autograd.forward_ad`` duals, ``torch.func.jvp`` /
+``jacfwd`` / ``vmap``) takes its own path, only when a tangent is present: the features and their tangents from the tangent
+kernel (`_FeaturesJvp`, `_FeaturesTangent`), ``ann_layers`` as the torch module it is.
 """
 
 import torch
+import torch._C._functorch as _functorch
 import pandas as pd
+from torch.autograd import forward_ad as _fwAD
 
 from . import _capi
 
@@ -390,6 +394,182 @@ def _double_backward(ctx, grad_out):
     return tuple(out)
 
 
+# ---- forward mode (torch.autograd.forward_ad, torch.func.jvp / jacfwd / vmap) ----------------------------------------------
+# A module's forward takes the path below only when a tangent is present: an input that is a forward-AD dual or a tensor a
+# torch.func transform wraps.  Every other call keeps its own path (fast path, operator, ctypes, graphs, scripting) untouched.
+def _transform_active():
+    """True inside an `fwAD.dual_level()` or a torch.func transform: only then can a tensor carry a tangent."""
+    return _fwAD._current_level >= 0 or _functorch.maybe_current_level() is not None
+
+
+def _has_tangent(t):
+    if not isinstance(t, torch.Tensor):
+        return False
+    if _functorch.is_functorch_wrapped_tensor(t):
+        return True
+    return _fwAD._current_level >= 0 and _fwAD.unpack_dual(t).tangent is not None
+
+
+def _refuse_ref_tangent(align_layer):
+    if align_layer is not None and _has_tangent(align_layer.ref_x):
+        raise RuntimeError("molann_amd: no forward-mode derivative with respect to the alignment reference ref_x (tangents are "
+                           "provided for the coordinates x and the ann_layers parameters only)")
+
+
+def _tangent_input(x):
+    """x as the forward-mode kernels read it; raises as `_device_input` does."""
+    if not x.is_cuda:
+        raise RuntimeError("molann_amd runs on the MI355X only: got a %s tensor (no CPU path; move x and the "
+                           "module to a HIP device)" % x.device.type)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError("molann_amd kernels are float32 / float64; got %s" % x.dtype)
+    return x
+
+
+class _FeaturesJvp(torch.autograd.Function):
+    """The features of a plan where a tangent is present.  forward = molann_features_f32 / _f64 (what the plain path
+    computes), backward = molann_features_backward_f32 / _f64 (`_FeaturesVjp`), jvp = the forward-mode kernel
+    (`_FeaturesTangent`: frames_jvp_kernel).  New-style (setup_context) and with a vmap rule, so that torch.func can
+    transform it."""
+
+    @staticmethod
+    def forward(x, entry):
+        x = x.contiguous()
+        out = torch.empty((x.shape[0], entry.plan.feature_dim), dtype=x.dtype, device=x.device)
+        if x.shape[0] > 0:
+            with torch.cuda.device(x.device):
+                if x.dtype == torch.float64:
+                    entry.plan.features_f64(x, out)
+                else:
+                    entry.plan.features(x, out)
+        return out
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        x, entry = inputs
+        ctx.entry = entry
+        ctx.save_for_backward(x)
+        ctx.save_for_forward(x)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (x,) = ctx.saved_tensors
+        return _FeaturesVjp.apply(x, grad_out, ctx.entry), None
+
+    @staticmethod
+    def jvp(ctx, x_t, _entry_t):
+        (x,) = ctx.saved_tensors
+        return _FeaturesTangent.apply(x, x_t, ctx.entry)
+
+    @staticmethod
+    def vmap(info, in_dims, x, entry):
+        # a batch of x is more frames
+        x = x.movedim(in_dims[0], 0)
+        b, n = x.shape[0], x.shape[1]
+        f = _FeaturesJvp.apply(x.reshape((b * n,) + tuple(x.shape[2:])), entry)
+        return f.view(b, n, f.shape[-1]), 0
+
+
+class _FeaturesTangent(torch.autograd.Function):
+    """``J(x) v`` of a plan's features: v is [N, n_inp, 3] or [T, N, n_inp, 3] (T tangents in one launch: one read of x and
+    one rotation solve per frame).  Its vmap rule folds a batch of tangents into T and a batch of x into frames, which is
+    what torch.func.jacfwd (vmap over jvp) needs.  It is itself first-order: differentiating it again (hessian, reverse over
+    forward, forward over forward) raises."""
+
+    @staticmethod
+    def forward(x, v, entry):
+        one = v.dim() == 3
+        v = v.unsqueeze(0) if one else v
+        x = x.contiguous()
+        v = v.to(x.dtype).contiguous()
+        plan = entry.plan
+        out = torch.empty((v.shape[0], x.shape[0], plan.feature_dim), dtype=x.dtype, device=x.device)
+        if x.shape[0] > 0 and v.shape[0] > 0:
+            with torch.cuda.device(x.device):
+                if x.dtype == torch.float64:
+                    plan.features_jvp_f64(x, v, None, out)
+                else:
+                    plan.features_jvp(x, v, None, out)
+        return out[0] if one else out
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(ctx, grad):
+        raise RuntimeError("molann_amd: the forward-mode tangent of the features cannot be differentiated again (no derivative "
+                           "of J(x) v with respect to x or v: reverse over forward mode and torch.func.hessian are not provided)")
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        raise NotImplementedError("molann_amd: nested forward mode (forward over forward) is not provided: the tangent kernel is "
+                                  "first-order")
+
+    @staticmethod
+    def vmap(info, in_dims, x, v, entry):
+        xd, vd, _ = in_dims
+        b = info.batch_size
+        if xd is None:
+            v = v.movedim(vd, 0)                     # [B, N, n, 3] or [B, T, N, n, 3]: B (x T) tangents
+            if v.dim() == 4:
+                return _FeaturesTangent.apply(x, v, entry), 0
+            t = v.shape[1]
+            out = _FeaturesTangent.apply(x, v.reshape((b * t,) + tuple(v.shape[2:])), entry)
+            return out.view(b, t, out.shape[1], out.shape[2]), 0
+        x = x.movedim(xd, 0)                         # a batch of frames: fold it into N
+        n = x.shape[1]
+        xs = x.reshape((b * n,) + tuple(x.shape[2:]))
+        v = v.movedim(vd, 0) if vd is not None else v.expand((b,) + tuple(v.shape))
+        if v.dim() == 4:                             # [B, N, n, 3]
+            out = _FeaturesTangent.apply(xs, v.reshape(xs.shape), entry)
+            return out.view(b, n, out.shape[-1]), 0
+        t = v.shape[1]                               # [B, T, N, n, 3] -> [T, B N, n, 3]
+        out = _FeaturesTangent.apply(xs, v.transpose(0, 1).reshape((t,) + tuple(xs.shape)), entry)
+        return out.view(t, b, n, out.shape[-1]).transpose(0, 1), 0
+
+
+class _FeaturesVjp(torch.autograd.Function):
+    """``J(x)^T g`` of `_FeaturesJvp` through the existing backward kernels, with a vmap rule (torch.func.jacrev).  First-order:
+    its own derivatives (create_graph, hessian) raise."""
+
+    @staticmethod
+    def forward(x, g, entry):
+        x = x.contiguous()
+        g = g.to(x.dtype).contiguous()
+        gx = torch.empty_like(x)
+        if x.shape[0] > 0:
+            with torch.cuda.device(x.device):
+                if x.dtype == torch.float64:
+                    entry.plan.features_backward_f64(x, g, gx)
+                else:
+                    entry.plan.features_backward(x, g, gx)
+        return gx
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(ctx, grad):
+        raise RuntimeError("molann_amd: second derivatives are not provided where a forward-mode tangent is present "
+                           "(torch.func.hessian, create_graph=True on a forward-mode path)")
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        raise NotImplementedError("molann_amd: forward over reverse mode (torch.func.hessian) is not provided: it needs the "
+                                  "derivative of the features' backward")
+
+    @staticmethod
+    def vmap(info, in_dims, x, g, entry):
+        b = info.batch_size
+        x = x.movedim(in_dims[0], 0) if in_dims[0] is not None else x.expand((b,) + tuple(x.shape))
+        g = g.movedim(in_dims[1], 0) if in_dims[1] is not None else g.expand((b,) + tuple(g.shape))
+        n = x.shape[1]
+        gx = _FeaturesVjp.apply(x.reshape((b * n,) + tuple(x.shape[2:])), g.reshape(b * n, g.shape[-1]), entry)
+        return gx.view(x.shape), 0
+
+
 def _device_buffer(ref_x, x):
     """The module's `ref_x` buffer must live where x lives and have its dtype (the reference's matmul, ann.py:187,
     raises RuntimeError for mixed devices and for mixed dtypes too)."""
@@ -558,14 +738,21 @@ class AlignmentLayer(_PlanOwner, torch.nn.Module):
 
     def forward(self, x):
         _check_input(x, self.input_atom_num)
-        x = _device_input(x, backward_ok=True)
+        tangent = _transform_active() and (_has_tangent(x) or _has_tangent(self.ref_x))
+        x = _tangent_input(x) if tangent else _device_input(x, backward_ok=True)
+
+        def build():   # the aligned frame == alignment + one position item per atom: that plan has backward and tangent kernels
+            return _capi.Plan(self.input_atom_num, align_idx=self._local_align_atom_indices, ref_x=self.ref_x,
+                              features=[(_capi.FEAT_POSITION, list(range(self.input_atom_num)))])
+        if tangent:
+            _refuse_ref_tangent(self)
+            entry = _get_entry(self, x, "align_grad", build)
+            with torch.cuda.device(x.device):
+                entry.sync_ref(_device_buffer(self.ref_x, x))
+            return _FeaturesJvp.apply(x, entry).view(x.shape[0], self.input_atom_num, 3)
         if x.shape[0] == 0:
             return torch.empty_like(x)
         if _wants_grad(x):
-            # the aligned frame == alignment + one position item per atom: that plan has a backward kernel
-            def build():
-                return _capi.Plan(self.input_atom_num, align_idx=self._local_align_atom_indices, ref_x=self.ref_x,
-                                  features=[(_capi.FEAT_POSITION, list(range(self.input_atom_num)))])
             entry = _get_entry(self, x, "align_grad", build)
             with torch.cuda.device(x.device):
                 entry.sync_ref(_device_buffer(self.ref_x, x))
@@ -656,7 +843,12 @@ def _script_features(feature_owner, align_layer):
 
 def _run_features(feature_owner, x, align_layer, plan_owner=None):
     """features (optionally of the aligned frame) through one fused launch."""
-    x = _device_input(x, backward_ok=True)
+    tangent = _transform_active() and (_has_tangent(x) or (align_layer is not None and _has_tangent(align_layer.ref_x)))
+    if tangent:
+        _refuse_ref_tangent(align_layer)
+        x = _tangent_input(x)
+    else:
+        x = _device_input(x, backward_ok=True)
     spec, uav = _feature_spec(feature_owner)
     owner = plan_owner if plan_owner is not None else feature_owner
 
@@ -667,6 +859,11 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
                           ref_x=align_layer.ref_x, features=spec, use_angle_value=uav)
 
     entry = _get_entry(owner, x, "features", build)
+    if tangent:
+        with torch.cuda.device(x.device):
+            if align_layer is not None:
+                entry.sync_ref(_device_buffer(align_layer.ref_x, x))
+        return _FeaturesJvp.apply(x, entry)
     if x.shape[0] == 0:
         return torch.empty((0, entry.plan.feature_dim), dtype=x.dtype, device=x.device)
     if x.dtype == torch.float64:
@@ -825,6 +1022,14 @@ class MolANN(_PlanOwner, torch.nn.Module):
             entry.plan.value_and_vjp(x, g, y, dx)
         return y, dx
 
+    def _tangent_present(self, x):
+        if _has_tangent(x):
+            return True
+        al = getattr(self.preprocessing_layer, "align_layer", None)
+        if isinstance(al, AlignmentLayer) and _has_tangent(al.ref_x):
+            return True
+        return any(_has_tangent(p) for p in self.ann_layers.parameters())
+
     def last_launch_info(self):
         """Name + geometry of the kernels the last forward launched (bench / profiles / tests)."""
         st = self.__dict__.get("_fast")
@@ -888,6 +1093,10 @@ class MolANN(_PlanOwner, torch.nn.Module):
         return st
 
     def forward(self, x):
+        # ---- forward mode: a tangent on x or on the ann_layers parameters (fwAD dual, torch.func transform).  The preprocessing
+        # layer's tangent kernel, then ann_layers as the torch module it is (torch's forward AD of Linear and the activations).
+        if _transform_active() and self._tangent_present(x):
+            return self.ann_layers(self.preprocessing_layer(x))
         # ---- inference fast path (a 1024-frame call is ~3 us of kernel: the host side is what a caller waits for; tools/latency_breakdown.py).
         # Taken only when nothing it skips could matter: the same module objects as when the plan was made, a float32 [N > 0, n_inp, 3]
         # tensor on the plan's device, nothing to record for autograd.  Everything else takes the general path below, checks and all.

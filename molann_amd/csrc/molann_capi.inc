@@ -59,6 +59,7 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
     p->align_first = d->n_align > 0 ? d->align_idx[0] : 0;
     p->n_features = d->n_features;
     p->n_items = (int)items.size();
+    for (const ItemDev& it : items) p->has_position_items = p->has_position_items || it.type == IT_POSITION;
     p->d_feat = d_feat;
     p->use_angle_value = d->use_angle_value;
     p->n_layers = d->n_layers;
@@ -1826,5 +1827,62 @@ int molann_selftest_kabsch_backward(const double* H9, const float* R9, const flo
 }
 
 float molann_selftest_act_derivative(int act, float z) { return act_derivative(act, z, apply_activation(act, z)); }
+
+static int selftest_item_type(int type, int use_angle_value) {
+    if (type == MOLANN_FEAT_ANGLE) return use_angle_value ? IT_ANGLE_VAL : IT_ANGLE_COS;
+    if (type == MOLANN_FEAT_BOND) return IT_BOND;
+    if (type == MOLANN_FEAT_DIHEDRAL) return use_angle_value ? IT_DIHEDRAL_VAL : IT_DIHEDRAL_CS;
+    if (type == MOLANN_FEAT_POSITION) return IT_POSITION;
+    return -1;
+}
+
+int molann_selftest_feature_tangent_f32(int type, int use_angle_value, const float* a, const float* t, float* out3, float* dout3) {
+    if (!a || !t || !out3 || !dout3) return MOLANN_E_NULL;
+    const int it = selftest_item_type(type, use_angle_value);
+    if (it < 0) return MOLANN_E_FEATURE;
+    float v[3] = {0.f, 0.f, 0.f}, dv[3] = {0.f, 0.f, 0.f};
+    const int w = eval_item_tangent(it, v3(a[0], a[1], a[2]), v3(a[3], a[4], a[5]), v3(a[6], a[7], a[8]), v3(a[9], a[10], a[11]),
+                                    v3(t[0], t[1], t[2]), v3(t[3], t[4], t[5]), v3(t[6], t[7], t[8]), v3(t[9], t[10], t[11]), v, dv);
+    for (int i = 0; i < w; ++i) { out3[i] = v[i]; dout3[i] = dv[i]; }
+    return w;
+}
+
+int molann_selftest_feature_tangent_f64(int type, int use_angle_value, const double* a, const double* t, double* out3, double* dout3) {
+    if (!a || !t || !out3 || !dout3) return MOLANN_E_NULL;
+    const int it = selftest_item_type(type, use_angle_value);
+    if (it < 0) return MOLANN_E_FEATURE;
+    double v[3] = {0., 0., 0.}, dv[3] = {0., 0., 0.};
+    const int w = eval_item_tangent_f64(it, v3d(a[0], a[1], a[2]), v3d(a[3], a[4], a[5]), v3d(a[6], a[7], a[8]), v3d(a[9], a[10], a[11]),
+                                        v3d(t[0], t[1], t[2]), v3d(t[3], t[4], t[5]), v3d(t[6], t[7], t[8]), v3d(t[9], t[10], t[11]), v, dv);
+    for (int i = 0; i < w; ++i) { out3[i] = v[i]; dout3[i] = dv[i]; }
+    return w;
+}
+
+int molann_selftest_kabsch_rotation_f64(const double* H9, double e0, double* R9) {
+    if (!H9 || !R9) return MOLANN_E_NULL;
+    double h[9], r[9];
+    for (int i = 0; i < 9; ++i) h[i] = H9[i];
+    kabsch_rotation_t<double, double>(h, e0, r);
+    for (int i = 0; i < 9; ++i) R9[i] = r[i];
+    return MOLANN_OK;
+}
+
+int molann_selftest_kabsch_tangent(const double* H9, const double* R9, const double* dH9, double* dR9) {
+    if (!H9 || !R9 || !dH9 || !dR9) return MOLANN_E_NULL;
+    double h[9], r[9], dh[9], dr[9];
+    for (int i = 0; i < 9; ++i) { h[i] = H9[i]; r[i] = R9[i]; dh[i] = dH9[i]; }
+    kabsch_rotation_tangent_t<double>(h, r, dh, dr);
+    for (int i = 0; i < 9; ++i) dR9[i] = dr[i];
+    return MOLANN_OK;
+}
+
+int molann_selftest_kabsch_backward_f64(const double* H9, const double* R9, const double* GR9, double* GH9) {
+    if (!H9 || !R9 || !GR9 || !GH9) return MOLANN_E_NULL;
+    double h[9], r[9], gr[9], gh[9];
+    for (int i = 0; i < 9; ++i) { h[i] = H9[i]; r[i] = R9[i]; gr[i] = GR9[i]; }
+    kabsch_rotation_backward_t<double, double>(h, r, gr, gh);
+    for (int i = 0; i < 9; ++i) GH9[i] = gh[i];
+    return MOLANN_OK;
+}
 
 } // extern "C"

@@ -48,6 +48,7 @@ struct molann_plan {
     int family;        // 0 lane-per-frame, 1 wave-per-frame
     bool fused_mlp;    // lane kernel runs the MLP itself
     bool lane_mlp;     // the MLP is within the fused MLP's limits: on its own it runs in mlp_lane_kernel
+    bool has_position_items; // the forward mode needs the rotation's tangent (molann_jvp.inc)
     // device memory (one allocation)
     unsigned char* blob;
     int* d_align_idx;

@@ -615,4 +615,126 @@ MOLANN_HD void eval_item_backward_f64(int type, V3d a0, V3d a1, V3d a2, V3d a3, 
     }
 }
 
+// =================================================================================================
+// forward mode (tangents: the directional derivatives torch.autograd.forward_ad / torch.func.jvp ask for)
+// =================================================================================================
+template <typename T> struct VecOf;
+template <> struct VecOf<float> { typedef V3 type; };
+template <> struct VecOf<double> { typedef V3d type; };
+MOLANN_HD float tsqrt(float a) { return sqrtf(a); }
+MOLANN_HD double tsqrt(double a) { return sqrt(a); }
+MOLANN_HD float tacos(float a) { return acosf(a); }
+MOLANN_HD double tacos(double a) { return acos(a); }
+MOLANN_HD float tatan2(float y, float x) { return atan2f(y, x); }
+MOLANN_HD double tatan2(double y, double x) { return atan2(y, x); }
+
+// One item's values (as eval_item / eval_item_f64) and their derivatives along the atoms' tangents t0..t3.  The forward-mode
+// twin of eval_item_backward: exact divisions and square roots, no clamps (the reference's autograd has none either).
+template <typename T, typename V = typename VecOf<T>::type>
+MOLANN_HD int eval_item_tangent_t(int type, V a0, V a1, V a2, V a3, V t0, V t1, V t2, V t3, T (&out)[3], T (&dout)[3]) {
+    switch (type) {
+    case IT_BOND: {
+        const V r = a1 - a0, dr = t1 - t0;
+        const T d = tsqrt(dot(r, r));
+        out[0] = d;
+        dout[0] = d > (T)0 ? dot(r, dr) / d : (T)0;   // |r| = 0: the subgradient 0 the backward takes
+        return 1;
+    }
+    case IT_ANGLE_COS:
+    case IT_ANGLE_VAL: {
+        const V u = a0 - a1, v = a2 - a1, du = t0 - t1, dv = t2 - t1;
+        const T uu = dot(u, u), vv = dot(v, v);
+        const T inv_uv = (T)1 / (tsqrt(uu) * tsqrt(vv));
+        const T c = dot(u, v) * inv_uv;
+        // dc = (du.v + u.dv) / (|u||v|) - c (u.du / |u|^2 + v.dv / |v|^2)
+        const T dc = (dot(du, v) + dot(u, dv)) * inv_uv - c * (dot(u, du) / uu + dot(v, dv) / vv);
+        if (type == IT_ANGLE_VAL) {
+            out[0] = tacos(c);
+            dout[0] = -dc / tsqrt((T)1 - c * c);
+        } else {
+            out[0] = c;
+            dout[0] = dc;
+        }
+        return 1;
+    }
+    case IT_DIHEDRAL_CS:
+    case IT_DIHEDRAL_VAL: {
+        const V r12 = a1 - a0, r23 = a2 - a1, r34 = a3 - a2;
+        const V d12 = t1 - t0, d23 = t2 - t1, d34 = t3 - t2;
+        const V n1 = cross(r12, r23), n2 = cross(r23, r34);
+        const V dn1 = cross(d12, r23) + cross(r12, d23), dn2 = cross(d23, r34) + cross(r23, d34);
+        const T L = tsqrt(dot(r23, r23));
+        const T dL = L > (T)0 ? dot(r23, d23) / L : (T)0;
+        const T n1r34 = dot(n1, r34);
+        const T C = dot(n1, n2), S = n1r34 * L;
+        const T dC = dot(dn1, n2) + dot(n1, dn2);
+        const T dS = (dot(dn1, r34) + dot(n1, d34)) * L + n1r34 * dL;
+        const T rad2 = C * C + S * S;
+        if (type == IT_DIHEDRAL_VAL) { // d atan2(S, C) = (C dS - S dC) / (C^2 + S^2)
+            out[0] = tatan2(S, C);
+            dout[0] = (C * dS - S * dC) / rad2;
+            return 1;
+        }
+        const T inv_rad = (T)1 / tsqrt(rad2);
+        const T proj = (C * dC + S * dS) * inv_rad * inv_rad * inv_rad;   // d(1/rad) = -proj
+        out[0] = C * inv_rad;
+        out[1] = S * inv_rad;
+        dout[0] = dC * inv_rad - C * proj;
+        dout[1] = dS * inv_rad - S * proj;
+        return 2;
+    }
+    default: // IT_POSITION
+        out[0] = a0.x; out[1] = a0.y; out[2] = a0.z;
+        dout[0] = t0.x; dout[1] = t0.y; dout[2] = t0.z;
+        return 3;
+    }
+}
+
+MOLANN_HD int eval_item_tangent(int type, V3 a0, V3 a1, V3 a2, V3 a3, V3 t0, V3 t1, V3 t2, V3 t3, float (&out)[3], float (&dout)[3]) {
+    return eval_item_tangent_t<float>(type, a0, a1, a2, a3, t0, t1, t2, t3, out, dout);
+}
+MOLANN_HD int eval_item_tangent_f64(int type, V3d a0, V3d a1, V3d a2, V3d a3, V3d t0, V3d t1, V3d t2, V3d t3, double (&out)[3],
+                                    double (&dout)[3]) {
+    return eval_item_tangent_t<double>(type, a0, a1, a2, a3, t0, t1, t2, t3, out, dout);
+}
+
+// Tangent of kabsch_rotation: given H, the rotation R it produced and a direction dH, returns dR.  The adjoint of
+// kabsch_rotation_backward_t's closed form: with S = R^T H (symmetric at the optimum), dR = R [w]x where
+// (tr(S) I - S) w = vee(M - M^T), M = R^T dH.  tr(S) I - S is invertible exactly when the rotation is well defined
+// (s2 + d s3 > 0): a planar three-atom alignment needs no special case.  Where it is not, dR = 0, as the backward's G_H.
+template <typename T>
+MOLANN_HD void kabsch_rotation_tangent_t(const T (&H)[9], const T (&R)[9], const T (&dH)[9], T (&dR)[9]) {
+    T S[9], M[9];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            T s = (T)0, m = (T)0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { s = tfma(R[3 * k + a], H[3 * k + b], s); m = tfma(R[3 * k + a], dH[3 * k + b], m); }
+            S[3 * a + b] = s;
+            M[3 * a + b] = m;
+        }
+    const T s01 = (T)0.5 * (S[1] + S[3]), s02 = (T)0.5 * (S[2] + S[6]), s12 = (T)0.5 * (S[5] + S[7]);
+    const T tr = S[0] + S[4] + S[8];
+    const T b00 = tr - S[0], b11 = tr - S[4], b22 = tr - S[8], b01 = -s01, b02 = -s02, b12 = -s12;
+    const T m0 = M[7] - M[5], m1 = M[2] - M[6], m2 = M[3] - M[1];
+    const T c00 = b11 * b22 - b12 * b12, c01 = b02 * b12 - b01 * b22, c02 = b01 * b12 - b02 * b11;
+    const T c11 = b00 * b22 - b02 * b02, c12 = b01 * b02 - b00 * b12, c22 = b00 * b11 - b01 * b01;
+    const T det = b00 * c00 + b01 * c01 + b02 * c02;
+    constexpr T tiny = sizeof(T) == 8 ? (T)1e-300 : (T)1e-30;
+    const T inv = (det > tiny || det < -tiny) ? (T)1 / det : (T)0;
+    const T w0 = (c00 * m0 + c01 * m1 + c02 * m2) * inv;
+    const T w1 = (c01 * m0 + c11 * m1 + c12 * m2) * inv;
+    const T w2 = (c02 * m0 + c12 * m1 + c22 * m2) * inv;
+    // dR = R [w]x ,  [w]x = [[0,-w2,w1],[w2,0,-w0],[-w1,w0,0]]
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const T r0 = R[3 * a], r1 = R[3 * a + 1], r2 = R[3 * a + 2];
+        dR[3 * a + 0] = r1 * w2 - r2 * w1;
+        dR[3 * a + 1] = r2 * w0 - r0 * w2;
+        dR[3 * a + 2] = r0 * w1 - r1 * w0;
+    }
+}
+
 } // namespace molann
