@@ -949,8 +949,18 @@ at::Tensor activation(int64_t code, const at::Tensor& t) {
     }
 }
 
+// a forward-mode tangent (torch.autograd.forward_ad dual, torch.func.jvp / jacfwd: both at forward-AD level 0)
+bool has_tangent(const at::Tensor& t) { return t.defined() && t._fw_grad(/*level=*/0).defined(); }
+
 at::Tensor run_autograd(const at::Tensor& x, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
                         std::vector<at::Tensor> biases) {
+    // molann::run has no forward-mode derivative: without this check a float64 dual went below autograd and came back as the
+    // primal with no tangent, and a float32 one failed inside torch's C++ custom-Function machinery
+    bool tangent = has_tangent(x) || has_tangent(ref_x);
+    for (const auto& w : weights) tangent = tangent || has_tangent(w);
+    for (const auto& b : biases) tangent = tangent || has_tangent(b);
+    TORCH_CHECK(!tangent, "molann::run (a torch.jit.script'ed molann_amd module) has no forward-mode derivative: run "
+                "torch.autograd.forward_ad / torch.func.jvp / jacfwd on the eager molann_amd module instead");
     if (x.scalar_type() == at::kDouble) {
         // float64 (`model.double()`): gradients for the preprocessing come from molann_features_backward_f64; the MLP of a
         // float64 model under grad mode is ATen's (its parameters are read as they are anyway)

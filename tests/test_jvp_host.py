@@ -104,6 +104,75 @@ def test_kabsch_tangent_matches_oracle_jvp(case):
         assert float((got_dy - dy[0]).abs().max()) <= 1e-9 * max(scale, float(dy.abs().max())), name
 
 
+@pytest.mark.parametrize("regime", ["mirror", "flip180", "hinge", "offset"])
+def test_kabsch_tangent_on_far_frames_matches_oracle_jvp(regime):
+    """The tangent hook on covariances of frames far from the reference (tests/far_frames.py): the d = -1 branch, exact
+    180-degree turns, hinge motions, frames 100-1000 A from the origin.  Compared where the rotation is well conditioned."""
+    import far_frames as ff
+    from molann_amd import workloads as wl
+    L = _capi.lib()
+    xyz = wl.ALA_DIPEPTIDE_XYZ
+    for align in (list(range(22)), [1, 4, 6, 8, 14, 16, 18]):
+        ref = mo.center_reference(torch.from_numpy(np.asarray(xyz, np.float32)[align])).double()
+        frames = ff.draw(regime, xyz, align, 16, seed=4)
+        cond = ff.conditioning(frames, xyz, align)
+        xs = torch.from_numpy(frames).double()
+        vs = torch.randn(xs.shape, generator=torch.Generator().manual_seed(6), dtype=torch.float64)
+        compared = 0
+        for x, v, c in zip(xs, vs, cond):
+            H, R, dH, cen, dc = _kabsch_parts(x, v, align, ref)
+            dR = np.zeros(9)
+            assert L.molann_selftest_kabsch_tangent(_dp(H), _dp(R), _dp(dH), _dp(dR)) == 0
+            assert np.isfinite(dR).all(), (regime, dR)
+            if c < 1e-2:
+                continue
+            y, dy = torch.func.jvp(lambda a: mo.align_forward(a, align, ref), (x[None],), (v[None],))
+            Rt, dRt = torch.from_numpy(R).view(3, 3), torch.from_numpy(dR).view(3, 3)
+            got_dy = (v - dc) @ Rt + (x - cen) @ dRt
+            assert float(((x - cen) @ Rt - y[0]).abs().max()) <= 1e-9 * float(y.abs().max()), (regime, "y")
+            assert float((got_dy - dy[0]).abs().max()) <= 1e-9 * float(dy.abs().max()), (regime, len(align), float(c))
+            compared += 1
+        assert compared >= len(xs) // 2, (regime, compared)
+
+
+def test_kabsch_tangent_is_finite_on_singular_covariances():
+    """No defined rotation: all align atoms at one point (H = 0: dR = 0) or exactly on a line (rank 1), 1000 A out."""
+    L = _capi.lib()
+    ref = mo.center_reference(torch.randn(6, 3, generator=torch.Generator().manual_seed(1), dtype=torch.float64)).double()
+    line = np.outer(np.arange(6.0) - 2.5, [0.3, 0.5, 0.8])
+    for name, P in (("one point", np.full((6, 3), 1000.0)), ("collinear", line + 1000.0), ("collinear at 0", line)):
+        x = torch.from_numpy(P)
+        for seed in range(4):
+            v = torch.randn(x.shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+            H, R, dH, _, _ = _kabsch_parts(x, v, list(range(6)), ref)
+            assert np.isfinite(R).all(), name
+            dR = np.full(9, np.nan)
+            assert L.molann_selftest_kabsch_tangent(_dp(H), _dp(R), _dp(dH), _dp(dR)) == 0
+            assert np.isfinite(dR).all(), (name, dR)
+            if name == "one point":
+                assert not dR.any(), dR
+
+
+def test_scripted_module_refuses_forward_mode():
+    """molann::run has no forward-mode derivative: a dual or torch.func.jvp input raises (pointing to the eager module) before
+    any kernel runs, in float32 and float64, instead of returning the primal without a tangent."""
+    from torch.autograd import forward_ad as fwAD
+    from molann_amd import workloads as wl
+    from build_util import workload_model
+    for name in ("C3", "A3", "C2"):
+        w = wl.get_workload(name)
+        scripted = torch.jit.script(workload_model(w, torch.device("cpu")))
+        x = w.make_frames(2, seed=1)
+        for dtype in (torch.float32, torch.float64):
+            m = scripted.to(dtype)
+            xd = x.to(dtype)
+            with pytest.raises(RuntimeError, match="no forward-mode derivative.*eager molann_amd module"):
+                with fwAD.dual_level():
+                    m(fwAD.make_dual(xd, torch.ones_like(xd)))
+            with pytest.raises(RuntimeError, match="no forward-mode derivative"):
+                torch.func.jvp(m, (xd,), (torch.ones_like(xd),))
+
+
 def test_kabsch_tangent_is_the_adjoint_of_the_backward():
     """<dR, G_R> = <dH, G_H> with G_H from the backward's hook, for random directions and cotangents"""
     L = _capi.lib()
