@@ -192,6 +192,18 @@ int molann_features_jvp_f32(const molann_plan* plan, const float* x, const float
 int molann_features_jvp_f64(const molann_plan* plan, const double* x, const double* v, int64_t n_frames, int n_tangents, double* out,
                             double* tangent_out, molann_stream_t stream);
 
+/* -- second order ----------------------------------------------------------------------------- */
+/* The derivative of molann_features_backward_f64 along a direction, for create_graph=True through the float64 features (a
+ * loss on forces): for a cotangent g[n_frames, feature_dim] and a direction u[n_frames, n_inp, 3],
+ *   hx[n_frames, n_inp, 3]       = d/dx <u, J(x)^T g> = sum_k g_k Hess f_k(x) u   (the second-order adjoint),
+ *   hg[n_frames, feature_dim]    = J(x) u.
+ * Exact: the float64 backward's closed forms differentiated on a dual number, the rotation's tangent from the closed form of
+ * its adjoint (no difference quotients, no step).  Every plan with feature items (as molann_features_backward_f64), any frame
+ * size.  One launch (frames_hvp_f64_kernel; lane groups of 8..64 per frame; no atomics, so the results are identical run to
+ * run).  All pointers 8-byte aligned, contiguous. */
+int molann_features_hvp_f64(const molann_plan* plan, const double* x, const double* g, const double* u, int64_t n_frames, double* hx,
+                            double* hg, molann_stream_t stream);
+
 /* ann_layers ann.py:60-65 in float64 on features f[N, layer_dims[0]]: W, b HOST arrays of n_layers device pointers. */
 int molann_mlp_f64(const molann_plan* plan, const double* f, int64_t n_frames, const double* const* W, const double* const* b,
                    double* out, molann_stream_t stream);
@@ -315,6 +327,12 @@ int molann_selftest_feature_tangent_f64(int type, int use_angle_value, const dou
 int molann_selftest_kabsch_rotation_f64(const double* H9, double e0, double* R9);
 int molann_selftest_kabsch_tangent(const double* H9, const double* R9, const double* dH9, double* dR9);
 int molann_selftest_kabsch_backward_f64(const double* H9, const double* R9, const double* GR9, double* GH9);
+/* second order: the float64 item backward (ga12: 4 atoms x xyz) and its derivative along atom tangents t12 and a cotangent
+ * tangent dg3 (return the atom count); the Kabsch backward G_H and its derivative along (dH, dR, dG_R) */
+int molann_selftest_feature_backward_tangent_f64(int type, int use_angle_value, const double* atoms_xyz, const double* t12,
+                                                 const double* g3, const double* dg3, double* ga12, double* dga12);
+int molann_selftest_kabsch_backward_tangent(const double* H9, const double* R9, const double* GR9, const double* dH9, const double* dR9,
+                                            const double* dGR9, double* GH9, double* dGH9);
 
 #ifdef __cplusplus
 }

@@ -121,6 +121,9 @@ def lib():
             "molann_selftest_kabsch_rotation_f64": (i32, [vp, ctypes.c_double, vp]),
             "molann_selftest_kabsch_tangent": (i32, [vp, vp, vp, vp]),
             "molann_selftest_kabsch_backward_f64": (i32, [vp, vp, vp, vp]),
+            "molann_features_hvp_f64": (i32, [vp, vp, vp, vp, i64, vp, vp, vp]),
+            "molann_selftest_feature_backward_tangent_f64": (i32, [i32, i32, vp, vp, vp, vp, vp, vp]),
+            "molann_selftest_kabsch_backward_tangent": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -265,6 +268,14 @@ class Plan(object):
     def features_jvp_f64(self, x, v, out, tangent_out):
         """`features_jvp` in float64."""
         return self._jvp("molann_features_jvp_f64", x, v, out, tangent_out)
+
+    def features_hvp_f64(self, x, g, u, hx, hg):
+        """The derivative of `features_backward_f64` along u, exact, in one launch: ``hx = d/dx <u, J(x)^T g>`` [N, n_inp, 3] and
+        ``hg = J(x) u`` [N, feature_dim]; x, u, hx [N, n_inp, 3] and g, hg [N, feature_dim], float64, contiguous."""
+        code = _lib.molann_features_hvp_f64(self._handle, x.data_ptr(), g.data_ptr(), u.data_ptr(), x.shape[0], hx.data_ptr(),
+                                            hg.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if code != 0:
+            raise MolannHipError(code, "molann_features_hvp_f64")
 
     def mlp_f64(self, f, weights, biases, out):
         n = len(weights)

@@ -327,8 +327,10 @@ class _FeatBackward64(torch.autograd.Function):
     """``gx = J(x)^T g`` of the float64 features (`molann_features_backward_f64`) as a node that can itself be differentiated -
     what ``create_graph=True`` needs (second-order terms of a loss on forces; the reference gets them from autograd through its
     SVD, `ann.py:188-197`).  For a cotangent ``v`` on ``gx`` its backward needs ``d/dx [v . J(x)^T g]`` and ``d/dg [v . J(x)^T g] = J(x) v``:
-    both are directional derivatives along ``v`` - of the first-order kernel's own output and of the features - taken as CENTRAL
-    DIFFERENCES of the float64 kernels at the points `_difference_points` gives.  Four launches; itself first-order: under
+    both are directional derivatives along ``v`` - of the first-order kernel's own output and of the features - and one launch of
+    `molann_features_hvp_f64` gives both EXACTLY (the float64 backward's closed forms differentiated on a dual number).  Central
+    differences of the float64 kernels at the points `_difference_points` gives remain only for a plan that kernel would refuse
+    with MOLANN_E_UNSUPPORTED (there is none: every plan the float64 backward serves is covered).  Itself first-order: under
     ``create_graph=True`` its backward raises, as FeatBackward64Fn's does (``once_differentiable`` would not: the error node it
     leaves hangs off detached copies, so ``torch.autograd.grad`` with respect to x prunes it and drops the term in silence)."""
 
@@ -347,7 +349,16 @@ class _FeatBackward64(torch.autograd.Function):
             raise RuntimeError("molann_amd: gradients of order three are not available (the double backward is first-order itself)")
         x, g = ctx.saved_tensors
         plan = ctx.entry.plan
-        xp, xm, inv = _difference_points(x, v.contiguous().double())
+        v = v.contiguous().double()
+        hx, hg = torch.empty_like(x), torch.empty_like(g)
+        try:
+            with torch.cuda.device(x.device):
+                plan.features_hvp_f64(x, g, v, hx, hg)
+            return (hx if ctx.needs_input_grad[0] else None), (hg if ctx.needs_input_grad[1] else None), None
+        except _capi.MolannHipError as e:
+            if e.code != _capi.E_UNSUPPORTED:
+                raise
+        xp, xm, inv = _difference_points(x, v)
         gxp, gxm = torch.empty_like(x), torch.empty_like(x)
         fp = torch.empty((x.shape[0], plan.feature_dim), dtype=torch.float64, device=x.device)
         fm = torch.empty_like(fp)

@@ -200,6 +200,11 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
     const size_t o_va_atoms = carve(sizeof(int) * std::max<size_t>(1, va_atoms.size()));
     const size_t o_va_ptr = carve(sizeof(int) * std::max<size_t>(1, va_ptr.size()));
     const size_t o_va_list = carve(sizeof(int) * std::max<size_t>(1, va_list.size()));
+    // second order without atomics: every atom's item slots, then its align slots, in a fixed order (molann_hvp.inc)
+    std::vector<int> hv_ptr, hv_list;
+    if (p->n_items > 0) hvp_tables(d->n_inp, items, d->align_idx, d->n_align, hv_ptr, hv_list);
+    const size_t o_hv_ptr = carve(sizeof(int) * std::max<size_t>(1, hv_ptr.size()));
+    const size_t o_hv_list = carve(sizeof(int) * std::max<size_t>(1, hv_list.size()));
     // AlignmentLayer.forward under autograd arrives as a feature plan with ONE position item per atom, in atom order: its
     // feature rows are the aligned frame, its backward the dense gradient of the alignment (frames_align_bwd_regs_kernel)
     std::vector<int> align_slot;
@@ -317,6 +322,7 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
     p->d_bw_list = (int*)(p->blob + o_bw_list); p->d_bw_align = (int*)(p->blob + o_bw_align);
     p->d_align_slot = (int*)(p->blob + o_align_slot);
     p->d_va_atoms = (int*)(p->blob + o_va_atoms); p->d_va_ptr = (int*)(p->blob + o_va_ptr); p->d_va_list = (int*)(p->blob + o_va_list);
+    p->d_hv_ptr = (int*)(p->blob + o_hv_ptr); p->d_hv_list = (int*)(p->blob + o_hv_list);
     p->d_wlane = (float*)(p->blob + o_wlane);
     p->d_wmfma = (void*)(p->blob + o_wmfma);
     p->d_work = (float*)(p->blob + o_work);
@@ -375,6 +381,10 @@ int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
         e = hipMemcpy(p->d_va_atoms, va_atoms.data(), sizeof(int) * va_atoms.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(p->d_va_ptr, va_ptr.data(), sizeof(int) * va_ptr.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(p->d_va_list, va_list.data(), sizeof(int) * va_list.size(), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && !hv_ptr.empty()) {
+        e = hipMemcpy(p->d_hv_ptr, hv_ptr.data(), sizeof(int) * hv_ptr.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !hv_list.empty()) e = hipMemcpy(p->d_hv_list, hv_list.data(), sizeof(int) * hv_list.size(), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) { (void)hipFree(p->blob); delete p; return (int)e; }
     snprintf(p->last_info, sizeof(p->last_info), "(no launch yet)");

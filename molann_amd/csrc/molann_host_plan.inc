@@ -99,6 +99,7 @@ struct molann_plan {
     int gvjp_state, gvjp_b, gvjp_wpb, gvjp_lds, gvjp_bpc;
     int* d_va_atoms; int* d_va_ptr; int* d_va_list;   // ... its touched atoms and what each gathers (group_vjp_tables)
     int va_touched, va_list_len;
+    int* d_hv_ptr; int* d_hv_list;   // second order (molann_hvp.inc): per atom, its item slots (4 it + j) and align slots (-(i + 1))
     hipModule_t mbwd_mod;
     hipFunction_t mbwd_fn;     // backward of the fused family's MLP (molann_mlp_bwd.inc), compiled at the first backward
     int mbwd_state, mbwd_wpb;
@@ -256,5 +257,21 @@ void fill_pre_args(const molann_plan* p, PreArgs& a, long n_frames, int mode, in
     a.ablate = debug_env().ablate;
 }
 
+
+// per atom of the frame (hv_ptr: n_inp + 1 offsets into hv_list): the slots 4 it + j of the items that name it (item order), then
+// -(i + 1) for each place i it holds in the alignment set (an atom named twice there has two rows) - frames_hvp_kernel's gather
+inline void hvp_tables(int n_inp, const std::vector<ItemDev>& items, const int* align_idx, int n_align, std::vector<int>& ptr,
+                       std::vector<int>& list) {
+    std::vector<std::vector<int>> per(n_inp);
+    for (size_t it = 0; it < items.size(); ++it)
+        for (int j = 0; j < item_atoms(items[it].type); ++j) per[items[it].idx[j]].push_back((int)(4 * it + j));
+    for (int i = 0; i < n_align; ++i) per[align_idx[i]].push_back(-(i + 1));
+    ptr.assign(1, 0);
+    list.clear();
+    for (int k = 0; k < n_inp; ++k) {
+        list.insert(list.end(), per[k].begin(), per[k].end());
+        ptr.push_back((int)list.size());
+    }
+}
 
 } // namespace

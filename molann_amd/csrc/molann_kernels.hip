@@ -58,9 +58,11 @@ using namespace molann;
 #include "molann_dev_bwd.inc"
 #include "molann_dev_mlp.inc"
 #include "molann_dev_jvp.inc"
+#include "molann_dev_hvp.inc"
 // Host code (what `make san` instruments: -fno-gpu-sanitize leaves the device code alone):
 #include "molann_host_plan.inc"
 #include "molann_host_jit.inc"
 #include "molann_host_launch.inc"
 #include "molann_capi.inc"
 #include "molann_jvp.inc"
+#include "molann_hvp.inc"

@@ -737,4 +737,174 @@ MOLANN_HD void kabsch_rotation_tangent_t(const T (&H)[9], const T (&R)[9], const
     }
 }
 
+// =================================================================================================
+// second order: tangents of the reverse pass (forward over reverse).  For a cotangent g on the features and a direction u on
+// the atoms, d/dx <u, J(x)^T g> = sum_k g_k Hess f_k(x) u is the derivative of the float64 backward along u.  The float64
+// backward's closed forms are instantiated on a dual number (value + one tangent): every product, quotient and square root
+// carries its first-order term, so the result is the exact derivative of the formulas, with nothing iterative inside
+// (the rotation's own tangent dR comes from kabsch_rotation_tangent_t, not from differentiating the solver).
+// =================================================================================================
+struct Dual {
+    double v, d;   // value, tangent
+};
+MOLANN_HD Dual dual(double v, double d) { Dual r; r.v = v; r.d = d; return r; }
+MOLANN_HD Dual operator+(Dual a, Dual b) { return dual(a.v + b.v, a.d + b.d); }
+MOLANN_HD Dual operator-(Dual a, Dual b) { return dual(a.v - b.v, a.d - b.d); }
+MOLANN_HD Dual operator-(Dual a) { return dual(-a.v, -a.d); }
+MOLANN_HD Dual operator-(double s, Dual a) { return dual(s - a.v, -a.d); }
+MOLANN_HD Dual operator*(Dual a, Dual b) { return dual(a.v * b.v, fma(a.v, b.d, a.d * b.v)); }
+MOLANN_HD Dual operator*(double s, Dual a) { return dual(s * a.v, s * a.d); }
+MOLANN_HD Dual operator/(Dual a, Dual b) {
+    const double q = a.v / b.v;
+    return dual(q, (a.d - q * b.d) / b.v);
+}
+MOLANN_HD Dual operator/(double s, Dual b) {
+    const double q = s / b.v;
+    return dual(q, -q * b.d / b.v);
+}
+MOLANN_HD Dual tfma(Dual a, Dual b, Dual c) { return dual(fma(a.v, b.v, c.v), fma(a.v, b.d, fma(a.d, b.v, c.d))); }
+MOLANN_HD Dual tsqrt(Dual a) {
+    const double s = sqrt(a.v);
+    return dual(s, s > 0.0 ? 0.5 * a.d / s : 0.0);
+}
+MOLANN_HD double value_of(double a) { return a; }
+MOLANN_HD double value_of(Dual a) { return a.v; }
+
+struct V3x {
+    Dual x, y, z;
+};
+MOLANN_HD V3x v3x(Dual x, Dual y, Dual z) { V3x r; r.x = x; r.y = y; r.z = z; return r; }
+MOLANN_HD V3x v3x(V3d p, V3d t) { return v3x(dual(p.x, t.x), dual(p.y, t.y), dual(p.z, t.z)); }
+MOLANN_HD V3x operator-(V3x a, V3x b) { return v3x(a.x - b.x, a.y - b.y, a.z - b.z); }
+MOLANN_HD V3x operator+(V3x a, V3x b) { return v3x(a.x + b.x, a.y + b.y, a.z + b.z); }
+MOLANN_HD V3x operator*(Dual s, V3x a) { return v3x(s * a.x, s * a.y, s * a.z); }
+MOLANN_HD Dual dot(V3x a, V3x b) { return tfma(a.z, b.z, tfma(a.y, b.y, a.x * b.x)); }
+MOLANN_HD V3x cross(V3x a, V3x b) { return v3x(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+MOLANN_HD void axpy(V3x& acc, Dual s, V3x a) { acc.x = tfma(s, a.x, acc.x); acc.y = tfma(s, a.y, acc.y); acc.z = tfma(s, a.z, acc.z); }
+MOLANN_HD V3d val3(V3x a) { return v3d(a.x.v, a.y.v, a.z.v); }
+MOLANN_HD V3d tan3(V3x a) { return v3d(a.x.d, a.y.d, a.z.d); }
+
+// eval_item_backward_f64's formulas on any scalar T (double, Dual) with vectors V: the same branches, taken on the values
+template <typename T, typename V>
+MOLANN_HD void eval_item_backward_gen(int type, V a0, V a1, V a2, V a3, const T (&g)[3], V& ga0, V& ga1, V& ga2, V& ga3) {
+    const T zero = (T)(0.0 * g[0]);
+    switch (type) {
+    case IT_BOND: {
+        const V r = a1 - a0;
+        const T d2 = dot(r, r);
+        const T inv = value_of(d2) > 0.0 ? (T)(1.0 / tsqrt(d2)) : zero;
+        axpy(ga1, g[0] * inv, r);
+        axpy(ga0, -(g[0] * inv), r);
+        return;
+    }
+    case IT_ANGLE_COS:
+    case IT_ANGLE_VAL: {
+        const V u = a0 - a1, v = a2 - a1;
+        const T uu = dot(u, u), vv = dot(v, v), uv = dot(u, v);
+        const T inv_uv = 1.0 / (tsqrt(uu) * tsqrt(vv));
+        const T c = uv * inv_uv;
+        T gc = g[0];
+        if (type == IT_ANGLE_VAL) gc = -(g[0] / tsqrt(1.0 - c * c));
+        V gu = zero * u, gv = zero * v;
+        axpy(gu, gc * inv_uv, v); axpy(gu, -(gc * c / uu), u);
+        axpy(gv, gc * inv_uv, u); axpy(gv, -(gc * c / vv), v);
+        ga0 = ga0 + gu;
+        ga2 = ga2 + gv;
+        ga1 = ga1 - (gu + gv);
+        return;
+    }
+    case IT_DIHEDRAL_CS:
+    case IT_DIHEDRAL_VAL: {
+        const V r12 = a1 - a0, r23 = a2 - a1, r34 = a3 - a2;
+        const V n1 = cross(r12, r23), n2 = cross(r23, r34);
+        const T L2 = dot(r23, r23);
+        const T L = tsqrt(L2);
+        const T n1r34 = dot(n1, r34);
+        const T C = dot(n1, n2), S = n1r34 * L;
+        const T rad2 = tfma(C, C, S * S);
+        T gC, gS;
+        if (type == IT_DIHEDRAL_CS) {
+            const T inv_rad = 1.0 / tsqrt(rad2);
+            const T proj = (g[0] * C + g[1] * S) * inv_rad * inv_rad * inv_rad;
+            gC = g[0] * inv_rad - proj * C;
+            gS = g[1] * inv_rad - proj * S;
+        } else {
+            gC = -(g[0] * S / rad2);
+            gS = g[0] * C / rad2;
+        }
+        V gn1 = gC * n2; axpy(gn1, gS * L, r34);
+        const V gn2 = gC * n1;
+        V gr34 = (gS * L) * n1;
+        V gr23 = (value_of(L) > 0.0 ? (T)(gS * n1r34 / L) : zero) * r23;
+        const V gr12 = cross(r23, gn1);
+        gr23 = gr23 + cross(gn1, r12) + cross(r34, gn2);
+        gr34 = gr34 + cross(gn2, r23);
+        ga0 = ga0 - gr12;
+        ga1 = ga1 + (gr12 - gr23);
+        ga2 = ga2 + (gr23 - gr34);
+        ga3 = ga3 + gr34;
+        return;
+    }
+    default: // IT_POSITION
+        ga0.x = ga0.x + g[0]; ga0.y = ga0.y + g[1]; ga0.z = ga0.z + g[2];
+        return;
+    }
+}
+
+// Tangent of eval_item_backward_f64 along the atoms' tangents t0..t3 and a cotangent tangent dg: ga[j] (the gradient itself)
+// and dga[j] (its derivative) are ACCUMULATED into.  With dg = 0, dga[j] = sum_k g_k Hess(f_k) t restricted to atom j.
+template <typename T = double>
+MOLANN_HD void eval_item_backward_tangent_t(int type, V3d a0, V3d a1, V3d a2, V3d a3, V3d t0, V3d t1, V3d t2, V3d t3, const T (&g)[3],
+                                            const T (&dg)[3], V3d (&ga)[4], V3d (&dga)[4]) {
+    const Dual gd[3] = {dual(g[0], dg[0]), dual(g[1], dg[1]), dual(g[2], dg[2])};
+    V3x gx[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gx[j] = v3x(ga[j], dga[j]);
+    eval_item_backward_gen<Dual, V3x>(type, v3x(a0, t0), v3x(a1, t1), v3x(a2, t2), v3x(a3, t3), gd, gx[0], gx[1], gx[2], gx[3]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { ga[j] = val3(gx[j]); dga[j] = tan3(gx[j]); }
+}
+
+// Tangent of kabsch_rotation_backward_t (G_H = R [n]x, n = (tr(S) I - S)^-1 vee(R^T G_R - G_R^T R), S = R^T H) along
+// (dH, dR, dG_R): GH receives G_H, dGH its derivative.  dR is the rotation's tangent for dH (kabsch_rotation_tangent_t).
+// Where the rotation is ill defined (det of tr(S) I - S below 1e-300) both are zero, as the backward's G_H.
+template <typename T = double>
+MOLANN_HD void kabsch_rotation_backward_tangent_t(const T (&H)[9], const T (&R)[9], const T (&GR)[9], const T (&dH)[9], const T (&dR)[9],
+                                                  const T (&dGR)[9], T (&GH)[9], T (&dGH)[9]) {
+    Dual S[9], M[9];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            Dual s = dual(0., 0.), m = dual(0., 0.);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const Dual r = dual(R[3 * k + a], dR[3 * k + a]);
+                s = tfma(r, dual(H[3 * k + b], dH[3 * k + b]), s);
+                m = tfma(r, dual(GR[3 * k + b], dGR[3 * k + b]), m);
+            }
+            S[3 * a + b] = s;
+            M[3 * a + b] = m;
+        }
+    const Dual s01 = 0.5 * (S[1] + S[3]), s02 = 0.5 * (S[2] + S[6]), s12 = 0.5 * (S[5] + S[7]);
+    const Dual tr = S[0] + S[4] + S[8];
+    const Dual b00 = tr - S[0], b11 = tr - S[4], b22 = tr - S[8], b01 = -s01, b02 = -s02, b12 = -s12;
+    const Dual m0 = M[7] - M[5], m1 = M[2] - M[6], m2 = M[3] - M[1];
+    const Dual c00 = b11 * b22 - b12 * b12, c01 = b02 * b12 - b01 * b22, c02 = b01 * b12 - b02 * b11;
+    const Dual c11 = b00 * b22 - b02 * b02, c12 = b01 * b02 - b00 * b12, c22 = b00 * b11 - b01 * b01;
+    const Dual det = b00 * c00 + b01 * c01 + b02 * c02;
+    const bool ok = det.v > 1e-300 || det.v < -1e-300;
+    const Dual inv = ok ? 1.0 / det : dual(0., 0.);
+    const Dual n0 = (c00 * m0 + c01 * m1 + c02 * m2) * inv;
+    const Dual n1 = (c01 * m0 + c11 * m1 + c12 * m2) * inv;
+    const Dual n2 = (c02 * m0 + c12 * m1 + c22 * m2) * inv;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const Dual r0 = dual(R[3 * a], dR[3 * a]), r1 = dual(R[3 * a + 1], dR[3 * a + 1]), r2 = dual(R[3 * a + 2], dR[3 * a + 2]);
+        const Dual g0 = r1 * n2 - r2 * n1, g1 = r2 * n0 - r0 * n2, g2 = r0 * n1 - r1 * n0;
+        GH[3 * a] = g0.v; GH[3 * a + 1] = g1.v; GH[3 * a + 2] = g2.v;
+        dGH[3 * a] = g0.d; dGH[3 * a + 1] = g1.d; dGH[3 * a + 2] = g2.d;
+    }
+}
+
 } // namespace molann

@@ -659,10 +659,11 @@ at::Tensor activation(int64_t code, const at::Tensor& t);
 // rebuilt as a DIFFERENTIABLE composition: the float64 features as a node (Features64Fn) whose backward - J(x)^T g, the float64
 // kernel - is itself a node (FeatBackward64Fn) with a backward of its own, and the MLP as ATen ops on the live parameters.
 // FeatBackward64Fn's backward needs, for a cotangent v on J^T g, d/dx [v . J(x)^T g] and d/dg [..] = J(x) v: directional
-// derivatives along v of the first-order kernel's output and of the features, taken as central differences of the float64
-// kernels, per frame with h = 6e-6 / |v|_max: a move of 6e-6 in the coordinates' own unit, set by the length scale of the geometry
-// (bonds, angles, dihedrals, the aligned set) and not by where the frame sits in the box (molann_amd/ann.py: _difference_points
-// is the same step in Python and says why).
+// derivatives along v of the first-order kernel's output and of the features, both exact from one launch of
+// molann_features_hvp_f64.  Central differences of the float64 kernels remain for a plan that kernel refuses (none does), per frame
+// with h = 6e-6 / |v|_max: a move of 6e-6 in the coordinates' own unit, set by the length scale of the geometry (bonds, angles,
+// dihedrals, the aligned set) and not by where the frame sits in the box (molann_amd/ann.py: _difference_points is the same step in
+// Python and says why).
 struct FeatBackward64Fn : public torch::autograd::Function<FeatBackward64Fn> {
     static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& x, const at::Tensor& g, std::vector<int64_t> desc,
                               const at::Tensor& ref_x) {
@@ -678,6 +679,25 @@ struct FeatBackward64Fn : public torch::autograd::Function<FeatBackward64Fn> {
         const std::vector<int64_t> desc = ctx->saved_data["desc"].toIntVector();
         at::AutoDispatchBelowADInplaceOrView below;
         const at::Tensor v = grad_outputs[0].to(at::kDouble).contiguous();
+        {   // exact, one launch: molann_features_hvp_f64 on the plan of desc in this library's cache (as run_backward finds it)
+            const at::Tensor xc = x.contiguous(), gc = g.contiguous();
+            const c10::DeviceGuard guard(xc.device());
+            auto e = entry_for(desc[1] == KIND_ALIGN ? align_as_features(desc) : desc, xc, ref_x);
+            at::Tensor hx = at::empty_like(xc), hg = at::empty_like(gc);
+            int rc = MOLANN_OK;
+            if (xc.size(0) > 0) {
+                hipStream_t stream = c10::hip::getCurrentHIPStream(xc.get_device()).stream();
+                std::lock_guard<std::mutex> lock(e->mu);
+                sync_live(*e, xc, ref_x, {}, {}, stream);
+                rc = molann_features_hvp_f64(e->plan, xc.data_ptr<double>(), gc.data_ptr<double>(), v.data_ptr<double>(), xc.size(0),
+                                             hx.data_ptr<double>(), hg.data_ptr<double>(), stream);
+            }
+            if (rc != MOLANN_E_UNSUPPORTED) {
+                check(rc, "molann_features_hvp_f64");
+                return {ctx->needs_input_grad(0) ? hx : at::Tensor(), ctx->needs_input_grad(1) ? hg : at::Tensor(), at::Tensor(), at::Tensor()};
+            }
+        }
+        // (central differences: only for a plan the exact kernel refuses - there is none)
         const at::Tensor vmax = v.abs().amax({1, 2}, true);
         const at::Tensor h = at::where(vmax > 0, 6e-6 / vmax.clamp_min(1e-300), at::zeros_like(vmax));
         const at::Tensor inv = at::where(h > 0, 0.5 / h.clamp_min(1e-300), at::zeros_like(h));
