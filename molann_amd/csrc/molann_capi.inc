@@ -31,596 +31,6 @@ const char* molann_error_string(int code) {
     }
 }
 
-int molann_plan_create(const molann_plan_desc* d, molann_plan** out_plan) {
-    if (!out_plan) return MOLANN_E_NULL;
-    *out_plan = nullptr;
-    const int v = validate_desc(d);
-    if (v != MOLANN_OK) return v;
-
-    // ---- expand the feature list into items (column order = list order, ann.py:473) ------------
-    std::vector<ItemDev> items;
-    const int d_feat = expand_items(d, items);
-    if (d->n_layers > 0 && d->n_features > 0 && d->layer_dims[0] != d_feat) return MOLANN_E_DESC;
-
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-
-    molann_plan* p = new (std::nothrow) molann_plan();
-    if (!p) return (int)hipErrorOutOfMemory;
-    memset(p, 0, sizeof(*p));
-    p->launch_mu = new std::mutex();
-    p->jit_mu = new std::mutex();
-    p->device = dev;
-    p->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    p->n_inp = d->n_inp;
-    p->n_align = d->n_align;
-    p->align_first = d->n_align > 0 ? d->align_idx[0] : 0;
-    p->n_features = d->n_features;
-    p->n_items = (int)items.size();
-    for (const ItemDev& it : items) p->has_position_items = p->has_position_items || it.type == IT_POSITION;
-    p->d_feat = d_feat;
-    p->use_angle_value = d->use_angle_value;
-    p->n_layers = d->n_layers;
-    p->act = d->activation;
-    p->mlp_prec = d->mlp_precision;
-    if (d->n_layers > 0)
-        for (int i = 0; i <= d->n_layers; ++i) p->dims[i] = d->layer_dims[i];
-    p->out_dim = d->n_layers > 0 ? d->layer_dims[d->n_layers] : d_feat;
-
-    // ---- kernel family and MLP placement -------------------------------------------------------
-    int max_w = 0;
-    for (int i = 1; i <= d->n_layers; ++i) max_w = std::max(max_w, d->layer_dims[i]);
-    const bool cheap_act = d->activation != MOLANN_ACT_ELU && d->activation != MOLANN_ACT_SOFTPLUS &&
-                           d->activation != MOLANN_ACT_GELU;
-    const bool small_mlp = d->n_layers > 0 && d->n_layers <= LANE_MLP_MAX_LAYERS && max_w <= LANE_MLP_MAX_WIDTH &&
-                           d_feat <= LANE_MLP_MAX_WIDTH && d->mlp_precision == MOLANN_MLP_F32 && cheap_act;
-    // feature dims 33..64 in front of such an MLP: fused too, by the plan-specialised kernel only (16 k-steps in layer 0)
-    const bool wide_in_mlp = !small_mlp && d->n_layers > 0 && d->n_layers <= LANE_MLP_MAX_LAYERS && max_w <= LANE_MLP_MAX_WIDTH &&
-                             d_feat <= 2 * LANE_MLP_MAX_WIDTH && d->mlp_precision == MOLANN_MLP_F32 && cheap_act;
-    const int cols_needed = std::max(1, small_mlp ? ceil_to(d_feat, 4) : d_feat);
-    // touched atoms -> slots in first-use order: align atoms, then the feature table's atoms
-    std::vector<int> slot_of(d->n_inp, -1), slots;
-    auto slot = [&](int atom) {
-        if (slot_of[atom] < 0) { slot_of[atom] = (int)slots.size(); slots.push_back(atom); }
-        return slot_of[atom];
-    };
-    bool align_is_prefix = true; // align atom i must be slot i (no repeated align atoms)
-    for (int i = 0; i < d->n_align; ++i) align_is_prefix = align_is_prefix && (slot(d->align_idx[i]) == i);
-    std::vector<ItemDev> items_slot(items);
-    for (auto& it : items_slot)
-        for (int i = 0; i < 4; ++i) it.idx[i] = slot(it.idx[i]);
-    p->n_slots = (int)slots.size();
-    // (plan creation is setup time: MOLANN_NO_REGS / MOLANN_NO_JIT select the other generic modes here)
-    p->regs_mode = p->n_items > 0 && p->n_items <= 64 && p->n_slots <= 16 && align_is_prefix &&
-                   getenv("MOLANN_NO_REGS") == nullptr;
-    memset(p->geom, 0, sizeof(p->geom));
-    const bool lane_tables_fit = d->n_align <= 64 && (long)d->n_inp * 768 <= 65536;
-    if (p->n_items > 0 && lane_tables_fit && cols_needed <= LANE_MAX_COLS)
-        lane_geometry(p->geom[0], 64 * d->n_inp * 12, cols_needed);
-    if (d->n_align > 0 && lane_tables_fit) lane_geometry(p->geom[1], 64 * d->n_inp * 12, 1);
-    // The plan-specialised lane kernel stages only the touched 16-byte windows of a frame, so its tile does not grow
-    // with n_inp: a plan that touches few atoms (<= 32) of a LARGE frame is a lane-per-frame plan too, as long as
-    // hipRTC is there to build it (the ahead-of-time lane kernel needs the dense tile and cannot serve it).
-    const char* nojit_env = getenv("MOLANN_NO_JIT");
-    bool jit_possible = rtc_api()->ok && !(nojit_env && nojit_env[0] == '1') && p->n_items > 0 &&
-                        p->n_items <= JIT_MAX_ITEMS && p->n_slots <= JIT_MAX_SLOTS && align_is_prefix &&
-                        cols_needed <= LANE_MAX_COLS && 3 * d->n_inp >= 4;
-    if (jit_possible) { // and its LDS geometry (compact tile + staging rows) must leave room for >= 4 waves per CU
-        JitSpec probe;
-        probe.win = compact_windows(slots, d->n_inp);
-        molann_plan::LaneGeom pg;
-        memset(&pg, 0, sizeof(pg));
-        jit_geometry(probe, pg, ((small_mlp || wide_in_mlp) && d->n_features > 0) ? d_feat : cols_needed, cols_needed);
-        jit_possible = pg.ok != 0;
-    }
-    const bool lane_by_jit_only = jit_possible && !p->geom[0].ok;
-    const bool fused_by_jit_only = jit_possible && wide_in_mlp && d->n_features > 0;
-    // the family names the kernel that serves the plan's main product (features if it has any)
-    p->family = (p->n_items > 0 ? (p->geom[0].ok || lane_by_jit_only) : p->geom[1].ok) ? 0 : 1;
-    p->fused_mlp = ((p->family == 0) && small_mlp && d->n_features > 0) || fused_by_jit_only;
-    // a head within the fused MLP's limits behind a kernel that cannot fuse it (wave per frame), or called on its own
-    // (molann_mlp_packed_f32): mlp_lane_kernel on the same weight fragments
-    p->lane_mlp = small_mlp && !(getenv("MOLANN_NO_LANE_MLP") && getenv("MOLANN_NO_LANE_MLP")[0] == '1');
-    p->jit_only = lane_by_jit_only || fused_by_jit_only;
-
-    // ---- device blob ----------------------------------------------------------------------------
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_align = carve(sizeof(int) * std::max(1, d->n_align));
-    const size_t o_ref = carve(sizeof(float) * (3 * (size_t)d->n_align + 8));
-    const size_t o_ref64 = carve(sizeof(double) * (3 * (size_t)d->n_align + 8));
-    const size_t o_items = carve(sizeof(ItemDev) * std::max<size_t>(1, items.size()));
-    const size_t o_items_slot = carve(sizeof(ItemDev) * std::max<size_t>(1, items.size()));
-    const size_t o_slots = carve(sizeof(int) * std::max<size_t>(1, slots.size()));
-    // frames_ring_kernel tables (plans the lane kernels do not serve): windows, image positions
-    std::vector<int> ring_win, ring_align_pos;
-    std::vector<ItemDev> ring_items;
-    p->ring_nd = 0;
-    if (p->family == 1 && p->n_items > 0 && align_is_prefix) {
-        const std::vector<int> win = compact_windows(slots, d->n_inp);
-        static const int buckets[] = {1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 30, 32};
-        int nd = 0;
-        for (int b : buckets)
-            if (nd == 0 && (long)b * 64 >= (long)win.size()) nd = b;
-        if (nd > 0) {
-            // dword position of the atom's x inside the image; its three dwords are contiguous there: either one
-            // window holds all of them (always so for the window clamped to the frame's end, which may overlap its
-            // predecessor), or the atom runs over the end of window k and window k + 1 starts right behind it
-            auto pos_of = [&](int atom) {
-                const int d0 = 3 * atom;
-                for (size_t k = 0; k < win.size(); ++k)
-                    if (d0 >= win[k] && d0 + 2 < win[k] + 4) return (int)(4 * k) + d0 - win[k];
-                for (size_t k = 0; k < win.size(); ++k)
-                    if (d0 >= win[k] && d0 < win[k] + 4) return (int)(4 * k) + d0 - win[k];
-                return 0;
-            };
-            for (int w : win) ring_win.push_back(4 * w);
-            for (int i = 0; i < d->n_align; ++i) ring_align_pos.push_back(pos_of(d->align_idx[i]));
-            ring_items = items;
-            for (auto& it : ring_items)
-                for (int i = 0; i < 4; ++i) it.idx[i] = pos_of(it.idx[i]);
-            p->ring_nd = nd;
-            p->ring_nwin = (int)win.size();
-        }
-    }
-    const size_t o_ring_win = carve(sizeof(int) * std::max<size_t>(1, ring_win.size()));
-    const size_t o_ring_apos = carve(sizeof(int) * std::max<size_t>(1, ring_align_pos.size()));
-    const size_t o_ring_items = carve(sizeof(ItemDev) * std::max<size_t>(1, ring_items.size()));
-    // backward of large frames without atomics: who contributes to which touched atom
-    std::vector<int> bw_atoms, bw_ptr, bw_list, bw_align;
-    if (!p->geom[0].ok && p->n_items > 0 && d->n_layers >= 0) {
-        std::vector<std::vector<int>> contrib(d->n_inp);
-        std::vector<int> al_of(d->n_inp, -1);
-        std::vector<char> touched(d->n_inp, 0);
-        for (size_t it = 0; it < items.size(); ++it)
-            for (int j = 0; j < item_atoms(items[it].type); ++j) { contrib[items[it].idx[j]].push_back((int)(4 * it + j)); touched[items[it].idx[j]] = 1; }
-        for (int i = 0; i < d->n_align; ++i) { if (al_of[d->align_idx[i]] < 0) al_of[d->align_idx[i]] = i; touched[d->align_idx[i]] = 1; }
-        bool repeated_align = false;
-        { std::vector<char> seen(d->n_inp, 0); for (int i = 0; i < d->n_align; ++i) { repeated_align = repeated_align || seen[d->align_idx[i]]; seen[d->align_idx[i]] = 1; } }
-        if (!repeated_align) {   // (an alignment set that names an atom twice keeps the atomics: the atom has two reference rows)
-            bw_ptr.push_back(0);
-            for (int a0 = 0; a0 < d->n_inp; ++a0)
-                if (touched[a0]) {
-                    bw_atoms.push_back(a0);
-                    bw_align.push_back(al_of[a0]);
-                    bw_list.insert(bw_list.end(), contrib[a0].begin(), contrib[a0].end());
-                    bw_ptr.push_back((int)bw_list.size());
-                }
-        }
-    }
-    p->bw_touched = (int)bw_atoms.size();
-    p->bw_list_len = (int)bw_list.size();
-    // values + vjp in one launch (molann_group_vjp.inc): the same lists for every alignment set, rows named twice included
-    std::vector<int> va_atoms, va_ptr, va_list;
-    if (!p->geom[0].ok && p->n_items > 0) group_vjp_tables(d->n_inp, items, d->align_idx, d->n_align, va_atoms, va_ptr, va_list);
-    p->va_touched = (int)va_atoms.size();
-    p->va_list_len = (int)va_list.size();
-    const size_t o_va_atoms = carve(sizeof(int) * std::max<size_t>(1, va_atoms.size()));
-    const size_t o_va_ptr = carve(sizeof(int) * std::max<size_t>(1, va_ptr.size()));
-    const size_t o_va_list = carve(sizeof(int) * std::max<size_t>(1, va_list.size()));
-    // second order without atomics: every atom's item slots, then its align slots, in a fixed order (molann_hvp.inc)
-    std::vector<int> hv_ptr, hv_list;
-    if (p->n_items > 0) hvp_tables(d->n_inp, items, d->align_idx, d->n_align, hv_ptr, hv_list);
-    const size_t o_hv_ptr = carve(sizeof(int) * std::max<size_t>(1, hv_ptr.size()));
-    const size_t o_hv_list = carve(sizeof(int) * std::max<size_t>(1, hv_list.size()));
-    // AlignmentLayer.forward under autograd arrives as a feature plan with ONE position item per atom, in atom order: its
-    // feature rows are the aligned frame, its backward the dense gradient of the alignment (frames_align_bwd_regs_kernel)
-    std::vector<int> align_slot;
-    p->dense_positions = false;
-    if (d->n_align > 0 && d->n_layers == 0 && (int)items.size() == d->n_inp && !p->geom[0].ok) {
-        bool dense = true, repeated = false;
-        for (int i = 0; i < d->n_inp && dense; ++i) dense = items[i].type == IT_POSITION && items[i].idx[0] == i && items[i].col == 3 * i;
-        align_slot.assign(d->n_inp, -1);
-        for (int i = 0; i < d->n_align; ++i) { repeated = repeated || align_slot[d->align_idx[i]] >= 0; align_slot[d->align_idx[i]] = i; }
-        p->dense_positions = dense && !repeated && getenv("MOLANN_NO_DENSE_ALIGN") == nullptr;
-        if (!p->dense_positions) align_slot.clear();
-    }
-    const size_t o_align_slot = carve(sizeof(int) * std::max<size_t>(1, align_slot.size()));
-    const size_t o_bw_atoms = carve(sizeof(int) * std::max<size_t>(1, bw_atoms.size()));
-    const size_t o_bw_ptr = carve(sizeof(int) * std::max<size_t>(1, bw_ptr.size()));
-    const size_t o_bw_list = carve(sizeof(int) * std::max<size_t>(1, bw_list.size()));
-    const size_t o_bw_align = carve(sizeof(int) * std::max<size_t>(1, bw_align.size()));
-
-    size_t lane_floats = 0;
-    if (p->fused_mlp || p->lane_mlp) lane_floats = (size_t)d->n_layers * (1024 + 512) + 1024;
-    const size_t o_wlane = carve(sizeof(float) * std::max<size_t>(1, lane_floats));
-    size_t mfma_bytes = 0;
-    const bool bf16 = d->mlp_precision == MOLANN_MLP_BF16;
-    const int kgran = bf16 ? 32 : 16;
-    int max_kp = 16;
-    if (d->n_layers > 0) {
-        const size_t es = bf16 ? 2 : 4;
-        for (int l = 0; l < d->n_layers; ++l) {
-            p->kp[l] = ceil_to(p->dims[l], kgran);
-            p->jp[l] = ceil_to(p->dims[l + 1], 16);
-            max_kp = std::max(max_kp, std::max(p->kp[l], p->jp[l]));
-        }
-        // the activations written by layer l (Jp columns) are read as layer l+1's Kp columns
-        for (int l = 0; l + 1 < d->n_layers; ++l) max_kp = std::max(max_kp, p->kp[l + 1]);
-        for (int l = 0; l < d->n_layers; ++l) {
-            p->moff[l] = (long)(mfma_bytes / es);
-            mfma_bytes += ((size_t)p->jp[l] * p->kp[l]) * es + (size_t)p->jp[l] * 4;
-            mfma_bytes = (mfma_bytes + 15) & ~(size_t)15;
-        }
-        // two activation buffers: [0] holds the inputs of even layers, [1] of odd layers (layer l writes what
-        // layer l+1 reads).  Row strides: 16-byte multiples, off the power of two.
-        int need[2] = {16, 16};
-        for (int l = 0; l < d->n_layers; ++l) {
-            need[l & 1] = std::max(need[l & 1], p->kp[l]);
-            if (l + 1 < d->n_layers) need[(l + 1) & 1] = std::max(need[(l + 1) & 1], std::max(p->jp[l], p->kp[l + 1]));
-        }
-        (void)max_kp;
-        for (int i = 0; i < 2; ++i) p->mlp_ld[i] = need[i] + (bf16 ? 8 : 4);
-        p->mlp_lds_per_wave = 16 * (p->mlp_ld[0] + p->mlp_ld[1]) * (int)es;
-        if (p->mlp_lds_per_wave > 163840) { delete p; return MOLANN_E_UNSUPPORTED; }
-        if (p->mlp_lds_per_wave > 65536) { // a single wave's two activation buffers exceed the default 64 KiB cap
-            hipError_t ea = bf16 ? hipFuncSetAttribute((const void*)mlp_mfma_kernel<true>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 163840)
-                                 : hipFuncSetAttribute((const void*)mlp_mfma_kernel<false>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-            if (ea != hipSuccess) { delete p; return (int)ea; }
-        }
-    }
-    const size_t o_wmfma = carve(std::max<size_t>(16, mfma_bytes));
-    // wide bf16 MLP next to a gather kernel: the chain kernel's weight stream (molann_mlp_jit.inc), when its
-    // two LDS slabs fit and at least one 16-frame block per wave fits the register file
-    ChainGeom cg;
-    memset(&cg, 0, sizeof(cg));
-    size_t chain_bytes = 0;
-    int chain_fb = 0;
-    if (d->n_layers > 0 && !p->fused_mlp) {
-        cg.nl = d->n_layers;
-        cg.bf16 = bf16 ? 1 : 0;
-        for (int i = 0; i <= d->n_layers; ++i) cg.dims[i] = p->dims[i];
-        for (int fb = 4; fb >= 1 && chain_fb == 0; --fb) // upper bound; plan creation steps down while the build spills
-            if (fb * cg.regs_per_fb() <= (chain_resident(cg) ? 256 : 512)) chain_fb = fb;     // resident: two waves per SIMD
-        if (!chain_resident(cg) && 2 * cg.slab_max() * 1024 > 163840 - 1024) chain_fb = 0;
-        if (chain_fb > 0) {
-            p->chain_stream_bytes = cg.total_frags() * 1024;
-            chain_bytes = (size_t)p->chain_stream_bytes + (size_t)cg.bias_off(cg.nl) * 4;
-        }
-    }
-    const size_t o_wchain = carve(std::max<size_t>(16, chain_bytes));
-    p->work_frames = 0;
-    size_t work_bytes = 0;
-    if (d->n_layers > 0 && d->n_features > 0 && !p->fused_mlp) {
-        // feature chunk handed from the preprocessing kernel to the MLP kernel: sized to stay
-        // resident in the 256 MiB Infinity Cache
-        long wf = (64l << 20) / ((long)d_feat * 4);
-        wf = std::max<long>(1024, std::min<long>(wf, 1l << 21)); // (narrow feature rows: few, large chunks - each costs ~6 host API calls, and a
-                                                                  //  feature launch of 512 k frames takes 37 us where one of 1 M takes 46)
-        wf &= ~63l;
-        wf = std::max<long>(512, (wf / 2) & ~63l); // per half
-        // Large frames: the feature rows are a few percent of the frame bytes, so letting them spill past the Infinity
-        // Cache costs little, while a chunk that small leaves the MLP kernel (one block per CU, 64 FB frames per block
-        // and step) a fraction of the chip: frames_ring_kernel holds every CU, the two kernels run one after the other,
-        // and C5's MLP took 3.7 us per 1000 frames in 24 576-frame chunks against 1.2 on its own.  Up to 256 MiB per half.
-        // (Round 3: for every wave-per-frame plan, not only those whose feature rows are a small part of the frame.  P2 - 166 atoms,
-        // 126 features - ran 16 chunks of 66 560 frames per 1 M: 260 frames per CU and launch, both kernels all ramp and tail,
-        // 1.64 ms; in 4 chunks 0.86 ms.)
-        if (p->family == 1)
-            wf = std::max<long>(wf, std::min<long>(1l << 18, ((256l << 20) / ((long)d_feat * 4)) & ~63l));
-        p->work_frames = wf;
-        work_bytes = 2 * (size_t)wf * d_feat * 4;
-    }
-    const size_t o_work = carve(std::max<size_t>(16, work_bytes));
-
-    hipError_t e = hipMalloc((void**)&p->blob, off);
-    if (e != hipSuccess) { delete p; return (int)e; }
-    p->d_align_idx = (int*)(p->blob + o_align);
-    p->d_ref = (float*)(p->blob + o_ref);
-    p->d_ref64 = (double*)(p->blob + o_ref64);
-    p->d_items = (ItemDev*)(p->blob + o_items);
-    p->d_items_slot = (ItemDev*)(p->blob + o_items_slot);
-    p->d_slots = (int*)(p->blob + o_slots);
-    p->d_ring_win = (int*)(p->blob + o_ring_win);
-    p->d_ring_align_pos = (int*)(p->blob + o_ring_apos);
-    p->d_ring_items = (ItemDev*)(p->blob + o_ring_items);
-    p->d_bw_atoms = (int*)(p->blob + o_bw_atoms); p->d_bw_ptr = (int*)(p->blob + o_bw_ptr);
-    p->d_bw_list = (int*)(p->blob + o_bw_list); p->d_bw_align = (int*)(p->blob + o_bw_align);
-    p->d_align_slot = (int*)(p->blob + o_align_slot);
-    p->d_va_atoms = (int*)(p->blob + o_va_atoms); p->d_va_ptr = (int*)(p->blob + o_va_ptr); p->d_va_list = (int*)(p->blob + o_va_list);
-    p->d_hv_ptr = (int*)(p->blob + o_hv_ptr); p->d_hv_list = (int*)(p->blob + o_hv_list);
-    p->d_wlane = (float*)(p->blob + o_wlane);
-    p->d_wmfma = (void*)(p->blob + o_wmfma);
-    p->d_work = (float*)(p->blob + o_work);
-    p->d_wchain = p->blob + o_wchain;
-
-    // ---- upload (synchronous: plan creation is setup time) --------------------------------------
-    if (d->n_align > 0) {
-        std::vector<float> refc(3 * (size_t)d->n_align + 8, 0.f);
-        std::vector<double> refd(3 * (size_t)d->n_align + 8, 0.);
-        // centred here whatever the caller passes (pack_ref_kernel: the alignment does not depend on it)
-        double mean[3] = {0, 0, 0}, s[4] = {0, 0, 0, 0};
-        for (int i = 0; i < d->n_align; ++i)
-            for (int c = 0; c < 3; ++c) mean[c] += d->ref_x[3 * i + c];
-        for (int c = 0; c < 3; ++c) mean[c] /= (double)d->n_align;
-        for (int i = 0; i < d->n_align; ++i) {
-            for (int c = 0; c < 3; ++c) {
-                const float r = (float)((double)d->ref_x[3 * i + c] - mean[c]);
-                refc[3 * i + c] = r;
-                refd[3 * i + c] = r;
-                s[c] += r;
-                s[3] += (double)r * r;
-            }
-        }
-        float* c = refc.data() + 3 * (size_t)d->n_align;
-        double* c64 = refd.data() + 3 * (size_t)d->n_align;
-        for (int k = 0; k < 4; ++k) { c[k] = (float)s[k]; c64[k] = s[k]; }
-        c[4] = 1.0f / (float)d->n_align;
-        c[5] = (float)d->n_align;
-        c64[4] = 1.0 / (double)d->n_align;
-        c64[5] = (double)d->n_align;
-        e = hipMemcpy(p->d_align_idx, d->align_idx, sizeof(int) * d->n_align, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_ref, refc.data(), sizeof(float) * refc.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_ref64, refd.data(), sizeof(double) * refd.size(), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && !items.empty())
-        e = hipMemcpy(p->d_items, items.data(), sizeof(ItemDev) * items.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !items.empty())
-        e = hipMemcpy(p->d_items_slot, items_slot.data(), sizeof(ItemDev) * items.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !slots.empty())
-        e = hipMemcpy(p->d_slots, slots.data(), sizeof(int) * slots.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && p->ring_nd > 0) {
-        e = hipMemcpy(p->d_ring_win, ring_win.data(), sizeof(int) * ring_win.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !ring_align_pos.empty())
-            e = hipMemcpy(p->d_ring_align_pos, ring_align_pos.data(), sizeof(int) * ring_align_pos.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_ring_items, ring_items.data(), sizeof(ItemDev) * ring_items.size(), hipMemcpyHostToDevice);
-    }
-
-    if (e == hipSuccess && p->bw_touched > 0) {
-        e = hipMemcpy(p->d_bw_atoms, bw_atoms.data(), sizeof(int) * bw_atoms.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_bw_ptr, bw_ptr.data(), sizeof(int) * bw_ptr.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !bw_list.empty()) e = hipMemcpy(p->d_bw_list, bw_list.data(), sizeof(int) * bw_list.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !align_slot.empty()) e = hipMemcpy(p->d_align_slot, align_slot.data(), sizeof(int) * align_slot.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_bw_align, bw_align.data(), sizeof(int) * bw_align.size(), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && p->va_touched > 0) {
-        e = hipMemcpy(p->d_va_atoms, va_atoms.data(), sizeof(int) * va_atoms.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_va_ptr, va_ptr.data(), sizeof(int) * va_ptr.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_va_list, va_list.data(), sizeof(int) * va_list.size(), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && !hv_ptr.empty()) {
-        e = hipMemcpy(p->d_hv_ptr, hv_ptr.data(), sizeof(int) * hv_ptr.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !hv_list.empty()) e = hipMemcpy(p->d_hv_list, hv_list.data(), sizeof(int) * hv_list.size(), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) { (void)hipFree(p->blob); delete p; return (int)e; }
-    snprintf(p->last_info, sizeof(p->last_info), "(no launch yet)");
-    if (p->work_frames > 0) {
-        e = hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking);
-        for (int h = 0; h < 2 && e == hipSuccess; ++h) {
-            e = hipEventCreateWithFlags(&p->ev_feat[h], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_mlp[h], hipEventDisableTiming);
-            if (e == hipSuccess && h == 0) e = hipEventCreateWithFlags(&p->ev_done, hipEventDisableTiming);
-        }
-        if (e != hipSuccess) { (void)hipFree(p->blob); delete p; return (int)e; }
-    }
-    // ---- plan-specialised lane kernel --------------------------------------------------------------
-    snprintf(p->jit_note, sizeof(p->jit_note), "jit: not applicable");
-    const char* nojit = nojit_env;
-    if (jit_possible) {
-        JitSpec j;
-        j.n_inp = d->n_inp; j.n_align = d->n_align; j.act = d->activation; j.d_feat = d_feat;
-        j.n_layers = p->fused_mlp ? d->n_layers : 0;
-        j.out_cols = p->fused_mlp ? p->out_dim : d_feat;
-        j.slots = slots; j.items = items_slot;
-        // compact tile: only the 16-byte windows of a frame that hold a touched atom go to LDS, so more waves fit
-        j.win = compact_windows(slots, d->n_inp);
-        jit_geometry(j, p->jit_geom, p->fused_mlp ? d_feat : cols_needed, cols_needed);
-        if (p->fused_mlp) j.dims.assign(p->dims, p->dims + d->n_layers + 1);
-        p->spec = new (std::nothrow) JitSpecBox();
-        if (p->spec) {
-            p->spec->j = j;
-            for (int l = 0; l < j.n_layers; ++l) { p->spec->kp.push_back(p->kp[l]); p->spec->jp.push_back(p->jp[l]); p->spec->woff.push_back(p->moff[l]); }
-            p->n_grad_params = 0;
-            for (int l = 0; l < j.n_layers; ++l) p->n_grad_params += p->dims[l + 1] * p->dims[l] + p->dims[l + 1];
-        }
-        int rc = -1;
-        const bool frame_ok = p->jit_geom.ok && 3 * d->n_inp >= 4;
-        if (frame_ok) {
-            std::vector<char> code;
-            std::string log;
-            // no SLP vectorisation: hipcc otherwise packs a fifth of this straight-line fp32 code into v_pk_* pairs, which
-            // buys ~1.2x on those operations at two waves per SIMD and pays for it with ~130 register moves per tile and 44
-            // more registers (C3: 166 -> 122 VGPRs, 74 -> 70 us; tools/ab_flags.sh)
-            rc = jit_compile(jit_source(j), code, log, "-fno-slp-vectorize");
-            hipModule_t mod = nullptr;
-            hipFunction_t fn = nullptr;
-            bool loaded = rc == 0 && hipModuleLoadData(&mod, code.data()) == hipSuccess && hipModuleGetFunction(&fn, mod, "molann_lane_jit") == hipSuccess;
-            int scratch = 0;
-            if (loaded && j.ncons > 10 && hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, fn) == hipSuccess && scratch > 0) {
-                // Three or four layers of 32 units: the weight fragments do not fit the 128 registers of four waves per SIMD and the
-                // build spills.  Ten consumers (three waves per SIMD, 168 registers) serve the stream as well as fourteen.
-                JitSpec j3 = j;
-                molann_plan::LaneGeom g3;
-                memset(&g3, 0, sizeof(g3));
-                jit_geometry(j3, g3, p->fused_mlp ? d_feat : cols_needed, cols_needed, 10);
-                std::vector<char> code3;
-                hipModule_t mod3 = nullptr;
-                hipFunction_t fn3 = nullptr;
-                int scratch3 = 0;
-                if (g3.ok && jit_compile(jit_source(j3), code3, log, "-fno-slp-vectorize") == 0 && hipModuleLoadData(&mod3, code3.data()) == hipSuccess &&
-                    hipModuleGetFunction(&fn3, mod3, "molann_lane_jit") == hipSuccess &&
-                    hipFuncGetAttribute(&scratch3, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, fn3) == hipSuccess && scratch3 < scratch) {
-                    (void)hipModuleUnload(mod);
-                    mod = mod3; fn = fn3; code.swap(code3);
-                    j = j3; p->jit_geom = g3;
-                    if (p->spec) p->spec->j = j;
-                } else if (mod3) {
-                    (void)hipModuleUnload(mod3);
-                }
-            }
-            if (!loaded) {
-                if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann jit failed rc=%d\n%s\n", rc, log.c_str());
-                if (mod) (void)hipModuleUnload(mod);
-            } else {
-                p->jit_mod = mod; p->jit_fn = fn; p->jit_nl = j.n_layers; p->jit_waves = 2;
-                p->jit_ncons = j.ncons; p->jit_nload = j.nload; p->jit_nslot = j.nslot; p->jit_bpc = j.bpc; p->jit_lds_block = j.lds_block;
-                snprintf(p->jit_note, sizeof(p->jit_note), "jit: specialised kernel, %d+1 waves per block, %zu bytes", j.ncons, code.size());
-            }
-        }
-        if (!p->jit_fn) snprintf(p->jit_note, sizeof(p->jit_note), "jit: unavailable (rc=%d), generic kernel", rc);
-    }
-    if (p->jit_only && !p->jit_fn) { // hipRTC is present but the build failed: no other lane kernel for this plan
-        if (p->fused_mlp) { // its MLP was planned into that kernel: nothing to fall back to
-            molann_plan_destroy(p);
-            return MOLANN_E_UNSUPPORTED;
-        }
-        p->jit_only = false;
-        if (!p->geom[0].ok) p->family = 1; // features from the wave-per-frame kernel
-    }
-    // ---- AlignmentLayer.forward through the specialised kernel: the aligned frame is the feature row of one position item per
-    // atom, so molann_align_f32 is the loader / consumer kernel too (built at its first call).  Small frames only.
-    if (d->n_align > 0 && d->n_inp <= JIT_MAX_SLOTS && 3 * d->n_inp <= LANE_MAX_COLS && 3 * d->n_inp >= 4 && rtc_api()->ok &&
-        !(nojit && nojit[0] == '1')) {
-        JitSpec j;
-        std::vector<int> seen(d->n_inp, 0);
-        bool distinct = true;
-        for (int i = 0; i < d->n_align; ++i) { distinct = distinct && !seen[d->align_idx[i]]; seen[d->align_idx[i]] = 1; j.slots.push_back(d->align_idx[i]); }
-        for (int a = 0; a < d->n_inp; ++a) if (!seen[a]) j.slots.push_back(a);
-        if (distinct) {
-            for (int u = 0; u < d->n_inp; ++u) { ItemDev it = {IT_POSITION, 3 * j.slots[u], {u, u, u, u}, {0, 0}}; j.items.push_back(it); }
-            j.n_inp = d->n_inp; j.n_align = d->n_align; j.act = 0; j.d_feat = 3 * d->n_inp; j.n_layers = 0; j.out_cols = 3 * d->n_inp;
-            j.win = compact_windows(j.slots, d->n_inp);
-            molann_plan::LaneGeom g;
-            memset(&g, 0, sizeof(g));
-            jit_geometry(j, g, j.d_feat, j.d_feat);
-            if (g.ok && (p->align_spec = new (std::nothrow) JitSpecBox())) p->align_spec->j = j;
-        }
-    }
-    // ---- a small head that no lane kernel fuses (wave-per-frame features): its description for the MLP's backward kernel
-    if (p->lane_mlp && !p->fused_mlp && d->n_features > 0 && rtc_api()->ok && (p->mlp_spec = new (std::nothrow) JitSpecBox())) {
-        JitSpec& mj = p->mlp_spec->j;
-        mj.n_layers = d->n_layers; mj.act = d->activation; mj.d_feat = d_feat;
-        mj.dims.assign(p->dims, p->dims + d->n_layers + 1);
-        p->n_grad_params = 0;
-        for (int l = 0; l < d->n_layers; ++l) {
-            p->mlp_spec->kp.push_back(p->kp[l]); p->mlp_spec->jp.push_back(p->jp[l]); p->mlp_spec->woff.push_back(p->moff[l]);
-            p->n_grad_params += p->dims[l + 1] * p->dims[l] + p->dims[l + 1];
-        }
-    }
-    // ---- plan-specialised wide bf16 MLP ----------------------------------------------------------------
-    snprintf(p->chain_note, sizeof(p->chain_note), "chain: not applicable");
-    if (chain_fb > 0 && !(nojit && nojit[0] == '1') && !p->lane_mlp) {
-        // most frames per wave (A-fragment reuse) that the register file holds without scratch
-        int rc = -1;
-        for (int fb = chain_fb; fb >= 1 && !p->chain_fn; --fb) {
-            std::vector<char> code;
-            std::string log;
-            rc = jit_compile(jit_source_chain(cg, p->act, fb), code, log);
-            hipModule_t mod = nullptr;
-            hipFunction_t fn = nullptr;
-            if (rc != 0 || hipModuleLoadData(&mod, code.data()) != hipSuccess ||
-                hipModuleGetFunction(&fn, mod, "molann_mlp_chain") != hipSuccess) {
-                if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann chain jit failed rc=%d\n%s\n", rc, log.c_str());
-                if (mod) (void)hipModuleUnload(mod);
-                break;
-            }
-            int scratch = 0;
-            (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, fn);
-            if (scratch > 0 && fb > 1) { (void)hipModuleUnload(mod); continue; }
-            p->chain_mod = mod; p->chain_fn = fn; p->chain_fb = fb; p->chain_waves = chain_waves(cg); p->chain_nslab = chain_nslab(cg);
-            snprintf(p->chain_note, sizeof(p->chain_note), "chain: specialised kernel, FB=%d, %zu bytes", fb, code.size());
-        }
-        if (!p->chain_fn) snprintf(p->chain_note, sizeof(p->chain_note), "chain: unavailable (rc=%d), mlp_mfma_kernel", rc);
-    }
-    // ---- backward of a wide fp32 head whose chain stream is resident (molann_chain_bwd.inc), built at its first use: where it
-    // serves the head, the parameter-gradient buffer has the head's layout (molann_mlp_backward_f32)
-    if (chain_fb > 0 && chain_resident(cg) && !bf16 && !p->fused_mlp && !p->lane_mlp && rtc_api()->ok && !(nojit && nojit[0] == '1')) {
-        const int act = d->activation;
-        std::vector<int> kp(p->kp, p->kp + d->n_layers), jp(p->jp, p->jp + d->n_layers);
-        if (act == 0 || act == 1 || act == 2 || act == 3 || act == 5 || act == 7) p->cbwd_waves = chain_bwd_waves(kp, jp);
-        if (p->cbwd_waves > 0) {
-            p->n_grad_params = 0;
-            for (int l = 0; l < d->n_layers; ++l) p->n_grad_params += p->dims[l + 1] * p->dims[l] + p->dims[l + 1];
-        }
-    }
-    // ---- the whole forward of a WIDE head in one lane kernel (round 3) ----------------------------------------------------
-    // Hidden widths 33 .. ~128 behind a lane-per-frame preprocessing: features kernel + chain MLP kernel cost a launch, a
-    // round trip of the features through the workspace and - the feature kernel holds every CU - no overlap.  Where the
-    // chain's weight stream fits LDS beside a (shorter) ring, the specialised lane kernel runs the chain's arithmetic as its
-    // MLP stage (molann_lane_jit.inc: WIDE_MLP).  Eight consumers + two loaders where the ring still has four slots.
-    if (jit_possible && p->family == 0 && !p->fused_mlp && d->n_layers > 0 && d->n_features > 0 && !bf16 && chain_fb > 0 && chain_resident(cg) &&
-        p->chain_stream_bytes <= 112 * 1024 && d_feat <= LANE_MAX_COLS && getenv("MOLANN_NO_WIDE_FUSED") == nullptr) {
-        JitSpec j;
-        j.n_inp = d->n_inp; j.n_align = d->n_align; j.act = d->activation; j.d_feat = d_feat;
-        j.n_layers = d->n_layers; j.out_cols = p->out_dim;
-        j.slots = slots; j.items = items_slot;
-        j.win = compact_windows(slots, d->n_inp);
-        j.dims.assign(p->dims, p->dims + d->n_layers + 1);
-        j.wide_mlp = true; j.img_bytes = (int)p->chain_stream_bytes;
-        int first = 8;     // (measured, [6,64,64,8] at 1 M frames: 188 / 175 / 176 / 182 us with 6 / 8 / 10 / 14 consumers)
-        if (const char* e = diag_env("MOLANN_DEBUG_WIDE_CONS")) first = std::max(1, std::min(14, atoi(e)));
-        for (int wide_cons : {first, 6}) {       // six consumers + two loaders = two waves per SIMD: 256 registers for the wider heads
-            if (p->wide_fn) break;
-            JitSpec jw = j;
-            molann_plan::LaneGeom wg;
-            memset(&wg, 0, sizeof(wg));
-            jit_geometry(jw, wg, d_feat, cols_needed, wide_cons);
-            if (!(wg.ok && jw.nslot >= 4)) continue;
-            if (wide_cons == 6 && jw.ncons + jw.nload > 8) continue;
-            std::vector<char> code;
-            std::string log;
-            hipModule_t mod = nullptr;
-            hipFunction_t fn = nullptr;
-            int scratch = 1;
-            if (jit_compile(jit_source(jw), code, log, "-fno-slp-vectorize") == 0 && hipModuleLoadData(&mod, code.data()) == hipSuccess &&
-                hipModuleGetFunction(&fn, mod, "molann_lane_jit") == hipSuccess &&
-                hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, fn) == hipSuccess && scratch == 0) {
-                p->wide_mod = mod; p->wide_fn = fn;
-                p->wide_ncons = jw.ncons; p->wide_nload = jw.nload; p->wide_nslot = jw.nslot; p->wide_bpc = jw.bpc; p->wide_lds_block = jw.lds_block;
-            } else {
-                if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann wide fused forward with %d consumers not used (scratch=%d)\n%s\n", jw.ncons, scratch, log.c_str());
-                if (mod) (void)hipModuleUnload(mod);
-            }
-        }
-    }
-    *out_plan = p;
-    return MOLANN_OK;
-}
-
-int molann_plan_destroy(molann_plan* p) {
-    if (!p) return MOLANN_OK;
-    {   // kernels of this plan may still be running or queued (`y = model(x); del model`): its code objects and device
-        // memory go only when the device has drained.  Destroying a plan is setup-time work, like creating one.
-        int cur = -1;
-        const bool sw = hipGetDevice(&cur) == hipSuccess && cur != p->device && hipSetDevice(p->device) == hipSuccess;
-        (void)hipDeviceSynchronize();
-        if (sw) (void)hipSetDevice(cur);
-    }
-    if (p->jit_mod) (void)hipModuleUnload(p->jit_mod);
-    if (p->bwd_mod) (void)hipModuleUnload(p->bwd_mod);
-    if (p->mbwd_mod) (void)hipModuleUnload(p->mbwd_mod);
-    if (p->cbwd_mod) (void)hipModuleUnload(p->cbwd_mod);
-    if (p->rbwd_mod) (void)hipModuleUnload(p->rbwd_mod);
-    if (p->vjp_mod) (void)hipModuleUnload(p->vjp_mod);
-    if (p->gvjp_mod) (void)hipModuleUnload(p->gvjp_mod);
-    if (p->wide_mod) (void)hipModuleUnload(p->wide_mod);
-    if (p->feat_mod) (void)hipModuleUnload(p->feat_mod);
-    if (p->train_mod) (void)hipModuleUnload(p->train_mod);
-    if (p->align_mod) (void)hipModuleUnload(p->align_mod);
-    delete p->align_spec;
-    delete p->mlp_spec;
-    if (p->d_bwork) (void)hipFree(p->d_bwork);
-    if (p->d_gpart) (void)hipFree(p->d_gpart);
-    if (p->ev_bwork) (void)hipEventDestroy(p->ev_bwork);
-    if (p->chain_mod) (void)hipModuleUnload(p->chain_mod);
-    delete p->spec;
-    if (p->side) {
-        (void)hipStreamSynchronize(p->side);
-        for (int h = 0; h < 2; ++h) { (void)hipEventDestroy(p->ev_feat[h]); (void)hipEventDestroy(p->ev_mlp[h]); }
-        (void)hipEventDestroy(p->ev_done);
-        (void)hipStreamDestroy(p->side);
-    }
-    delete p->launch_mu;
-    delete p->jit_mu;
-    hipError_t e = hipFree(p->blob);
-    delete p;
-    return (int)e;
-}
-
 int molann_plan_feature_dim(const molann_plan* p) { return p ? p->d_feat : MOLANN_E_NULL; }
 int molann_plan_out_dim(const molann_plan* p) { return p ? p->out_dim : MOLANN_E_NULL; }
 int molann_plan_kernel_family(const molann_plan* p) { return p ? p->family : MOLANN_E_NULL; }
@@ -664,11 +74,7 @@ int molann_plan_update_mlp(molann_plan* p, const float* const* W, const float* c
     // the MFMA copy serves molann_mlp_packed_f32 and the unfused forward
     hipLaunchKernelGGL(pack_mfma_kernel, dim3(64, p->n_layers), dim3(256), 0, (hipStream_t)stream, p->d_wmfma, a);
     if (p->chain_fn || p->wide_fn) {
-        ChainGeom g;
-        memset(&g, 0, sizeof(g));
-        g.nl = p->n_layers;
-        g.bf16 = p->mlp_prec == MOLANN_MLP_BF16 ? 1 : 0;
-        for (int i = 0; i <= p->n_layers; ++i) g.dims[i] = p->dims[i];
+        const ChainGeom g = chain_geom(p->dims, p->n_layers, p->mlp_prec == MOLANN_MLP_BF16);
         ChainPackArgs c;
         memset(&c, 0, sizeof(c));
         c.n_layers = g.nl; c.npair = g.npair(); c.bf16 = g.bf16; c.stream_bytes = p->chain_stream_bytes;
@@ -705,14 +111,10 @@ int molann_align_f32(const molann_plan* cp, const float* x, int64_t n, float* ou
         if (p->align_state == 0) {
             std::lock_guard<std::mutex> lock(*p->jit_mu);
             if (p->align_state == 0) {
-                std::vector<char> code;
-                std::string log;
-                int st = -1;
-                if (jit_compile(jit_source(p->align_spec->j), code, log, "-fno-slp-vectorize") == 0 && hipModuleLoadData(&p->align_mod, code.data()) == hipSuccess &&
-                    hipModuleGetFunction(&p->align_fn, p->align_mod, "molann_lane_jit") == hipSuccess)
-                    st = 1;
-                else if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann alignment jit failed\n%s\n", log.c_str());
-                p->align_state = st;
+                BuiltKernel k;
+                const bool built = build_kernel(jit_source(p->align_spec->j), "molann_lane_jit", "-fno-slp-vectorize", "alignment jit", k);
+                p->align_mod = k.mod; p->align_fn = k.fn;
+                p->align_state = built ? 1 : -1;
             }
         }
         if (p->align_state == 1) {
@@ -933,13 +335,11 @@ int molann_plan_supports_backward(const molann_plan* p) {
     if (!p->geom[0].ok) { // large frames: the features (frames_wave_bwd_kernel), and a head within the fused MLP's limits behind them
         if (p->n_items <= 0) return 0;
         if (p->n_layers == 0) return 1;
-        const int act = p->act;
-        return (p->mlp_spec && p->mbwd_state >= 0 && rtc_api()->ok && (act == 0 || act == 1 || act == 2 || act == 3 || act == 5 || act == 7)) ? 1 : 0;
+        return (p->mlp_spec && p->mbwd_state >= 0 && rtc_api()->ok && act_served(p->act)) ? 1 : 0;
     }
     if (!p->spec || p->n_items <= 0 || p->bwd_state < 0 || !rtc_api()->ok) return 0;
     if (p->n_layers > 0 && (!p->fused_mlp || p->d_feat > LANE_MLP_MAX_WIDTH || p->mbwd_state < 0)) return 0;
-    const int act = p->act;
-    if (p->n_layers > 0 && !(act == 0 || act == 1 || act == 2 || act == 3 || act == 5 || act == 7)) return 0;
+    if (p->n_layers > 0 && !act_served(p->act)) return 0;
     return 1;
 }
 
@@ -974,20 +374,11 @@ int ensure_mlp_bwd(molann_plan* p) {
     if (p->mbwd_state == 0 || !p->d_gpart) {
         std::lock_guard<std::mutex> lock(*p->jit_mu);
         if (p->mbwd_state == 0) {
-            const int rows = mlp_bwd_rows(mlp_box(p)->j.dims, p->act);
-            const int wpb = (int)std::min<long>(8, (163840 - 64) / ((long)rows * 68 * 4));
-            std::vector<char> code;
-            std::string log;
-            int rc = -1;
-            if (wpb >= 1) rc = jit_compile(jit_source_mlp_bwd(*mlp_box(p), wpb), code, log);
-            if (rc == 0 && hipModuleLoadData(&p->mbwd_mod, code.data()) == hipSuccess &&
-                hipModuleGetFunction(&p->mbwd_fn, p->mbwd_mod, "molann_mlp_bwd") == hipSuccess) {
-                p->mbwd_wpb = wpb;
-                p->mbwd_state = 1;
-            } else {
-                p->mbwd_state = -1;
-                if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann mlp backward jit failed rc=%d\n%s\n", rc, log.c_str());
-            }
+            const int wpb = mlp_bwd_wpb(mlp_box(p)->j.dims, p->act);
+            BuiltKernel k;
+            const bool built = wpb >= 1 && build_kernel(jit_source_mlp_bwd(*mlp_box(p), wpb), "molann_mlp_bwd", nullptr, "mlp backward jit", k);
+            p->mbwd_mod = k.mod; p->mbwd_fn = k.fn; p->mbwd_wpb = wpb;
+            p->mbwd_state = built ? 1 : -1;
         }
         if (p->mbwd_state == 1 && !p->d_gpart) {
             { const int er = ensure_bwd_event(p); if (er != MOLANN_OK) return er; }
@@ -1002,19 +393,13 @@ int ensure_chain_bwd(molann_plan* p) {
     if (p->cbwd_state == 0 || !p->d_gpart) {
         std::lock_guard<std::mutex> lock(*p->jit_mu);
         if (p->cbwd_state == 0) {
-            const int nl = p->n_layers;
-            std::vector<int> dims(p->dims, p->dims + nl + 1), kp(p->kp, p->kp + nl), jp(p->jp, p->jp + nl);
-            std::vector<long> woff(p->moff, p->moff + nl);
-            std::vector<char> code;
-            std::string log;
-            const int rc = jit_compile(jit_source_chain_bwd(dims, kp, jp, woff, p->act, p->cbwd_waves), code, log);
-            if (rc == 0 && hipModuleLoadData(&p->cbwd_mod, code.data()) == hipSuccess &&
-                hipModuleGetFunction(&p->cbwd_fn, p->cbwd_mod, "molann_chain_bwd") == hipSuccess) {
-                p->cbwd_state = 1;
-            } else {
-                p->cbwd_state = -1;
-                if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann chain backward jit failed rc=%d\n%s\n", rc, log.c_str());
-            }
+            JitSpecBox b;      // (the head's sizes and the layout of its fp32 weight copy)
+            set_layout(b, p->kp, p->jp, p->moff, p->n_layers);
+            BuiltKernel k;
+            const bool built = build_kernel(jit_source_chain_bwd(std::vector<int>(p->dims, p->dims + p->n_layers + 1), b.kp, b.jp, b.woff, p->act, p->cbwd_waves),
+                                            "molann_chain_bwd", nullptr, "chain backward jit", k);
+            p->cbwd_mod = k.mod; p->cbwd_fn = k.fn;
+            p->cbwd_state = built ? 1 : -1;
         }
         if (p->cbwd_state == 1 && !p->d_gpart) {
             { const int er = ensure_bwd_event(p); if (er != MOLANN_OK) return er; }
@@ -1025,23 +410,17 @@ int ensure_chain_bwd(molann_plan* p) {
 }
 
 int ensure_features_bwd(molann_plan* p, molann_plan::LaneGeom& g) {
-    lane_geometry(g, 64 * p->n_inp * 12, 1); // the dense frame tile (reused for the gradient rows)
+    features_bwd_geometry(p->n_inp, g);
     if (!g.ok) return MOLANN_E_UNSUPPORTED;
     if (p->bwd_state == 0) {
         std::lock_guard<std::mutex> lock(*p->jit_mu);
         if (p->bwd_state == 0) {
-            std::vector<char> code;
-            std::string log;
             JitSpecBox b = *p->spec;
             b.j.wpb = g.wpb;
-            const int rc = jit_compile(jit_source_bwd(b, g.lds_per_wave), code, log);
-            if (rc == 0 && hipModuleLoadData(&p->bwd_mod, code.data()) == hipSuccess &&
-                hipModuleGetFunction(&p->bwd_fn, p->bwd_mod, "molann_lane_bwd") == hipSuccess) {
-                p->bwd_state = 1;
-            } else {
-                p->bwd_state = -1;
-                if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann backward jit failed rc=%d\n%s\n", rc, log.c_str());
-            }
+            BuiltKernel k;
+            const bool built = build_kernel(jit_source_bwd(b, g.lds_per_wave), "molann_lane_bwd", nullptr, "backward jit", k);
+            p->bwd_mod = k.mod; p->bwd_fn = k.fn;
+            p->bwd_state = built ? 1 : -1;
         }
     }
     return p->bwd_state == 1 ? MOLANN_OK : MOLANN_E_UNSUPPORTED;
@@ -1061,21 +440,16 @@ int ensure_ring_bwd(molann_plan* p) {
                 // no scratch, against 2564 + 16 spilled registers with it); the default for the plans that spill without it.
                 const std::string src = jit_source_bwd_ring(b);
                 for (int attempt = 0; attempt < 2 && st != 1; ++attempt) {
-                    std::vector<char> code;
-                    std::string log;
-                    const int rc = jit_compile(src, code, log, attempt == 0 ? "-fno-slp-vectorize" : nullptr);
-                    int scratch = -1;
-                    hipModule_t mod = nullptr;
-                    hipFunction_t fn = nullptr;
-                    if (rc == 0 && hipModuleLoadData(&mod, code.data()) == hipSuccess && hipModuleGetFunction(&fn, mod, "molann_bwd_ring") == hipSuccess &&
-                        hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, fn) == hipSuccess && scratch == 0) {
-                        p->rbwd_mod = mod; p->rbwd_fn = fn;
-                        p->rbwd_ncons = b.j.ncons; p->rbwd_nload = b.j.nload; p->rbwd_nslot = b.j.nslot; p->rbwd_lds = b.j.lds_block;
-                        st = 1;
-                    } else {
-                        if (mod) (void)hipModuleUnload(mod);
-                        if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann one-pass backward, build %d not used (rc=%d, scratch=%d)\n%s\n", attempt, rc, scratch, log.c_str());
+                    BuiltKernel k;
+                    if (!build_kernel(src, "molann_bwd_ring", attempt == 0 ? "-fno-slp-vectorize" : nullptr, "one-pass backward", k)) continue;
+                    if (k.scratch != 0) {
+                        if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann one-pass backward, build %d not used (scratch=%d)\n", attempt, k.scratch);
+                        k.unload();
+                        continue;
                     }
+                    p->rbwd_mod = k.mod; p->rbwd_fn = k.fn;
+                    p->rbwd_ncons = b.j.ncons; p->rbwd_nload = b.j.nload; p->rbwd_nslot = b.j.nslot; p->rbwd_lds = b.j.lds_block;
+                    st = 1;
                 }
             }
             p->rbwd_state = st;
@@ -1375,18 +749,10 @@ int ensure_ring_vjp(molann_plan* p) {
                 b.j.with_values = true;
                 const std::string src = jit_source_bwd_ring(b);
                 for (int attempt = 0; attempt < 2 && st != 1; ++attempt) {   // (scratch is tolerated here: a latency path, not a throughput path)
-                    std::vector<char> code;
-                    std::string log;
-                    hipModule_t mod = nullptr;
-                    hipFunction_t fn = nullptr;
-                    if (jit_compile(src, code, log, attempt == 0 ? "-fno-slp-vectorize" : nullptr) == 0 && hipModuleLoadData(&mod, code.data()) == hipSuccess &&
-                        hipModuleGetFunction(&fn, mod, "molann_bwd_ring") == hipSuccess) {
-                        p->vjp_mod = mod; p->vjp_fn = fn;
-                        st = 1;
-                    } else {
-                        if (mod) (void)hipModuleUnload(mod);
-                        if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann value + vjp build %d failed\n%s\n", attempt, log.c_str());
-                    }
+                    BuiltKernel k;
+                    if (!build_kernel(src, "molann_bwd_ring", attempt == 0 ? "-fno-slp-vectorize" : nullptr, "value + vjp build", k)) continue;
+                    p->vjp_mod = k.mod; p->vjp_fn = k.fn;
+                    st = 1;
                 }
             }
             p->vjp_state = st;
@@ -1401,12 +767,7 @@ int ensure_ring_vjp(molann_plan* p) {
 // tables do not fit the LDS at B >= 2 or hipRTC is missing.
 bool group_vjp_serves(const molann_plan* p) {
     if (p->geom[0].ok || p->n_items <= 0 || p->va_touched <= 0 || !rtc_api()->ok) return false;
-    if (p->n_layers == 0) return true;
-    const int act = p->act;
-    if (p->mlp_prec != MOLANN_MLP_F32 || p->n_layers > LANE_MLP_MAX_LAYERS || p->d_feat > LANE_MLP_MAX_WIDTH) return false;
-    for (int l = 1; l <= p->n_layers; ++l)
-        if (p->dims[l] > LANE_MLP_MAX_WIDTH) return false;
-    return act == 0 || act == 1 || act == 2 || act == 3 || act == 5 || act == 7;
+    return p->n_layers == 0 || head_is_small(p->dims, p->n_layers, p->d_feat, p->mlp_prec, p->act);
 }
 
 int ensure_group_vjp(molann_plan* p) {
@@ -1415,33 +776,23 @@ int ensure_group_vjp(molann_plan* p) {
         std::lock_guard<std::mutex> lock(*p->jit_mu);
         if (p->gvjp_state == 0) {
             int st = -1;
-            const int nl = p->n_layers;
-            std::vector<int> dims, kp, jp;
-            std::vector<long> woff;
-            if (nl > 0) {
-                dims.assign(p->dims, p->dims + nl + 1); kp.assign(p->kp, p->kp + nl); jp.assign(p->jp, p->jp + nl); woff.assign(p->moff, p->moff + nl);
-            }
+            std::vector<int> dims;
+            JitSpecBox b;
+            if (p->n_layers > 0) dims.assign(p->dims, p->dims + p->n_layers + 1);
+            set_layout(b, p->kp, p->jp, p->moff, p->n_layers);
             GroupVjpGeom g;
-            if (group_vjp_geometry(dims, p->act, p->d_feat, p->n_align, p->n_items, p->va_touched, p->va_list_len, g)) {
-                std::vector<char> code;
-                std::string log;
-                hipModule_t mod = nullptr;
-                hipFunction_t fn = nullptr;
-                const int rc = jit_compile(jit_source_group_vjp(dims, kp, jp, woff, p->act, p->d_feat, p->n_inp, p->n_align, p->n_items, p->va_touched,
-                                                                p->va_list_len, g), code, log);
-                if (rc == 0 && hipModuleLoadData(&mod, code.data()) == hipSuccess && hipModuleGetFunction(&fn, mod, "molann_group_vjp") == hipSuccess) {
-                    // blocks per CU at the launch's block size: all WPB waves (batches of at most one tile per CU), or half of them
-                    const int waves = g.wpb > 1 ? g.wpb / 2 : 1;
-                    int occ = 0;
-                    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64 * waves, 0) != hipSuccess || occ < 1)
-                        occ = std::max(1, std::min(163840 / g.lds, 32 / waves));
-                    p->gvjp_mod = mod; p->gvjp_fn = fn;
-                    p->gvjp_b = g.b; p->gvjp_wpb = g.wpb; p->gvjp_lds = g.lds; p->gvjp_bpc = occ;
-                    st = 1;
-                } else {
-                    if (mod) (void)hipModuleUnload(mod);
-                    if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann group value + vjp build failed rc=%d\n%s\n", rc, log.c_str());
-                }
+            BuiltKernel k;
+            if (group_vjp_geometry(dims, p->act, p->d_feat, p->n_align, p->n_items, p->va_touched, p->va_list_len, g) &&
+                build_kernel(jit_source_group_vjp(dims, b.kp, b.jp, b.woff, p->act, p->d_feat, p->n_inp, p->n_align, p->n_items, p->va_touched, p->va_list_len, g),
+                             "molann_group_vjp", nullptr, "group value + vjp build", k)) {
+                // blocks per CU at the launch's block size: all WPB waves (batches of at most one tile per CU), or half of them
+                const int waves = g.wpb > 1 ? g.wpb / 2 : 1;
+                int occ = 0;
+                if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.fn, 64 * waves, 0) != hipSuccess || occ < 1)
+                    occ = std::max(1, std::min(163840 / g.lds, 32 / waves));
+                p->gvjp_mod = k.mod; p->gvjp_fn = k.fn;
+                p->gvjp_b = g.b; p->gvjp_wpb = g.wpb; p->gvjp_lds = g.lds; p->gvjp_bpc = occ;
+                st = 1;
             }
             p->gvjp_state = st;
         }
@@ -1573,193 +924,96 @@ int molann_mlp_backward_f32(molann_plan* p, const float* f, const float* grad_ou
     return launch_mlp_bwd(p, f, grad_out, (long)n, grad_f, grad_params, (hipStream_t)stream);
 }
 
-// diagnostic / test hook: generate (and optionally compile, needs no GPU) the plan-specialised kernel
-// source for a description.  Returns the source length, or a negative MOLANN_E_* / positive hiprtcResult.
-int molann_debug_jit(const molann_plan_desc* d, int do_compile, char* buf, int cap) {
-    const int v = validate_desc(d);
-    if (v != MOLANN_OK) return v;
-    if (do_compile & 512) { // values + vjp in one launch for frames the lane kernels do not take (molann_group_vjp.inc), as the plan would build it
-        std::vector<ItemDev> items;
-        const int d_feat = expand_items(d, items);
-        if (items.empty()) return MOLANN_E_UNSUPPORTED;
-        std::vector<int> dims, kp, jp;
-        std::vector<long> woff;
-        if (d->n_layers > 0) {   // the heads the plan's mlp_spec describes (the fused MLP's limits), with a served activation
-            const int act = d->activation;
-            if (d->mlp_precision != MOLANN_MLP_F32 || d->n_layers > LANE_MLP_MAX_LAYERS || d_feat > LANE_MLP_MAX_WIDTH) return MOLANN_E_UNSUPPORTED;
-            if (!(act == 0 || act == 1 || act == 2 || act == 3 || act == 5 || act == 7)) return MOLANN_E_UNSUPPORTED;
-            dims.assign(d->layer_dims, d->layer_dims + d->n_layers + 1);
-            for (int v : dims) if (v > LANE_MLP_MAX_WIDTH) return MOLANN_E_UNSUPPORTED;
-            long off = 0;
-            for (int l = 0; l < d->n_layers; ++l) {   // the plan's fp32 MFMA copy: Wp[Jp][Kp] then bias[Jp], 16-byte aligned
-                kp.push_back(ceil_to(dims[l], 16)); jp.push_back(ceil_to(dims[l + 1], 16)); woff.push_back(off);
-                off += (long)jp.back() * kp.back() + jp.back();
-                off = (off + 3) & ~3l;
-            }
-        }
-        std::vector<int> atoms, ptr, list;
-        group_vjp_tables(d->n_inp, items, d->align_idx, d->n_align, atoms, ptr, list);
-        GroupVjpGeom g;
-        if (!group_vjp_geometry(dims, d->activation, d_feat, d->n_align, (int)items.size(), (int)atoms.size(), (int)list.size(), g)) return MOLANN_E_UNSUPPORTED;
-        const std::string src = jit_source_group_vjp(dims, kp, jp, woff, d->activation, d_feat, d->n_inp, d->n_align, (int)items.size(), (int)atoms.size(),
-                                                     (int)list.size(), g);
-        if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", src.c_str());
-        if (do_compile & 1) {
-            std::vector<char> code;
-            std::string log;
-            const int rc = jit_compile(src, code, log);
-            if (rc != 0) {
-                if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", log.c_str());
-                return rc > 0 ? rc : MOLANN_E_UNSUPPORTED;
-            }
-        }
-        return (int)src.size();
-    }
-    if (do_compile & 256) { // the backward of a wide fp32 head (molann_chain_bwd.inc), as plan creation would specialise it
-        if (d->n_layers <= 0) return MOLANN_E_STAGE;
-        if (d->mlp_precision != MOLANN_MLP_F32) return MOLANN_E_UNSUPPORTED;
-        const int act = d->activation;
-        if (!(act == 0 || act == 1 || act == 2 || act == 3 || act == 5 || act == 7)) return MOLANN_E_UNSUPPORTED;
-        ChainGeom cg;
-        memset(&cg, 0, sizeof(cg));
-        cg.nl = d->n_layers;
-        for (int i = 0; i <= d->n_layers; ++i) cg.dims[i] = d->layer_dims[i];
-        if (!chain_resident(cg)) return MOLANN_E_UNSUPPORTED;
-        std::vector<int> dims(d->layer_dims, d->layer_dims + d->n_layers + 1), kp, jp;
-        std::vector<long> woff;
-        long off = 0;
-        for (int l = 0; l < d->n_layers; ++l) {   // the plan's fp32 MFMA copy: Wp[Jp][Kp] then bias[Jp], 16-byte aligned
-            kp.push_back(ceil_to(dims[l], 16)); jp.push_back(ceil_to(dims[l + 1], 16)); woff.push_back(off);
-            off += (long)jp.back() * kp.back() + jp.back();
-            off = (off + 3) & ~3l;
-        }
-        const int waves = chain_bwd_waves(kp, jp);
-        if (waves <= 0) return MOLANN_E_UNSUPPORTED;
-        const std::string csrc = jit_source_chain_bwd(dims, kp, jp, woff, act, waves);
-        if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", csrc.c_str());
-        if (do_compile & 1) {
-            std::vector<char> code;
-            std::string log;
-            const int rc = jit_compile(csrc, code, log);
-            if (rc != 0) {
-                if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", log.c_str());
-                return rc > 0 ? rc : MOLANN_E_UNSUPPORTED;
-            }
-        }
-        return (int)csrc.size();
-    }
-    if (do_compile & 4) { // the wide bf16 MLP kernel of the same plan (FB as plan creation would choose it)
-        if (d->n_layers <= 0) return MOLANN_E_STAGE;
-        ChainGeom cg;
-        memset(&cg, 0, sizeof(cg));
-        cg.nl = d->n_layers;
-        cg.bf16 = d->mlp_precision == MOLANN_MLP_BF16 ? 1 : 0;
-        for (int i = 0; i <= d->n_layers; ++i) cg.dims[i] = d->layer_dims[i];
-        int fb = 0;
-        for (int f = 4; f >= 1 && fb == 0; --f)
-            if (f * cg.regs_per_fb() <= (chain_resident(cg) ? 256 : 400)) fb = f;
-        if (fb == 0 || (!chain_resident(cg) && 2 * cg.slab_max() * 1024 > 163840 - 1024)) return MOLANN_E_UNSUPPORTED;
-        const std::string csrc = jit_source_chain(cg, d->activation, fb);
-        if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", csrc.c_str());
-        if (do_compile & 1) {
-            std::vector<char> code;
-            std::string log;
-            const int rc = jit_compile(csrc, code, log);
-            if (rc != 0) {
-                if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", log.c_str());
-                return rc > 0 ? rc : MOLANN_E_UNSUPPORTED;
-            }
-        }
-        return (int)csrc.size();
-    }
-    JitSpec j;
-    std::vector<int> slot_of(d->n_inp, -1);
-    auto slot = [&](int atom) {
-        if (slot_of[atom] < 0) { slot_of[atom] = (int)j.slots.size(); j.slots.push_back(atom); }
-        return slot_of[atom];
-    };
-    for (int i = 0; i < d->n_align; ++i)
-        if (slot(d->align_idx[i]) != i) return MOLANN_E_UNSUPPORTED;
-    int col = 0;
-    for (int f = 0; f < d->n_features; ++f) {
-        const int* idx = d->feat_idx + d->feat_ptr[f];
-        const int cnt = d->feat_ptr[f + 1] - d->feat_ptr[f], t = d->feat_type[f];
-        if (t == MOLANN_FEAT_POSITION) {
-            for (int i = 0; i < cnt; ++i) { ItemDev it = {IT_POSITION, col, {slot(idx[i]), 0, 0, 0}, {0, 0}}; it.idx[1] = it.idx[2] = it.idx[3] = it.idx[0]; j.items.push_back(it); col += 3; }
-        } else {
-            ItemDev it;
-            it.type = t == MOLANN_FEAT_ANGLE ? (d->use_angle_value ? IT_ANGLE_VAL : IT_ANGLE_COS)
-                      : t == MOLANN_FEAT_BOND ? IT_BOND : (d->use_angle_value ? IT_DIHEDRAL_VAL : IT_DIHEDRAL_CS);
-            it.col = col;
-            for (int i = 0; i < 4; ++i) it.idx[i] = slot(idx[i < cnt ? i : 0]);
-            it.pad[0] = it.pad[1] = 0;
-            j.items.push_back(it);
-            col += item_width(it.type);
-        }
-    }
-    if (j.items.empty() || (int)j.items.size() > JIT_MAX_ITEMS || (int)j.slots.size() > JIT_MAX_SLOTS) return MOLANN_E_UNSUPPORTED;
-    j.n_inp = d->n_inp; j.n_align = d->n_align; j.act = d->activation; j.d_feat = col;
-    j.n_layers = d->n_layers; j.out_cols = d->n_layers > 0 ? d->layer_dims[d->n_layers] : col;
-    if (d->n_layers > 0) j.dims.assign(d->layer_dims, d->layer_dims + d->n_layers + 1);
-    molann_plan::LaneGeom g;
-    j.win = compact_windows(j.slots, d->n_inp);
-    if (do_compile & 128) { // the WIDE_MLP build (the whole forward of a wide head in the lane kernel)
-        if (d->n_layers <= 0 || d->mlp_precision != MOLANN_MLP_F32) return MOLANN_E_STAGE;
-        ChainGeom cg;
-        memset(&cg, 0, sizeof(cg));
-        cg.nl = d->n_layers; cg.bf16 = 0;
-        for (int i = 0; i <= d->n_layers; ++i) cg.dims[i] = d->layer_dims[i];
-        if (!chain_resident(cg) || cg.total_frags() * 1024 > 112 * 1024) return MOLANN_E_UNSUPPORTED;
-        j.wide_mlp = true; j.img_bytes = (int)(cg.total_frags() * 1024);
-    }
-    jit_geometry(j, g, col, std::max(1, d->n_layers > 0 ? ceil_to(col, 4) : col), j.wide_mlp ? 8 : 14);
-    if (!g.ok || 3 * d->n_inp < 4) return MOLANN_E_UNSUPPORTED;
-    j.waves_per_eu = 2;
-    j.save_feat = (do_compile & 32) != 0 && j.n_layers > 0;   // the feature-keeping twin of the fused forward
-    std::string src = jit_source(j);
-    if (do_compile & 2) { // the backward kernel of the same plan
-        JitSpecBox b;
-        b.j = j;
-        long off = 0;
-        for (int l = 0; l < j.n_layers; ++l) {
-            const int kp = ceil_to(j.dims[l], 16), jp = ceil_to(j.dims[l + 1], 16);
-            b.kp.push_back(kp); b.jp.push_back(jp); b.woff.push_back(off);
-            off += (long)jp * kp + jp;
-            off = (off + 3) & ~3l;
-        }
-        if (do_compile & 16) { // ... in one pass (molann_bwd_ring.inc)
-            if (j.n_layers > 0)
-                for (int v : j.dims) if (v > 32) return MOLANN_E_UNSUPPORTED;
-            long np = 0;
-            for (int l = 0; l < j.n_layers; ++l) np += (long)j.dims[l + 1] * j.dims[l] + j.dims[l + 1];
-            if (!bwd_ring_geometry(b.j, (int)np)) return MOLANN_E_UNSUPPORTED;
-            b.j.with_values = (do_compile & 64) != 0;          // ... the build that also stores the forward's outputs (molann_value_and_vjp_f32)
-            src = jit_source_bwd_ring(b);
-        } else if (do_compile & 8) { // ... its MLP half (molann_mlp_bwd.inc)
-            if (j.n_layers <= 0) return MOLANN_E_STAGE;
-            for (int v : j.dims) if (v > 32) return MOLANN_E_UNSUPPORTED;
-            const int rows = mlp_bwd_rows(j.dims, j.act);
-            const int wpb = (int)std::min<long>(8, (163840 - 64) / ((long)rows * 68 * 4));
-            if (wpb < 1) return MOLANN_E_UNSUPPORTED;
-            src = jit_source_mlp_bwd(b, wpb);
-        } else {             // ... its preprocessing half (molann_lane_bwd.inc)
-            molann_plan::LaneGeom gb;
-            lane_geometry(gb, 64 * d->n_inp * 12, 1);
-            b.j.wpb = gb.wpb;
-            src = jit_source_bwd(b, gb.lds_per_wave);
-        }
-    }
+// the hook's answer: the source in buf and its length; compiled too when asked (bit 1) - then a failure leaves the build log in buf
+static int debug_jit_answer(const std::string& src, int do_compile, const char* flags, char* buf, int cap) {
     if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", src.c_str());
     if (do_compile & 1) {
         std::vector<char> code;
         std::string log;
-        const int rc = jit_compile(src, code, log, (do_compile & 2) ? nullptr : "-fno-slp-vectorize");
+        const int rc = jit_compile(src, code, log, flags);
         if (rc != 0) {
             if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", log.c_str());
             return rc > 0 ? rc : MOLANN_E_UNSUPPORTED;
         }
     }
     return (int)src.size();
+}
+
+// diagnostic / test hook: generate (and optionally compile, needs no GPU) a plan-specialised kernel's source for a description.
+// Returns the source length, or a negative MOLANN_E_* / positive hiprtcResult.  Items, slots, windows, the head's layout and the
+// chain geometry are plan_choose's, every kernel's own geometry comes from the function its builder calls, so the source is the one
+// a plan of this description builds.  A kernel the plan would not build for the description is generated all the same (a head is
+// also asked for on its own, under a feature list that is not its input: E_DESC is plan creation's refusal, not the hook's).
+int molann_debug_jit(const molann_plan_desc* d, int do_compile, char* buf, int cap) {
+    const int v = validate_desc(d);
+    if (v != MOLANN_OK) return v;
+    PlanChoice c;
+    const int chosen = plan_choose(d, c);
+    if (chosen != MOLANN_OK && chosen != MOLANN_E_DESC) return chosen;
+    const int nl = d->n_layers, act = d->activation;
+    std::vector<int> dims;
+    if (nl > 0) dims.assign(d->layer_dims, d->layer_dims + nl + 1);
+    JitSpecBox b;      // the backward kernels read the fp32 copy of the weights
+    {
+        int kp[MOLANN_MAX_LAYERS], jp[MOLANN_MAX_LAYERS];
+        long off[MOLANN_MAX_LAYERS];
+        mlp_layout(d->layer_dims, nl, false, kp, jp, off);
+        set_layout(b, kp, jp, off, nl);
+    }
+    if (do_compile & 512) { // values + vjp in one launch for frames the lane kernels do not take (ensure_group_vjp)
+        if (c.items.empty()) return MOLANN_E_UNSUPPORTED;
+        if (nl > 0 && !head_is_small(d->layer_dims, nl, std::max(c.d_feat, d->layer_dims[0]), d->mlp_precision, act)) return MOLANN_E_UNSUPPORTED;
+        std::vector<int> atoms, ptr, list;
+        group_vjp_tables(d->n_inp, c.items, d->align_idx, d->n_align, atoms, ptr, list);
+        GroupVjpGeom g;
+        if (!group_vjp_geometry(dims, act, c.d_feat, d->n_align, (int)c.items.size(), (int)atoms.size(), (int)list.size(), g)) return MOLANN_E_UNSUPPORTED;
+        return debug_jit_answer(jit_source_group_vjp(dims, b.kp, b.jp, b.woff, act, c.d_feat, d->n_inp, d->n_align, (int)c.items.size(), (int)atoms.size(),
+                                                     (int)list.size(), g), do_compile, nullptr, buf, cap);
+    }
+    if (do_compile & 256) { // the backward of a wide fp32 head with a resident stream (ensure_chain_bwd)
+        if (nl <= 0) return MOLANN_E_STAGE;
+        if (d->mlp_precision != MOLANN_MLP_F32 || !act_served(act) || !chain_resident(c.cg)) return MOLANN_E_UNSUPPORTED;
+        const int waves = chain_bwd_waves(b.kp, b.jp);
+        if (waves <= 0) return MOLANN_E_UNSUPPORTED;
+        return debug_jit_answer(jit_source_chain_bwd(dims, b.kp, b.jp, b.woff, act, waves), do_compile, nullptr, buf, cap);
+    }
+    if (do_compile & 4) { // the chain MLP kernel at the FB plan creation starts from
+        if (nl <= 0) return MOLANN_E_STAGE;
+        const int fb = chain_fb_bound(c.cg);
+        if (fb == 0) return MOLANN_E_UNSUPPORTED;
+        return debug_jit_answer(jit_source_chain(c.cg, act, fb), do_compile, nullptr, buf, cap);
+    }
+    if (!c.lane_spec_ok) return MOLANN_E_UNSUPPORTED;
+    JitSpec j = c.fwd;     // with the whole head in the kernel, whether or not the plan fuses it
+    j.n_layers = nl; j.out_cols = c.out_dim; j.dims = dims;
+    if (do_compile & 128) { // the WIDE_MLP build (the whole forward of a wide head in the lane kernel)
+        if (nl <= 0 || d->mlp_precision != MOLANN_MLP_F32) return MOLANN_E_STAGE;
+        if (!chain_resident(c.cg) || c.cg.total_frags() * 1024 > 112 * 1024) return MOLANN_E_UNSUPPORTED;
+        j = wide_lane_spec(d, c);
+    }
+    molann_plan::LaneGeom g;
+    jit_geometry(j, g, c.d_feat, c.cols_needed, j.wide_mlp ? 8 : 14);
+    if (!g.ok || 3 * d->n_inp < 4) return MOLANN_E_UNSUPPORTED;
+    j.save_feat = (do_compile & 32) != 0 && nl > 0;   // the feature-keeping twin of the fused forward
+    if (!(do_compile & 2)) return debug_jit_answer(jit_source(j), do_compile, "-fno-slp-vectorize", buf, cap);
+    b.j = j;               // the backward kernels of the same plan
+    if (do_compile & (16 | 8))
+        for (int w : dims) if (w > LANE_MLP_MAX_WIDTH) return MOLANN_E_UNSUPPORTED;
+    if (do_compile & 16) { // ... in one pass (ensure_ring_bwd; bit 64: the build that also stores the forward's outputs, ensure_ring_vjp)
+        if (!bwd_ring_geometry(b.j, grad_params_count(d->layer_dims, nl))) return MOLANN_E_UNSUPPORTED;
+        b.j.with_values = (do_compile & 64) != 0;
+        return debug_jit_answer(jit_source_bwd_ring(b), do_compile, nullptr, buf, cap);
+    }
+    if (do_compile & 8) { // ... its MLP half (ensure_mlp_bwd)
+        if (nl <= 0) return MOLANN_E_STAGE;
+        const int wpb = mlp_bwd_wpb(dims, act);
+        if (wpb < 1) return MOLANN_E_UNSUPPORTED;
+        return debug_jit_answer(jit_source_mlp_bwd(b, wpb), do_compile, nullptr, buf, cap);
+    }
+    molann_plan::LaneGeom gb; // ... its preprocessing half (ensure_features_bwd)
+    features_bwd_geometry(d->n_inp, gb);
+    b.j.wpb = gb.wpb;
+    return debug_jit_answer(jit_source_bwd(b, gb.lds_per_wave), do_compile, nullptr, buf, cap);
 }
 
 // diagnostic: read and clear the phase-stamp sums (16 x u64; [0..5] consumer phases, [6] clock ratio, [7] = number of

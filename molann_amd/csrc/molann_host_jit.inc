@@ -643,4 +643,28 @@ int jit_compile(const std::string& src, std::vector<char>& code, std::string& lo
     return (int)r;
 }
 
+// One specialised kernel, ready to launch: compiled (or read from the code-object cache), loaded, its entry point resolved and its
+// scratch bytes asked for (-1: the runtime does not say).  false: nothing stays loaded, rc is the compiler's (0 when the code
+// object did not load), and MOLANN_JIT_VERBOSE prints what failed with the build log.  Which build a caller keeps is its own policy.
+struct BuiltKernel {
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    int scratch = -1, rc = -1;
+    size_t bytes = 0;      // of the code object
+    void unload() { if (mod) (void)hipModuleUnload(mod); mod = nullptr; fn = nullptr; }
+};
+bool build_kernel(const std::string& src, const char* entry, const char* flags, const char* what, BuiltKernel& k) {
+    std::vector<char> code;
+    std::string log;
+    k.rc = jit_compile(src, code, log, flags);
+    k.bytes = code.size();
+    if (k.rc == 0 && hipModuleLoadData(&k.mod, code.data()) == hipSuccess && hipModuleGetFunction(&k.fn, k.mod, entry) == hipSuccess) {
+        if (hipFuncGetAttribute(&k.scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k.fn) != hipSuccess) k.scratch = -1;
+        return true;
+    }
+    k.unload();
+    if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann %s failed rc=%d\n%s\n", what, k.rc, log.c_str());
+    return false;
+}
+
 } // namespace

@@ -38,14 +38,10 @@ int launch_pre(molann_plan* p, const float* x, long n_frames, float* out, int mo
             if (p->train_state == 0) {
                 JitSpec j = p->spec->j;
                 j.save_feat = true;
-                std::vector<char> code;
-                std::string log;
-                int st = -1;
-                if (jit_compile(jit_source(j), code, log, "-fno-slp-vectorize") == 0 && hipModuleLoadData(&p->train_mod, code.data()) == hipSuccess &&
-                    hipModuleGetFunction(&p->train_fn, p->train_mod, "molann_lane_jit") == hipSuccess)
-                    st = 1;
-                else if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann training-forward jit failed\n%s\n", log.c_str());
-                p->train_state = st;
+                BuiltKernel k;
+                const bool built = build_kernel(jit_source(j), "molann_lane_jit", "-fno-slp-vectorize", "training-forward jit", k);
+                p->train_mod = k.mod; p->train_fn = k.fn;
+                p->train_state = built ? 1 : -1;
             }
         }
         if (p->train_state != 1) return MOLANN_E_UNSUPPORTED;
@@ -63,16 +59,11 @@ int launch_pre(molann_plan* p, const float* x, long n_frames, float* out, int mo
                 molann_plan::LaneGeom g;
                 memset(&g, 0, sizeof(g));
                 jit_geometry(j, g, std::max(1, j.d_feat), std::max(1, j.d_feat));
-                std::vector<char> code;
-                std::string log;
-                int st = -1;
-                if (g.ok && jit_compile(jit_source(j), code, log, "-fno-slp-vectorize") == 0 &&
-                    hipModuleLoadData(&p->feat_mod, code.data()) == hipSuccess &&
-                    hipModuleGetFunction(&p->feat_fn, p->feat_mod, "molann_lane_jit") == hipSuccess) {
-                    p->feat_ncons = j.ncons; p->feat_nload = j.nload; p->feat_nslot = j.nslot; p->feat_bpc = j.bpc; p->feat_lds_block = j.lds_block;
-                    st = 1;
-                } else if (getenv("MOLANN_JIT_VERBOSE")) fprintf(stderr, "molann features jit failed\n%s\n", log.c_str());
-                p->feat_state = st;
+                BuiltKernel k;
+                const bool built = g.ok && build_kernel(jit_source(j), "molann_lane_jit", "-fno-slp-vectorize", "features jit", k);
+                p->feat_mod = k.mod; p->feat_fn = k.fn;
+                p->feat_ncons = j.ncons; p->feat_nload = j.nload; p->feat_nslot = j.nslot; p->feat_bpc = j.bpc; p->feat_lds_block = j.lds_block;
+                p->feat_state = built ? 1 : -1;
             }
         }
         if (p->feat_state == 1)

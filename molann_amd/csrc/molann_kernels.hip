@@ -63,6 +63,7 @@ using namespace molann;
 #include "molann_host_plan.inc"
 #include "molann_host_jit.inc"
 #include "molann_host_launch.inc"
+#include "molann_host_create.inc"
 #include "molann_capi.inc"
 #include "molann_jvp.inc"
 #include "molann_hvp.inc"

@@ -84,6 +84,49 @@ for trial in range(400):
     h = ctypes.c_void_p()
     rc = L.molann_plan_create(ctypes.byref(d), ctypes.byref(h))   # no GPU here: validation + expansion, then a HIP error
     assert rc != 0 and not h.value
+# plan_choose - every decision plan creation makes, no device - on the shapes of the named workloads (C1-C5, P1, P2 and the
+# alignment-only A4 / A5), through every kernel the hook generates (source only) and through molann_plan_create up to its first
+# device call
+def chain_feats(n_atoms, n_feat, seed):
+    r = random.Random(seed)
+    out = []
+    for _ in range(n_feat):
+        t = r.choice([0, 1, 2])
+        s = r.randrange(0, n_atoms - 4)
+        out.append((t, list(range(s, s + ARITY[t]))))
+    return out
+
+
+def width(feats, uav=0):
+    return sum(3 * len(ix) if t == 3 else (2 if (t == 2 and not uav) else 1) for t, ix in feats)
+
+
+ALA = [(1, [4, 5]), (2, [0, 2, 1, 3])]
+BACKBONE = [1, 4, 6, 8, 14, 16, 18]
+C3F = [(2, [4, 6, 8, 14]), (2, [6, 8, 14, 16]), (1, [4, 5]), (0, [15, 14, 16])]
+CA, SEL = list(range(8, 5000, 16)), list(range(1, 166, 4))
+C4F, C5F = chain_feats(5000, 64, 41), chain_feats(5000, 256, 42)
+P1F = [(2, list(range(s, s + 4))) for s in range(4, 159, 20)]
+SHAPES = {"C1": (22, [], ALA, [3, 5, 3], 0), "C2": (22, [], ALA, None, 0), "C3": (22, BACKBONE, C3F, [6, 32, 8], 0),
+          "C4": (5000, CA, C4F, [width(C4F), 128, 64, 8], 0), "C5": (5000, CA, C5F, [width(C5F), 512, 256, 16], 1),
+          "P1": (166, SEL, P1F, [16, 32, 8], 0), "P2": (166, SEL, [(3, SEL)], [126, 64, 32, 2], 0),
+          "A4": (5000, CA, [], None, 0), "A5": (166, SEL, [], None, 0)}
+MODES = (0, 2, 2 | 8, 2 | 16, 2 | 16 | 64, 32, 4, 128, 256, 512)
+n_shapes = 0
+for name, (n_inp, align, feats, dims, prec) in SHAPES.items():
+    d, keep = desc(n_inp, align, feats, 0, dims, act=0, prec=prec)
+    got = [L.molann_debug_jit(ctypes.byref(d), mode, buf, 1 << 21) for mode in MODES]
+    assert any(rc > 1000 for rc in got) == bool(feats), (name, got)     # (an alignment alone has no specialised kernel of the hook's)
+    h = ctypes.c_void_p()
+    assert L.molann_plan_create(ctypes.byref(d), ctypes.byref(h)) > 0 and not h.value, name   # chosen, then the HIP error of a machine without a GPU
+    n_shapes += 1
+# two descriptions validate_desc rejects: they never reach the choice
+d, keep = desc(22, BACKBONE, [(1, [4, 22])], 0, None)                                        # atom index outside the frame
+assert all(L.molann_debug_jit(ctypes.byref(d), mode, buf, 1 << 21) == _capi.E_INDEX for mode in MODES)
+assert L.molann_plan_create(ctypes.byref(d), ctypes.byref(h)) == _capi.E_INDEX and not h.value
+d, keep = desc(22, BACKBONE, C3F, 0, [6, 32, 0, 8])                                          # a layer of width 0
+assert all(L.molann_debug_jit(ctypes.byref(d), mode, buf, 1 << 21) == _capi.E_DESC for mode in MODES)
+assert L.molann_plan_create(ctypes.byref(d), ctypes.byref(h)) == _capi.E_DESC and not h.value
 # malformed ABI, null pointers
 d, keep = desc(22, [1, 4], [(1, [4, 5])], 0, None, abi=99)
 assert L.molann_debug_jit(ctypes.byref(d), 0, buf, 1 << 21) < 0
@@ -112,5 +155,5 @@ for act in range(-1, 10):
         L.molann_selftest_act_derivative(act, ctypes.c_float(v))
 GR, GH = (ctypes.c_float * 9)(*[0.1 * i for i in range(9)]), (ctypes.c_float * 9)()
 assert L.molann_selftest_kabsch_backward(H, R, GR, GH) == 0
-print("san_driver ok: %d sources generated, %d descriptions rejected" % (n_ok, n_rej))
+print("san_driver ok: %d sources generated, %d descriptions rejected, %d workload shapes chosen" % (n_ok, n_rej, n_shapes))
 sys.exit(0)

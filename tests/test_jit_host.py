@@ -146,3 +146,38 @@ def test_chain_kernel_slab_buffers(dims, precision, nslab):
     src = buf.value.decode()
     assert "constexpr int NSLAB = %d;" % nslab in src
     assert ("constexpr bool RESIDENT = true;" in src) == (nslab == 1)
+
+
+def _chain_regs_per_fb(dims, bf16):
+    """ChainGeom::regs_per_fb (csrc/molann_dev_mlp.inc): the registers the chain kernel keeps live per 16-frame block."""
+    nl = len(dims) - 1
+    cb, kw = (2, 32) if bf16 else (1, 16)
+    ub = lambda l: (dims[l + 1] + 15) // 16                              # noqa: E731
+    ubp = lambda l: (ub(l) + cb - 1) // cb * cb                          # noqa: E731
+    ks = lambda l: (dims[0] + kw - 1) // kw if l == 0 else ubp(l - 1) // cb   # noqa: E731
+    m = 0
+    for p in range((nl + 1) // 2):
+        has_c = 2 * p + 1 < nl
+        ubc, ksn = (ub(2 * p + 1), ubp(2 * p + 1) // cb) if has_c else (0, 0)
+        m = max(m, 4 * (ks(2 * p) + ubc + cb + (ksn + 1) // 2))
+    return m
+
+
+@pytest.mark.parametrize("dims,precision", [([960, 64, 8], _capi.MLP_F32), ([960, 128, 8], _capi.MLP_BF16)])
+def test_streaming_chain_kernel_fb_is_the_plans(dims, precision):
+    """The chain kernel of a STREAMING head (weights through LDS slabs, four waves per block: one per SIMD, 512 registers) starts
+    at the most 16-frame blocks per wave whose registers fit 512 - plan creation's bound.  Both heads are chosen where a bound
+    of 400 gives another FB (fp32: 252 registers per block, 2 against 1; bf16: 136, 3 against 2), so a hook that does not read
+    the plan's choice is caught."""
+    regs = _chain_regs_per_fb(dims, precision == _capi.MLP_BF16)
+    fb_plan = max(f for f in (1, 2, 3, 4) if f * regs <= 512)
+    assert fb_plan != max(f for f in (1, 2, 3, 4) if f * regs <= 400)
+    d, keep = _desc(wl.get_workload("C3"))
+    ld = (ctypes.c_int32 * len(dims))(*dims)
+    d.n_layers, d.layer_dims, d.mlp_precision = len(dims) - 1, ld, precision
+    buf = ctypes.create_string_buffer(1 << 21)
+    rc = _capi.lib().molann_debug_jit(ctypes.byref(d), 4, buf, 1 << 21)
+    assert rc > 1000, rc
+    preamble = buf.value.decode().split('#line 1 "molann_mlp_jit.inc"')[0]
+    assert "constexpr bool RESIDENT = false;" in preamble
+    assert "constexpr int FB = %d;" % fb_plan in preamble
