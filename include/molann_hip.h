@@ -260,6 +260,22 @@ int molann_value_and_vjp_f32(molann_plan* plan, const float* x, const float* gra
 /* 1 when molann_value_and_vjp_f32 serves the plan, 0 otherwise.  Builds the kernel it reports (call it before a capture). */
 int molann_plan_supports_value_and_vjp(molann_plan* plan);
 
+/* molann_value_and_vjp_f32 in float64 (`model.double()`): out[N, out_dim] = molann_forward_f64(x) (molann_features_f64(x) for a
+ * plan without an MLP) AND grad_x[N, n_inp, 3] = the vector-Jacobian product for grad_out[N, out_dim], everything in double, in
+ * ONE launch of frames_value_vjp_f64_kernel (ahead of time: no hipRTC).  W, b as molann_forward_f64 takes them (HOST arrays of
+ * n_layers device pointers to the torch.nn.Linear tensors, read as they are; ignored - may be NULL - for a plan without an MLP).
+ * Parameters are data.  Every plan with feature items, with or without an alignment, any frame size, any head (all nine
+ * activations); lane groups of 8..64 per frame.  Each row of grad_x is stored once (zeros for atoms the plan does not touch), its
+ * terms summed in a plan-time order: no atomics, the same bits on every run.  MOLANN_E_STAGE for a plan without items,
+ * MOLANN_E_UNSUPPORTED only where one frame's rows (feature_dim + the hidden widths + twice the widest of them, in doubles)
+ * exceed the LDS of a compute unit.  All pointers 8-byte aligned, contiguous.  The call only enqueues on `stream` (no workspace, no
+ * event): thread-safe and capturable. */
+int molann_value_and_vjp_f64(molann_plan* plan, const double* x, const double* grad_out, int64_t n_frames, const double* const* W,
+                             const double* const* b, double* out, double* grad_x, molann_stream_t stream);
+
+/* 1 when molann_value_and_vjp_f64 serves the plan (feature items, and a frame's rows fit the LDS), 0 otherwise. */
+int molann_plan_supports_value_and_vjp_f64(const molann_plan* plan);
+
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
  * is fused into the lane kernel, and large-frame plans with a head within the fused MLP's limits (the features are written
@@ -318,6 +334,8 @@ float molann_selftest_activation(int act, float v);
 int molann_selftest_feature_backward(int type, int use_angle_value, const float* atoms_xyz, const float* g3, float* ga12);
 int molann_selftest_kabsch_backward(const double* H9, const float* R9, const float* GR9, float* GH9);
 float molann_selftest_act_derivative(int act, float z);
+/* the float64 head's derivative of activation `act` at the pre-activation z (all nine codes) */
+double molann_selftest_act_derivative_f64(int act, double z);
 /* forward mode: the item's values and their derivatives along the atoms' tangents (t12: 4 atoms x xyz); return the width */
 int molann_selftest_feature_tangent_f32(int type, int use_angle_value, const float* atoms_xyz, const float* t12, float* out3,
                                         float* dout3);

@@ -990,15 +990,21 @@ class MolANN(_PlanOwner, torch.nn.Module):
         forward plus a backward.  The Jacobian of one frame: ``x.expand(d_out, -1, -1)`` with ``torch.eye(d_out)`` as cotangent.
         No autograd graph is recorded (parameters are data); ``into=(y, dx)`` reuses the caller's buffers.  Models served by one
         fused plan whose backward is the one-pass kernel, and models on larger frames (molann_group_vjp) with no head or a head of
-        at most 4 layers, every width <= 32, fp32, tanh / ReLU / sigmoid / identity / SiLU / LeakyReLU; float32."""
+        at most 4 layers, every width <= 32, fp32, tanh / ReLU / sigmoid / identity / SiLU / LeakyReLU; float32.
+
+        float64 (`model.double()` and a float64 x; `molann_value_and_vjp_f64`, one launch of frames_value_vjp_f64_kernel): every
+        model served by one fused plan - any frame size, with or without an alignment, a head of any width with any of the
+        nine activations.  Each row of dx is stored once, its terms summed in a fixed order: the same bits on every call."""
         st = self._fast_state(x) if isinstance(x, torch.Tensor) and x.is_cuda else None
         if st is None or not st["fused"]:
             raise NotImplementedError("value_and_vjp needs a model served by one fused plan on a HIP device (a feature layer and a "
-                                      "Linear / activation head, float32, on a HIP tensor)")
+                                      "Linear / activation head, float32 or float64, on a HIP tensor)")
         al, fl = st["al"], st["fl"]
         _check_input(x, fl.input_atom_num)
+        if x.dtype == torch.float64:
+            return self._value_and_vjp_f64(st, x, grad_out, into)
         if x.dtype != torch.float32:
-            raise TypeError("value_and_vjp is float32 only; got %s" % x.dtype)
+            raise TypeError("value_and_vjp is float32 / float64; got %s" % x.dtype)
         x = x.detach()
         x = x if x.is_contiguous() else x.contiguous()
         lins = st["linears"]
@@ -1031,6 +1037,46 @@ class MolANN(_PlanOwner, torch.nn.Module):
                 y, dx = torch.empty((n, out_dim), dtype=torch.float32, device=x.device), torch.empty_like(x)
             g = grad_out if (grad_out.dtype == torch.float32 and grad_out.is_contiguous()) else grad_out.float().contiguous()
             entry.plan.value_and_vjp(x, g, y, dx)
+        return y, dx
+
+    def _value_and_vjp_f64(self, st, x, grad_out, into):
+        """`value_and_vjp` of a float64 model: the arguments are checked here for both ways to the kernel (the dispatcher
+        operator where that library is built, else the ctypes plan)."""
+        al, lins = st["al"], st["linears"]
+        w0 = lins[0].weight
+        if w0.device != x.device or w0.dtype != torch.float64:
+            raise RuntimeError("ann_layers must be float64 on %s for a float64 input (got %s on %s): call .double()"
+                               % (x.device, w0.dtype, w0.device))
+        x = x.detach()
+        x = x if x.is_contiguous() else x.contiguous()
+        n, out_dim = x.shape[0], st["out_dim"]
+        if not isinstance(grad_out, torch.Tensor) or grad_out.numel() != n * out_dim or grad_out.device != x.device:
+            raise ValueError("value_and_vjp: grad_out must hold [%d, %d] values on %s" % (n, out_dim, x.device))
+        if not grad_out.dtype.is_floating_point:
+            raise TypeError("value_and_vjp: grad_out must be a floating-point tensor; got %s" % grad_out.dtype)
+        if into is not None:
+            if len(into) != 2 or not all(isinstance(t, torch.Tensor) for t in into):
+                raise TypeError("value_and_vjp: `into` must be a pair of tensors (y, dx)")
+            y, dx = into
+            if y.dtype != torch.float64 or dx.dtype != torch.float64:
+                raise TypeError("value_and_vjp: `into` must be float64 like x; got %s, %s" % (y.dtype, dx.dtype))
+            if not (y.is_contiguous() and dx.is_contiguous()) or y.numel() != n * out_dim or dx.numel() != x.numel() \
+                    or y.device != x.device or dx.device != x.device:
+                raise ValueError("value_and_vjp: `into` must be contiguous {[%d, %d], %s} on %s" % (n, out_dim, tuple(x.shape), x.device))
+        g = grad_out if (grad_out.dtype == torch.float64 and grad_out.is_contiguous()) else grad_out.double().contiguous()
+        if st["op"] is not None:
+            y, dx = st["op_vjp"](x, st["handle"], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"],
+                                 [lin.weight for lin in lins], [lin.bias for lin in lins], g, list(into) if into is not None else [])
+            return y, dx
+        entry = st["entry"]()
+        with torch.cuda.device(x.device):
+            if al is not None:
+                entry.sync_ref(_device_buffer(al.ref_x, x))
+            if into is None:
+                y, dx = torch.empty((n, out_dim), dtype=torch.float64, device=x.device), torch.empty_like(x)
+            if n > 0:
+                entry.plan.value_and_vjp_f64(x, g, [lin.weight.detach().contiguous() for lin in lins],
+                                             [lin.bias.detach().contiguous() for lin in lins], y, dx)
         return y, dx
 
     def _tangent_present(self, x):

@@ -498,6 +498,22 @@ MOLANN_HD float act_derivative(int act, float z, float h) {
     }
 }
 
+// Derivative of apply_activation_f64 from its INPUT z (the float64 head keeps its pre-activations), all nine codes.
+MOLANN_HD double act_derivative_f64(int act, double z) {
+    switch (act) {
+    case 0: { const double t = tanh(z); return fma(-t, t, 1.0); }
+    case 1: return z > 0.0 ? 1.0 : 0.0;                    // torch's convention at 0
+    case 2: { const double s = 1.0 / (1.0 + exp(-z)); return s * (1.0 - s); }
+    case 3: return 1.0;
+    case 4: return z > 0.0 ? 1.0 : exp(z);                 // ELU(alpha=1)
+    case 5: { const double s = 1.0 / (1.0 + exp(-z)); return s * fma(z, 1.0 - s, 1.0); }   // SiLU' = s (1 + z (1 - s))
+    case 6: return z > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-z)); // Softplus(beta=1, threshold=20)
+    case 7: return z > 0.0 ? 1.0 : 0.01;
+    case 8: return fma(z * 0.39894228040143267794, exp(-0.5 * z * z), 0.5 * (1.0 + erf(z * 0.70710678118654752)));   // Phi(z) + z phi(z)
+    default: return 1.0;
+    }
+}
+
 // Backward of kabsch_rotation: given H, the rotation R it produced and G_R = dL/dR, returns G_H = dL/dH.
 // With S = R^T H (symmetric at the optimum) a perturbation dH turns R by dR = R [w]x where
 // (tr(S) I - S) w = vee(R^T dH - dH^T R); hence G_H = R [n]x, n = (tr(S) I - S)^-1 vee(M - M^T), M = R^T G_R.

@@ -379,8 +379,8 @@ std::vector<at::Tensor> run_backward_hip(const at::Tensor& x_in, std::vector<int
 }
 
 // {out, grad_x}: the forward's outputs and the vector-Jacobian product for grad_out in ONE launch (molann_value_and_vjp_f32: the
-// one-pass backward that also stores the outputs).  Parameters are data.  `into` (optional: {out, grad_x} of the right shapes)
-// is written instead of fresh tensors - a caller at every MD step keeps its two buffers.
+// one-pass backward that also stores the outputs; a float64 x: molann_value_and_vjp_f64 on the float64 Linear tensors).
+// Parameters are data.  `into` (optional: {out, grad_x} of the right shapes) is written instead of fresh tensors - a caller at every MD step keeps its two buffers.
 std::vector<at::Tensor> value_and_vjp_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x, const std::vector<at::Tensor>& weights,
                                            const std::vector<at::Tensor>& biases, const at::Tensor& grad_out, const std::vector<at::Tensor>& into);
 std::vector<at::Tensor> value_and_vjp_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -400,29 +400,49 @@ std::vector<at::Tensor> value_and_vjp_h_hip(const at::Tensor& x_in, int64_t hand
 std::vector<at::Tensor> value_and_vjp_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x, const std::vector<at::Tensor>& weights,
                                            const std::vector<at::Tensor>& biases, const at::Tensor& grad_out, const std::vector<at::Tensor>& into) {
     check_x(x_in, desc);
-    TORCH_CHECK(x_in.scalar_type() == at::kFloat, "molann::value_and_vjp: float32 only");
+    const bool f64 = x_in.scalar_type() == at::kDouble;   // `model.double()`: molann_value_and_vjp_f64, the Linear tensors read as they are
+    const at::ScalarType st = x_in.scalar_type();
     const at::Tensor x = x_in.contiguous();
     const c10::DeviceGuard guard(x.device());
     const bool align_only = desc[1] == KIND_ALIGN;
     auto e = entry_for(align_only ? align_as_features(desc) : desc, x, ref_x);
     const int64_t n = x.size(0);
     const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
-    at::Tensor g = grad_out.scalar_type() == at::kFloat && grad_out.is_contiguous() ? grad_out : grad_out.to(at::kFloat).contiguous();
+    at::Tensor g = grad_out.scalar_type() == st && grad_out.is_contiguous() ? grad_out : grad_out.to(st).contiguous();
     TORCH_CHECK(g.numel() == n * cols && g.device() == x.device(), "molann::value_and_vjp: grad_out must be [", n, ", ", cols, "] on ", x.device());
     at::Tensor out, gx;
     if (into.size() == 2) {
         out = into[0]; gx = into[1];
-        TORCH_CHECK(out.is_contiguous() && gx.is_contiguous() && out.scalar_type() == at::kFloat && gx.scalar_type() == at::kFloat &&
+        TORCH_CHECK(out.is_contiguous() && gx.is_contiguous() && out.scalar_type() == st && gx.scalar_type() == st &&
                     out.numel() == n * cols && gx.numel() == x.numel() && out.device() == x.device() && gx.device() == x.device(),
-                    "molann::value_and_vjp: `into` must be contiguous float32 {[N, out_dim], [N, n_inp, 3]} on x's device");
+                    "molann::value_and_vjp: `into` must be contiguous ", f64 ? "float64" : "float32", " {[N, out_dim], [N, n_inp, 3]} on x's device");
     } else {
         out = at::empty({n, cols}, x.options());
         gx = at::empty_like(x);
+    }
+    std::vector<at::Tensor> hold;
+    std::vector<const double*> W, B;
+    if (f64 && e->kind == KIND_FORWARD) {
+        TORCH_CHECK((int)weights.size() == e->n_layers && (int)biases.size() == e->n_layers, "molann::value_and_vjp: expected ", e->n_layers,
+                    " weight and bias tensors");
+        for (int l = 0; l < e->n_layers; ++l) {
+            TORCH_CHECK(weights[l].scalar_type() == at::kDouble && biases[l].scalar_type() == at::kDouble && weights[l].device() == x.device() &&
+                            biases[l].device() == x.device(),
+                        "molann::value_and_vjp: ann_layers must be float64 on ", x.device(), " for a float64 input");
+            hold.push_back(weights[l].detach().contiguous()); W.push_back(hold.back().data_ptr<double>());
+            hold.push_back(biases[l].detach().contiguous()); B.push_back(hold.back().data_ptr<double>());
+        }
     }
     if (n == 0) return {out, gx};
     hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
     std::lock_guard<std::mutex> lock(e->mu);
     sync_live(*e, x, ref_x, weights, biases, stream);
+    if (f64) {
+        check(molann_value_and_vjp_f64(e->plan, x.data_ptr<double>(), g.data_ptr<double>(), n, W.data(), B.data(), out.data_ptr<double>(),
+                                       gx.data_ptr<double>(), stream),
+              "molann_value_and_vjp_f64");
+        return {out, gx};
+    }
     check(molann_value_and_vjp_f32(e->plan, x.data_ptr<float>(), g.data_ptr<float>(), n, out.data_ptr<float>(), gx.data_ptr<float>(), stream),
           "molann_value_and_vjp_f32");
     return {out, gx};

@@ -23,7 +23,7 @@ def _unpin_plans(desc, device):
 
 class GraphedForward(object):
     def __init__(self, model, example_x, warmup=3):
-        assert example_x.is_cuda and example_x.dtype == torch.float32
+        assert example_x.is_cuda and example_x.dtype in (torch.float32, torch.float64)   # float64: a `model.double()`
         self.model = model
         self.static_x = example_x.detach().clone().contiguous()
         self.static_y = None
@@ -82,15 +82,19 @@ class GraphedForces(GraphedForward):
     nothing else links the two graphs), built and warmed before capture.  Models on frames of a few hundred atoms with a small
     head (no one-pass kernel: wave-per-frame preprocessing) are captured as forward-with-kept-features and the two-launch backward
     on them (`_recapture_kept_features`); their `value_and_vjp` is one launch of molann_group_vjp where the plan has it.
+    A float64 model (`model.double()`, float64 `x_example`): the second graph is one launch of `molann_value_and_vjp_f64`, which
+    `vjp` and `value_and_vjp` replay.
     `recapture()` after changing parameters."""
 
     def recapture(self):
         super(GraphedForces, self).recapture()
         x = self.static_x
+        if x.dtype == torch.float64:
+            return self._recapture_f64()
         plan = self.model.plan_for(x) if hasattr(self.model, "plan_for") else None
         if plan is None or not plan.supports_backward():
             raise NotImplementedError("GraphedForces needs a model served by one fused plan with a backward kernel")
-        self._kept = False
+        self._kept = self._f64 = False
         if plan.backward_kind() == 1 and plan.kernel_family == 1:
             return self._recapture_kept_features(plan)
         if plan.backward_kind() != 2:
@@ -113,6 +117,30 @@ class GraphedForces(GraphedForward):
         self.bwd_graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.bwd_graph), torch.cuda.device(x.device):
             plan.backward(x, self.static_dy, self.static_dx, None)
+        return self
+
+    def _recapture_f64(self):
+        """A float64 model (`model.double()`): values and forces are ONE launch of `molann_value_and_vjp_f64`, which only enqueues
+        on the stream it is given (no workspace, no events, nothing built at run time), so it captures as it is.  The backward
+        graph holds that launch on the static x and cotangent; `vjp` and `value_and_vjp` both replay it."""
+        x = self.static_x
+        st = self.model._fast_state(x) if hasattr(self.model, "_fast_state") else None
+        if st is None or not st["fused"]:
+            raise NotImplementedError("GraphedForces needs a model served by one fused plan")
+        self._kept, self._f64, self._plan = False, True, None
+        self.static_dy = torch.zeros_like(self.static_y)
+        self.static_dx = torch.empty_like(x)
+        self.static_y2 = torch.empty_like(self.static_y)
+        side = torch.cuda.Stream(device=x.device)
+        side.wait_stream(torch.cuda.current_stream(x.device))
+        with torch.cuda.stream(side), torch.cuda.device(x.device):
+            for _ in range(self._warmup):       # builds the plan and synchronises ref_x outside the capture
+                self.model.value_and_vjp(x, self.static_dy, into=(self.static_y2, self.static_dx))
+        torch.cuda.current_stream(x.device).wait_stream(side)
+        torch.cuda.synchronize(x.device)
+        self.bwd_graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.bwd_graph), torch.cuda.device(x.device):
+            self.model.value_and_vjp(x, self.static_dy, into=(self.static_y2, self.static_dx))
         return self
 
     def _recapture_kept_features(self, plan):
@@ -166,6 +194,11 @@ class GraphedForces(GraphedForward):
         if x.shape != self.static_x.shape or dy.shape != self.static_dy.shape:
             raise ValueError("GraphedForces was captured for %s / %s, got %s / %s" % (tuple(self.static_x.shape), tuple(self.static_dy.shape),
                                                                                     tuple(x.shape), tuple(dy.shape)))
+        if self._f64:                             # the captured launch of molann_value_and_vjp_f64
+            self.static_x.copy_(x)
+            self.static_dy.copy_(dy)
+            self.bwd_graph.replay()
+            return self.static_y2, self.static_dx
         if self._kept and not self._single:       # no single launch for this plan: the two replays
             self.static_x.copy_(x)
             self.static_dy.copy_(dy)
