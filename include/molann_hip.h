@@ -276,6 +276,22 @@ int molann_value_and_vjp_f64(molann_plan* plan, const double* x, const double* g
 /* 1 when molann_value_and_vjp_f64 serves the plan (feature items, and a frame's rows fit the LDS), 0 otherwise. */
 int molann_plan_supports_value_and_vjp_f64(const molann_plan* plan);
 
+/* Values AND the full Jacobian of a float64 model in ONE launch of frames_value_jac_f64_kernel (ahead of time: no hipRTC):
+ * out[N, out_dim] = molann_value_and_vjp_f64's out, bit for bit, and jac[N, out_dim, n_inp, 3] with jac[f, k] = d out[f, k] / d x[f]
+ * (out_dim = feature_dim for a plan without an MLP), everything in double.  x, the Kabsch solve, the features and the head forward
+ * are read and computed once per frame, each item's backward once per output column of the item; the out_dim rows are linear
+ * combinations of those.  W, b as molann_value_and_vjp_f64 takes them.  Every row of every jac[f, k] is stored once (zeros for atoms
+ * the plan does not touch), its terms summed in a plan-time order: no atomics, the same bits on every run.  MOLANN_E_STAGE for a
+ * plan without items, MOLANN_E_UNSUPPORTED where one frame's rows (feature_dim + the hidden widths + 2 out_dim times the widest
+ * layer input, + 12 out_dim with an alignment, in doubles) exceed the LDS of a compute unit.  n_frames < 0: MOLANN_E_DESC;
+ * n_frames == 0: nothing is read or launched.  All pointers 8-byte aligned, contiguous.  The call only enqueues on `stream` (no
+ * workspace, no event): thread-safe and capturable. */
+int molann_value_and_jacobian_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                                  double* out, double* jac, molann_stream_t stream);
+
+/* 1 when molann_value_and_jacobian_f64 serves the plan (feature items, and a frame's rows fit the LDS), 0 otherwise. */
+int molann_plan_supports_value_and_jacobian_f64(const molann_plan* plan);
+
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
  * is fused into the lane kernel, and large-frame plans with a head within the fused MLP's limits (the features are written
@@ -336,6 +352,9 @@ int molann_selftest_kabsch_backward(const double* H9, const float* R9, const flo
 float molann_selftest_act_derivative(int act, float z);
 /* the float64 head's derivative of activation `act` at the pre-activation z (all nine codes) */
 double molann_selftest_act_derivative_f64(int act, double z);
+/* the unit-cotangent local Jacobian frames_value_jac_f64_kernel combines: jac36[c][j][xyz] = d(output column c of the item) /
+ * d(atom j) for the item's 4 atoms (rows past the item's width are 0); returns the width */
+int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* atoms_xyz, double* jac36);
 /* forward mode: the item's values and their derivatives along the atoms' tangents (t12: 4 atoms x xyz); return the width */
 int molann_selftest_feature_tangent_f32(int type, int use_angle_value, const float* atoms_xyz, const float* t12, float* out3,
                                         float* dout3);

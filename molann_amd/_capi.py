@@ -103,6 +103,8 @@ def lib():
             "molann_value_and_vjp_f32": (i32, [vp, vp, vp, i64, vp, vp, vp]),
             "molann_value_and_vjp_f64": (i32, [vp, vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp]),
             "molann_plan_supports_value_and_vjp_f64": (i32, [vp]),
+            "molann_value_and_jacobian_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp]),
+            "molann_plan_supports_value_and_jacobian_f64": (i32, [vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -117,6 +119,7 @@ def lib():
             "molann_selftest_kabsch_backward": (i32, [vp, vp, vp, vp]),
             "molann_selftest_act_derivative": (f32, [i32, f32]),
             "molann_selftest_act_derivative_f64": (ctypes.c_double, [i32, ctypes.c_double]),
+            "molann_selftest_item_jacobian_f64": (i32, [i32, i32, vp, vp]),
             "molann_features_jvp_f32": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
             "molann_features_jvp_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
             "molann_selftest_feature_tangent_f32": (i32, [i32, i32, vp, vp, vp, vp]),
@@ -363,6 +366,22 @@ class Plan(object):
         if code != 0:
             raise MolannHipError(code, "molann_value_and_vjp_f64")
         return out, grad_x
+
+    def supports_value_and_jacobian_f64(self):
+        """True when `value_and_jacobian_f64` serves this plan: feature items, and a frame's rows fit the LDS (nothing is built)."""
+        return lib().molann_plan_supports_value_and_jacobian_f64(self._handle) == 1
+
+    def value_and_jacobian_f64(self, x, weights, biases, out, jac):
+        """out[N, d_out] and jac[N, d_out, n_inp, 3] = d out / d x in float64, one launch of frames_value_jac_f64_kernel: `weights` /
+        `biases` are the float64 Linear tensors on x's device, read as they are (empty lists for a plan without a head)."""
+        n = len(weights)
+        W = (ctypes.c_void_p * max(1, n))(*[w.data_ptr() for w in weights])
+        B = (ctypes.c_void_p * max(1, n))(*[b.data_ptr() for b in biases])
+        code = _lib.molann_value_and_jacobian_f64(self._handle, x.data_ptr(), x.shape[0], W, B, out.data_ptr(), jac.data_ptr(),
+                                                  torch.cuda.current_stream().cuda_stream)
+        if code != 0:
+            raise MolannHipError(code, "molann_value_and_jacobian_f64")
+        return out, jac
 
     def forward_train(self, x, out, features):
         """`forward_packed` that also keeps the features (for `mlp_backward` + `features_backward`)."""

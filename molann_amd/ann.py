@@ -987,7 +987,9 @@ class MolANN(_PlanOwner, torch.nn.Module):
         """``(y, dx)`` with ``y = self(x)`` and ``dx = sum_k grad_out[:, k] d y[:, k] / d x`` in ONE kernel launch
         (`molann_value_and_vjp_f32`: the one-pass backward recomputes the forward anyway and, in this build, stores it too).
         For a caller that needs a collective variable and its forces at every step (`README.rst:49`): ~half the host time of a
-        forward plus a backward.  The Jacobian of one frame: ``x.expand(d_out, -1, -1)`` with ``torch.eye(d_out)`` as cotangent.
+        forward plus a backward.  The full Jacobian of a float64 model: `value_and_jacobian`, one launch that reads x and solves the
+        rotation once per frame (``x.expand(d_out, -1, -1)`` with ``torch.eye(d_out)`` as cotangent repeats both per output; it
+        remains the route for float32).
         No autograd graph is recorded (parameters are data); ``into=(y, dx)`` reuses the caller's buffers.  Models served by one
         fused plan whose backward is the one-pass kernel, and models on larger frames (molann_group_vjp) with no head or a head of
         at most 4 layers, every width <= 32, fp32, tanh / ReLU / sigmoid / identity / SiLU / LeakyReLU; float32.
@@ -1078,6 +1080,60 @@ class MolANN(_PlanOwner, torch.nn.Module):
                 entry.plan.value_and_vjp_f64(x, g, [lin.weight.detach().contiguous() for lin in lins],
                                              [lin.bias.detach().contiguous() for lin in lins], y, dx)
         return y, dx
+
+    def value_and_jacobian(self, x, into=None):
+        """``(y, jac)`` with ``y = self(x)`` [N, d_out] and ``jac[f, k] = d y[f, k] / d x[f]`` [N, d_out, n_inp, 3], float64, in ONE
+        kernel launch (`molann_value_and_jacobian_f64`, frames_value_jac_f64_kernel): what a collective variable hands an MD engine
+        (every component's derivative with respect to the positions) and what a loss built from ``grad_x y_k`` for every k needs.
+        x, the rotation, the features and the head forward are read and computed once per frame; ``y`` is `value_and_vjp`'s, bit for
+        bit.  No autograd graph is recorded (parameters are data); ``into=(y, jac)`` reuses the caller's buffers.  Every row of
+        ``jac`` is stored once, its terms summed in a fixed order: the same bits on every call.  `model.double()` and a float64 x
+        on a HIP device; a model served by one fused plan."""
+        route = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
+        st = self._fast_state(x) if isinstance(x, torch.Tensor) and x.is_cuda else None
+        if st is None or not st["fused"]:
+            raise NotImplementedError("value_and_jacobian needs a model served by one fused plan on a HIP device (a feature layer and a "
+                                      "Linear / activation head, float64, on a HIP tensor); otherwise " + route)
+        al, fl, lins = st["al"], st["fl"], st["linears"]
+        _check_input(x, fl.input_atom_num)
+        if x.dtype != torch.float64:
+            raise TypeError("value_and_jacobian is float64: call model.double() and pass a float64 x (got %s); for float32 %s"
+                            % (x.dtype, route))
+        w0 = lins[0].weight
+        if w0.device != x.device or w0.dtype != torch.float64:
+            raise RuntimeError("ann_layers must be float64 on %s for a float64 input (got %s on %s): call .double()"
+                               % (x.device, w0.dtype, w0.device))
+        x = x.detach()
+        x = x if x.is_contiguous() else x.contiguous()
+        n, out_dim = x.shape[0], st["out_dim"]
+        if into is not None:
+            if len(into) != 2 or not all(isinstance(t, torch.Tensor) for t in into):
+                raise TypeError("value_and_jacobian: `into` must be a pair of tensors (y, jac)")
+            y, jac = into
+            if y.dtype != torch.float64 or jac.dtype != torch.float64:
+                raise TypeError("value_and_jacobian: `into` must be float64 like x; got %s, %s" % (y.dtype, jac.dtype))
+            if not (y.is_contiguous() and jac.is_contiguous()) or y.numel() != n * out_dim or jac.numel() != out_dim * x.numel() \
+                    or y.device != x.device or jac.device != x.device:
+                raise ValueError("value_and_jacobian: `into` must be contiguous {[%d, %d], [%d, %d, %d, 3]} on %s"
+                                 % (n, out_dim, n, out_dim, x.shape[1], x.device))
+        if st["op"] is not None:
+            y, jac = torch.ops.molann.value_and_jacobian_h(x, st["handle"], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"],
+                                                           [lin.weight for lin in lins], [lin.bias for lin in lins],
+                                                           list(into) if into is not None else [])
+            return y, jac
+        entry = st["entry"]()
+        with torch.cuda.device(x.device):
+            if not entry.plan.supports_value_and_jacobian_f64():
+                raise NotImplementedError("value_and_jacobian: one frame's rows exceed the LDS of a compute unit for this model; " + route)
+            if al is not None:
+                entry.sync_ref(_device_buffer(al.ref_x, x))
+            if into is None:
+                y = torch.empty((n, out_dim), dtype=torch.float64, device=x.device)
+                jac = torch.empty((n, out_dim, x.shape[1], 3), dtype=torch.float64, device=x.device)
+            if n > 0:
+                entry.plan.value_and_jacobian_f64(x, [lin.weight.detach().contiguous() for lin in lins],
+                                                  [lin.bias.detach().contiguous() for lin in lins], y, jac)
+        return y, jac
 
     def _tangent_present(self, x):
         if _has_tangent(x):

@@ -19,6 +19,8 @@ namespace {
 //      tables) - a slot recomputes its item's backward and adds g_p, an align slot adds G_H ref_i - cen.  Every row of gx is
 //      stored once, untouched atoms as zeros: no atomics, no zeroing pass, the same bits on every run.
 // The lanes of a frame exchange data through LDS only inside their own wave: lds_wave_sync() orders it, there is no block barrier.
+// Steps 1-3 are the device functions frame_rotation_f64 / frame_features_f64 / frame_head_forward_f64 below, shared with
+// frames_value_jac_f64_kernel (molann_dev_jac_f64.inc).
 // =============================================================================================
 struct VjpF64Args {
     long n_frames;
@@ -53,6 +55,73 @@ __device__ __forceinline__ void item_backward_f64(const ItemDev& d, const double
     eval_item_backward_f64(d.type, y[0], y[1], y[2], y[3], g3, gy[0], gy[1], gy[2], gy[3]);
 }
 
+// Steps 1-3 of a frame, shared with frames_value_jac_f64_kernel (molann_dev_jac_f64.inc): they do not depend on the cotangent.
+// ---- 1. centroid, covariance, rotation (frames_f64_kernel's formulas)
+template <int G>
+__device__ __forceinline__ void frame_rotation_f64(const double* __restrict__ xf, const int* __restrict__ align_idx, const double* __restrict__ ref64,
+                                                   int n_align, int gl, V3d& c, double (&h)[9], double (&R)[9]) {
+    double sx = 0., sy = 0., sz = 0.;
+    for (int i = gl; i < n_align; i += G) { const V3d p = load_atom_f64(xf, align_idx[i]); sx += p.x; sy += p.y; sz += p.z; }
+    const double inv_a = 1.0 / (double)n_align;
+    c = v3d(group_sum<G>(sx) * inv_a, group_sum<G>(sy) * inv_a, group_sum<G>(sz) * inv_a);
+    double g = 0.;
+    for (int i = gl; i < n_align; i += G) {
+        const double rx = ref64[3 * i], ry = ref64[3 * i + 1], rz = ref64[3 * i + 2];
+        const V3d p = load_atom_f64(xf, align_idx[i]) - c;
+        g = fma(p.x, p.x, fma(p.y, p.y, fma(p.z, p.z, g)));
+        h[0] = fma(p.x, rx, h[0]); h[1] = fma(p.x, ry, h[1]); h[2] = fma(p.x, rz, h[2]);
+        h[3] = fma(p.y, rx, h[3]); h[4] = fma(p.y, ry, h[4]); h[5] = fma(p.y, rz, h[5]);
+        h[6] = fma(p.z, rx, h[6]); h[7] = fma(p.z, ry, h[7]); h[8] = fma(p.z, rz, h[8]);
+    }
+    g = group_sum<G>(g);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) h[i] = group_sum<G>(h[i]);
+    kabsch_rotation_t<double, double>(h, 0.5 * (g + ref64[3 * n_align + 3]) * 1.0001, R);
+}
+
+// ---- 2. features (lanes over the items) into fdst: the frame's LDS row, or y where the plan has no head
+template <int G>
+__device__ __forceinline__ void frame_features_f64(const double* __restrict__ xf, const ItemDev* __restrict__ items, int n_items, int gl,
+                                                   bool has_align, V3d c, const double (&R)[9], double* fdst) {
+    for (int it = gl; it < n_items; it += G) {
+        const ItemDev d = items[it];
+        V3d p0 = load_atom_f64(xf, d.idx[0]), p1 = load_atom_f64(xf, d.idx[1]), p2 = load_atom_f64(xf, d.idx[2]), p3 = load_atom_f64(xf, d.idx[3]);
+        if (has_align) { p0 = rotate(p0 - c, R); p1 = rotate(p1 - c, R); p2 = rotate(p2 - c, R); p3 = rotate(p3 - c, R); }
+        double v[3];
+        const int w = eval_item_f64(d.type, p0, p1, p2, p3, v);
+        fdst[d.col] = v[0];
+        if (w > 1) fdst[d.col + 1] = v[1];
+        if (w > 2) fdst[d.col + 2] = v[2];
+    }
+}
+
+// ---- 3. head forward: the hidden layers' pre-activations go to zrows, the last layer to of; returns the end of the pre-activations
+template <int G>
+__device__ __forceinline__ double* frame_head_forward_f64(const F64Mlp& m, int gl, const double* feat, double* zrows, double* row0, double* row1,
+                                                          double* of) {
+    const double* cur = feat;
+    double* nxt = row0;
+    double* zl = zrows;
+    for (int l = 0; l < m.n_layers; ++l) {
+        const int K = m.dims[l], J = m.dims[l + 1];
+        const bool last = l + 1 == m.n_layers;
+        const double* Wl = m.W[l];
+        const double* bl = m.b[l];
+        for (int j = gl; j < J; j += G) {
+            const double* w = Wl + (long)j * K;
+            double acc = bl[j];
+            for (int k = 0; k < K; ++k) acc = fma(w[k], cur[k], acc);
+            if (last) of[j] = acc;
+            else { zl[j] = acc; nxt[j] = apply_activation_f64(m.act, acc); }
+        }
+        lds_wave_sync();
+        if (!last) zl += J;
+        cur = nxt;
+        nxt = nxt == row0 ? row1 : row0;
+    }
+    return zl;
+}
+
 template <int G>
 __global__ __launch_bounds__(256) void frames_value_vjp_f64_kernel(const double* __restrict__ x, const double* __restrict__ gout,
                                                                    double* __restrict__ out, double* __restrict__ gx,
@@ -76,65 +145,18 @@ __global__ __launch_bounds__(256) void frames_value_vjp_f64_kernel(const double*
         double* gxf = gx + f * frame_dw;
         const double* gf = gout + f * (long)a.d_out;
         double* of = out + f * (long)a.d_out;
-        // ---- 1. centroid, covariance, rotation (frames_f64_kernel's formulas)
+        // ---- 1. centroid, covariance, rotation
         double R[9] = {1., 0., 0., 0., 1., 0., 0., 0., 1.};
         double h[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
         V3d c = v3d(0., 0., 0.);
-        if (has_align) {
-            double sx = 0., sy = 0., sz = 0.;
-            for (int i = gl; i < a.n_align; i += G) { const V3d p = load_atom_f64(xf, align_idx[i]); sx += p.x; sy += p.y; sz += p.z; }
-            const double inv_a = 1.0 / (double)a.n_align;
-            c = v3d(group_sum<G>(sx) * inv_a, group_sum<G>(sy) * inv_a, group_sum<G>(sz) * inv_a);
-            double g = 0.;
-            for (int i = gl; i < a.n_align; i += G) {
-                const double rx = ref64[3 * i], ry = ref64[3 * i + 1], rz = ref64[3 * i + 2];
-                const V3d p = load_atom_f64(xf, align_idx[i]) - c;
-                g = fma(p.x, p.x, fma(p.y, p.y, fma(p.z, p.z, g)));
-                h[0] = fma(p.x, rx, h[0]); h[1] = fma(p.x, ry, h[1]); h[2] = fma(p.x, rz, h[2]);
-                h[3] = fma(p.y, rx, h[3]); h[4] = fma(p.y, ry, h[4]); h[5] = fma(p.y, rz, h[5]);
-                h[6] = fma(p.z, rx, h[6]); h[7] = fma(p.z, ry, h[7]); h[8] = fma(p.z, rz, h[8]);
-            }
-            g = group_sum<G>(g);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) h[i] = group_sum<G>(h[i]);
-            kabsch_rotation_t<double, double>(h, 0.5 * (g + ref64[3 * a.n_align + 3]) * 1.0001, R);
-        }
+        if (has_align) frame_rotation_f64<G>(xf, align_idx, ref64, a.n_align, gl, c, h, R);
         // ---- 2. features
-        double* fdst = has_head ? feat : of;
-        for (int it = gl; it < a.n_items; it += G) {
-            const ItemDev d = items[it];
-            V3d p0 = load_atom_f64(xf, d.idx[0]), p1 = load_atom_f64(xf, d.idx[1]), p2 = load_atom_f64(xf, d.idx[2]), p3 = load_atom_f64(xf, d.idx[3]);
-            if (has_align) { p0 = rotate(p0 - c, R); p1 = rotate(p1 - c, R); p2 = rotate(p2 - c, R); p3 = rotate(p3 - c, R); }
-            double v[3];
-            const int w = eval_item_f64(d.type, p0, p1, p2, p3, v);
-            fdst[d.col] = v[0];
-            if (w > 1) fdst[d.col + 1] = v[1];
-            if (w > 2) fdst[d.col + 2] = v[2];
-        }
+        frame_features_f64<G>(xf, items, a.n_items, gl, has_align, c, R, has_head ? feat : of);
         const double* df = gf;     // dL/dfeat: the cotangent itself without a head
         if (has_head) {
             lds_wave_sync();
             // ---- 3. head forward
-            const double* cur = feat;
-            double* nxt = row0;
-            double* zl = zrows;
-            for (int l = 0; l < m.n_layers; ++l) {
-                const int K = m.dims[l], J = m.dims[l + 1];
-                const bool last = l + 1 == m.n_layers;
-                const double* Wl = m.W[l];
-                const double* bl = m.b[l];
-                for (int j = gl; j < J; j += G) {
-                    const double* w = Wl + (long)j * K;
-                    double acc = bl[j];
-                    for (int k = 0; k < K; ++k) acc = fma(w[k], cur[k], acc);
-                    if (last) of[j] = acc;
-                    else { zl[j] = acc; nxt[j] = apply_activation_f64(m.act, acc); }
-                }
-                lds_wave_sync();
-                if (!last) zl += J;
-                cur = nxt;
-                nxt = nxt == row0 ? row1 : row0;
-            }
+            double* zl = frame_head_forward_f64<G>(m, gl, feat, zrows, row0, row1, of);
             // ---- 4. head backward: zl is past the last hidden layer's pre-activations
             const double* g = gf;
             double* gn = row0;

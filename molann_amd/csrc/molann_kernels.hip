@@ -60,6 +60,7 @@ using namespace molann;
 #include "molann_dev_jvp.inc"
 #include "molann_dev_hvp.inc"
 #include "molann_dev_vjp_f64.inc"
+#include "molann_dev_jac_f64.inc"
 // Host code (what `make san` instruments: -fno-gpu-sanitize leaves the device code alone):
 #include "molann_host_plan.inc"
 #include "molann_host_jit.inc"
@@ -69,3 +70,4 @@ using namespace molann;
 #include "molann_jvp.inc"
 #include "molann_hvp.inc"
 #include "molann_vjp_f64.inc"
+#include "molann_jac_f64.inc"

@@ -560,6 +560,57 @@ MOLANN_HD void kabsch_rotation_backward(const double (&H)[9], const float (&R)[9
     kabsch_rotation_backward_t<double>(H, R, GR, GH);
 }
 
+// kabsch_rotation_backward_t in two parts, for a caller with several G_R on one rotation (a Jacobian: one G_R per output).
+// _solve_t inverts B = tr(S) I - S once: Binv = the six entries of B's adjugate (00, 01, 02, 11, 12, 22) and 1 / det (0 where the
+// rotation is ill-defined).  _apply_t is the part that is linear in G_R: n = adj(B) vee(M - M^T) / det, G_H = R [n]x.  The same
+// operations in the same order as kabsch_rotation_backward_t, so solve + apply gives that function's bits.
+template <typename T, typename RT = float>
+MOLANN_HD void kabsch_rotation_backward_solve_t(const T (&H)[9], const RT (&R)[9], T (&Binv)[7]) {
+    T S[9];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            T s = (T)0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s = tfma((T)R[3 * k + a], H[3 * k + b], s);
+            S[3 * a + b] = s;
+        }
+    const T s01 = (T)0.5 * (S[1] + S[3]), s02 = (T)0.5 * (S[2] + S[6]), s12 = (T)0.5 * (S[5] + S[7]);
+    const T tr = S[0] + S[4] + S[8];
+    const T b00 = tr - S[0], b11 = tr - S[4], b22 = tr - S[8], b01 = -s01, b02 = -s02, b12 = -s12;
+    const T c00 = b11 * b22 - b12 * b12, c01 = b02 * b12 - b01 * b22, c02 = b01 * b12 - b02 * b11;
+    const T c11 = b00 * b22 - b02 * b02, c12 = b01 * b02 - b00 * b12, c22 = b00 * b11 - b01 * b01;
+    const T det = b00 * c00 + b01 * c01 + b02 * c02;
+    constexpr T tiny = sizeof(T) == 8 ? (T)1e-300 : (T)1e-30;
+    Binv[0] = c00; Binv[1] = c01; Binv[2] = c02; Binv[3] = c11; Binv[4] = c12; Binv[5] = c22;
+    Binv[6] = (det > tiny || det < -tiny) ? (T)1 / det : (T)0;
+}
+template <typename T, typename RT = float>
+MOLANN_HD void kabsch_rotation_backward_apply_t(const RT (&R)[9], const T (&Binv)[7], const RT (&GR)[9], RT (&GH)[9]) {
+    T M[9];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            T m = (T)0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) m = tfma((T)R[3 * k + a], (T)GR[3 * k + b], m);
+            M[3 * a + b] = m;
+        }
+    const T m0 = M[7] - M[5], m1 = M[2] - M[6], m2 = M[3] - M[1];
+    const T n0 = (Binv[0] * m0 + Binv[1] * m1 + Binv[2] * m2) * Binv[6];
+    const T n1 = (Binv[1] * m0 + Binv[3] * m1 + Binv[4] * m2) * Binv[6];
+    const T n2 = (Binv[2] * m0 + Binv[4] * m1 + Binv[5] * m2) * Binv[6];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const T r0 = R[3 * a], r1 = R[3 * a + 1], r2 = R[3 * a + 2];
+        GH[3 * a + 0] = (RT)(r1 * n2 - r2 * n1);
+        GH[3 * a + 1] = (RT)(r2 * n0 - r0 * n2);
+        GH[3 * a + 2] = (RT)(r0 * n1 - r1 * n0);
+    }
+}
+
 // ---- float64 reverse mode of the feature items (the reference differentiates its float64 forward with autograd too) ----
 MOLANN_HD V3d operator+(V3d a, V3d b) { return v3d(a.x + b.x, a.y + b.y, a.z + b.z); }
 MOLANN_HD V3d operator*(double s, V3d a) { return v3d(s * a.x, s * a.y, s * a.z); }
@@ -629,6 +680,16 @@ MOLANN_HD void eval_item_backward_f64(int type, V3d a0, V3d a1, V3d a2, V3d a3, 
         ga0 = ga0 + v3d(g[0], g[1], g[2]);
         return;
     }
+}
+
+// One row of an item's local Jacobian: u[j] = d(output column c of the item) / d(atom j), eval_item_backward_f64 under the unit
+// cotangent e_c.  Everything behind the item is linear in the cotangent, so a Jacobian evaluates this once per column of the
+// item (at most 3) and combines the rows with d y_k / d feat[col + c] for every output k.
+MOLANN_HD void item_unit_backward_f64(int type, V3d a0, V3d a1, V3d a2, V3d a3, int c, V3d (&u)[4]) {
+    const double e[3] = {c == 0 ? 1.0 : 0.0, c == 1 ? 1.0 : 0.0, c == 2 ? 1.0 : 0.0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) u[j] = v3d(0., 0., 0.);
+    eval_item_backward_f64(type, a0, a1, a2, a3, e, u[0], u[1], u[2], u[3]);
 }
 
 // =================================================================================================

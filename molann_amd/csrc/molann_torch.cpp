@@ -448,6 +448,71 @@ std::vector<at::Tensor> value_and_vjp_impl(const at::Tensor& x_in, const std::ve
     return {out, gx};
 }
 
+// {out, jac}: the float64 forward's outputs and the full Jacobian jac[N, out_dim, n_inp, 3] = d out / d x in ONE launch
+// (molann_value_and_jacobian_f64 on the float64 Linear tensors).  Parameters are data.  `into` as value_and_vjp's: {out, jac}.
+std::vector<at::Tensor> value_and_jacobian_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                                const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                                                const std::vector<at::Tensor>& into) {
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_jacobian is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_jacobian: a forward or a features description");
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    TORCH_CHECK(into.empty() || into.size() == 2, "molann::value_and_jacobian: `into` must be a pair of tensors (out, jac)");
+    at::Tensor out, jac;
+    if (into.size() == 2) {
+        out = into[0]; jac = into[1];
+        TORCH_CHECK_TYPE(out.scalar_type() == at::kDouble && jac.scalar_type() == at::kDouble, "molann::value_and_jacobian: `into` must be float64 like x");
+        TORCH_CHECK_VALUE(out.is_contiguous() && jac.is_contiguous() && out.numel() == n * cols && jac.numel() == cols * x.numel() &&
+                              out.device() == x.device() && jac.device() == x.device(),
+                          "molann::value_and_jacobian: `into` must be contiguous {[N, out_dim], [N, out_dim, n_inp, 3]} on x's device");
+    } else {
+        out = at::empty({n, cols}, x.options());
+        jac = at::empty({n, cols, x.size(1), 3}, x.options());
+    }
+    std::vector<at::Tensor> hold;
+    std::vector<const double*> W, B;
+    if (e->kind == KIND_FORWARD) {
+        TORCH_CHECK((int)weights.size() == e->n_layers && (int)biases.size() == e->n_layers, "molann::value_and_jacobian: expected ", e->n_layers,
+                    " weight and bias tensors");
+        for (int l = 0; l < e->n_layers; ++l) {
+            TORCH_CHECK(weights[l].scalar_type() == at::kDouble && biases[l].scalar_type() == at::kDouble && weights[l].device() == x.device() &&
+                            biases[l].device() == x.device(),
+                        "molann::value_and_jacobian: ann_layers must be float64 on ", x.device(), " for a float64 input: call .double()");
+            hold.push_back(weights[l].detach().contiguous()); W.push_back(hold.back().data_ptr<double>());
+            hold.push_back(biases[l].detach().contiguous()); B.push_back(hold.back().data_ptr<double>());
+        }
+    }
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_jacobian_f64(e->plan) == 1,
+                                "molann::value_and_jacobian: one frame's rows exceed the LDS of a compute unit for this model; use value_and_vjp "
+                                "on x.expand(d_out, ...) with torch.eye(d_out) as cotangent");
+    if (n == 0) return {out, jac};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_jacobian_f64(e->plan, x.data_ptr<double>(), n, W.data(), B.data(), out.data_ptr<double>(), jac.data_ptr<double>(), stream),
+          "molann_value_and_jacobian_f64");
+    return {out, jac};
+}
+std::vector<at::Tensor> value_and_jacobian_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                               std::vector<at::Tensor> biases, std::vector<at::Tensor> into) {
+    return value_and_jacobian_impl(x_in, desc, ref_x, weights, biases, into);
+}
+std::vector<at::Tensor> value_and_jacobian_h_hip(const at::Tensor& x_in, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                                 std::vector<at::Tensor> biases, std::vector<at::Tensor> into) {
+    std::shared_ptr<const std::vector<int64_t>> d;
+    {
+        std::lock_guard<std::mutex> lock(g_handle_mu);
+        TORCH_CHECK(handle >= 0 && (size_t)handle < g_handles.size(), "molann::value_and_jacobian_h: unknown handle ", handle);
+        d = g_handles[(size_t)handle];
+    }
+    return value_and_jacobian_impl(x_in, *d, ref_x, weights, biases, into);
+}
+
 // The fused forward that also keeps the features: {out, features} - or {out, empty} where the plan has no such twin of its
 // kernel (molann_plan_backward_kind != 1 ... != 2 plans recompute in molann_backward_f32).  float32 fused plans.
 std::vector<at::Tensor> run_train_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -1068,6 +1133,8 @@ TORCH_LIBRARY(molann, m) {
     m.def("run_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases) -> Tensor");
     m.def("value_and_vjp_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor grad_out, Tensor[] into) -> Tensor[]");
     m.def("value_and_vjp(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor grad_out, Tensor[] into) -> Tensor[]");
+    m.def("value_and_jacobian_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor[] into) -> Tensor[]");
+    m.def("value_and_jacobian(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor[] into) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
     m.def("run_head(Tensor feat, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases) -> Tensor", run_head);
@@ -1089,6 +1156,8 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_vjp", value_and_vjp_hip);
     m.impl("run_h", run_h_hip);
     m.impl("value_and_vjp_h", value_and_vjp_h_hip);
+    m.impl("value_and_jacobian", value_and_jacobian_hip);
+    m.impl("value_and_jacobian_h", value_and_jacobian_h_hip);
 }
 
 TORCH_LIBRARY_IMPL(molann, Autograd, m) { m.impl("run", run_autograd); }

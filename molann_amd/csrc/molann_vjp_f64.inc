@@ -27,9 +27,8 @@ inline void vjp64_rows(const molann_plan* p, int& max_w, int& per_frame) {
 
 // lanes per frame: the smallest group that covers the atoms, the items, the align atoms and the head's widest layer in one round
 // (8/4/2 frames per wave), a whole wave from 33 on; fewer waves per block, then one wave per frame, where the rows ask for it
-inline Vjp64Geom vjp64_geometry(const molann_plan* p) {
-    int max_w, per_frame;
-    vjp64_rows(p, max_w, per_frame);
+// (the rows are the caller's: molann_jac_f64.inc sizes its own and steps down the same way)
+inline Vjp64Geom vjp64_geometry_rows(const molann_plan* p, int max_w, int per_frame) {
     int work = std::max(std::max(p->n_inp, p->n_items), std::max(p->n_align, max_w));
     for (int l = 1; l <= p->n_layers; ++l) work = std::max(work, p->dims[l]);
     Vjp64Geom g;
@@ -42,6 +41,11 @@ inline Vjp64Geom vjp64_geometry(const molann_plan* p) {
     g.block = 64 * waves;
     g.lds = (size_t)(g.block / g.G) * bytes;
     return g;
+}
+inline Vjp64Geom vjp64_geometry(const molann_plan* p) {
+    int max_w, per_frame;
+    vjp64_rows(p, max_w, per_frame);
+    return vjp64_geometry_rows(p, max_w, per_frame);
 }
 
 template <int G>
