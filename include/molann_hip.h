@@ -292,6 +292,24 @@ int molann_value_and_jacobian_f64(molann_plan* plan, const double* x, int64_t n_
 /* 1 when molann_value_and_jacobian_f64 serves the plan (feature items, and a frame's rows fit the LDS), 0 otherwise. */
 int molann_plan_supports_value_and_jacobian_f64(const molann_plan* plan);
 
+/* Values AND the metric tensor of a float64 model in ONE launch of frames_value_metric_f64_kernel (ahead of time: no hipRTC):
+ * out[N, out_dim] = molann_value_and_jacobian_f64's out, bit for bit, and metric[N, out_dim, out_dim] with
+ *   metric[f, k, l] = sum_a atom_w[a] * (d out[f, k] / d x[f, a]) . (d out[f, l] / d x[f, a])
+ * (out_dim = feature_dim for a plan without an MLP), everything in double: the Jacobian contracted with itself over the atoms in
+ * the wave that computes it, never stored.  atom_w: n_inp doubles on the device (inverse masses, diffusion coefficients; any sign),
+ * or NULL for all ones - the same bits as an array of ones.  W, b as molann_value_and_jacobian_f64 takes them.  Parameters are
+ * data.  On a plan without an MLP the metric G of the features holds no parameter, and for any head behind it
+ * sum_a w_a |grad_a y_k|^2 = dF_k G dF_k^T with dF = d y / d features.  The terms are summed in a fixed order and metric[f, k, l] and
+ * metric[f, l, k] are stored from one value: no atomics, the same bits on every run, symmetric bit for bit.  MOLANN_E_STAGE for a
+ * plan without items, MOLANN_E_UNSUPPORTED where molann_value_and_jacobian_f64 refuses the plan or out_dim > 64.  n_frames < 0:
+ * MOLANN_E_DESC; n_frames == 0: nothing is read or launched.  All pointers 8-byte aligned, contiguous.  The call only enqueues on
+ * `stream` (no workspace, no event): thread-safe and capturable. */
+int molann_value_and_metric_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                                const double* atom_w, double* out, double* metric, molann_stream_t stream);
+
+/* 1 when molann_value_and_metric_f64 serves the plan (molann_value_and_jacobian_f64 serves it and out_dim <= 64), 0 otherwise. */
+int molann_plan_supports_value_and_metric_f64(const molann_plan* plan);
+
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
  * is fused into the lane kernel, and large-frame plans with a head within the fused MLP's limits (the features are written

@@ -105,6 +105,8 @@ def lib():
             "molann_plan_supports_value_and_vjp_f64": (i32, [vp]),
             "molann_value_and_jacobian_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp]),
             "molann_plan_supports_value_and_jacobian_f64": (i32, [vp]),
+            "molann_value_and_metric_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp, vp]),
+            "molann_plan_supports_value_and_metric_f64": (i32, [vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -382,6 +384,25 @@ class Plan(object):
         if code != 0:
             raise MolannHipError(code, "molann_value_and_jacobian_f64")
         return out, jac
+
+    def supports_value_and_metric_f64(self):
+        """True when `value_and_metric_f64` serves this plan: `value_and_jacobian_f64` serves it and it has at most 64 outputs
+        (nothing is built)."""
+        return lib().molann_plan_supports_value_and_metric_f64(self._handle) == 1
+
+    def value_and_metric_f64(self, x, weights, biases, atom_weights, out, metric):
+        """out[N, d_out] and metric[N, d_out, d_out] = sum_a w_a (d out_k / d x_a) . (d out_l / d x_a) in float64, one launch of
+        frames_value_metric_f64_kernel: `weights` / `biases` are the float64 Linear tensors on x's device, read as they are (empty
+        lists for a plan without a head); `atom_weights` holds the n_inp float64 values w_a on x's device, or is None for all ones."""
+        n = len(weights)
+        W = (ctypes.c_void_p * max(1, n))(*[w.data_ptr() for w in weights])
+        B = (ctypes.c_void_p * max(1, n))(*[b.data_ptr() for b in biases])
+        code = _lib.molann_value_and_metric_f64(self._handle, x.data_ptr(), x.shape[0], W, B,
+                                                atom_weights.data_ptr() if atom_weights is not None else None, out.data_ptr(),
+                                                metric.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if code != 0:
+            raise MolannHipError(code, "molann_value_and_metric_f64")
+        return out, metric
 
     def forward_train(self, x, out, features):
         """`forward_packed` that also keeps the features (for `mlp_backward` + `features_backward`)."""

@@ -898,6 +898,34 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
     return out
 
 
+_METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
+
+
+def _check_metric_args(name, x, n_inp, out_dim, weights, into):
+    """The `weights` and `into` checks of value_and_metric (before any launch); returns (weights or None, y, M) with y, M None where
+    `into` is."""
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64:
+            raise TypeError("%s: `weights` must be None or a float64 tensor of %d values; got %s"
+                            % (name, n_inp, weights.dtype if isinstance(weights, torch.Tensor) else type(weights).__name__))
+        if weights.numel() != n_inp or weights.device != x.device:
+            raise ValueError("%s: `weights` must hold %d values (one per atom) on %s; got %d on %s"
+                             % (name, n_inp, x.device, weights.numel(), weights.device))
+        weights = weights.detach().reshape(-1).contiguous()
+    y = M = None
+    if into is not None:
+        if len(into) != 2 or not all(isinstance(t, torch.Tensor) for t in into):
+            raise TypeError("%s: `into` must be a pair of tensors (y, M)" % name)
+        y, M = into
+        if y.dtype != torch.float64 or M.dtype != torch.float64:
+            raise TypeError("%s: `into` must be float64 like x; got %s, %s" % (name, y.dtype, M.dtype))
+        n = x.shape[0]
+        if not (y.is_contiguous() and M.is_contiguous()) or y.numel() != n * out_dim or M.numel() != n * out_dim * out_dim \
+                or y.device != x.device or M.device != x.device:
+            raise ValueError("%s: `into` must be contiguous {[%d, %d], [%d, %d, %d]} on %s" % (name, n, out_dim, n, out_dim, out_dim, x.device))
+    return weights, y, M
+
+
 class PreprocessingANN(_PlanOwner, torch.nn.Module):
     """``feature_layer(align_layer(x))``; ``align_layer=None`` means no alignment (`ann.py:533-565`)."""
 
@@ -923,6 +951,52 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
                 f'Input should be a 3d torch tensor, with sizes [*, {self.feature_layer.input_atom_num}, 3]. Actual sizes: {x.shape}'
         _check_input(x, self.feature_layer.input_atom_num)
         return _run_features(self.feature_layer, x, al, plan_owner=self)
+
+    def value_and_metric(self, x, weights=None, into=None):
+        """``(feat, G)`` with ``feat = self(x)`` [N, d_feat] and the metric tensor of the features
+        ``G[f, k, l] = sum_a w_a grad_a feat_k(x_f) . grad_a feat_l(x_f)`` [N, d_feat, d_feat], float64, in ONE kernel launch
+        (`molann_value_and_metric_f64`, frames_value_metric_f64_kernel, on this module's float64 feature plan): the Jacobian
+        contracted with itself over the atoms where it is computed, never stored.  ``weights``: None (all ones) or a float64 tensor of
+        n_inp values on x's device (inverse masses, diffusion coefficients; any sign).  G holds no parameter: for any head behind
+        these features ``sum_a w_a |grad_a y_k|^2 = dF_k G dF_k^T`` with ``dF = d y / d feat``, so a loss built from gradient norms
+        needs G once per dataset and no second-order pass through the preprocessing.  No autograd graph is recorded;
+        ``into=(feat, G)`` reuses the caller's buffers.  The same bits on every call, G symmetric bit for bit; ``weights=None`` gives
+        the bits of ``torch.ones``."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and self._fusable()):
+            raise NotImplementedError("value_and_metric needs a FeatureLayer behind an AlignmentLayer or none, float64, on a HIP tensor; "
+                                      "otherwise " + _METRIC_ROUTE)
+        fl = self.feature_layer
+        al = self.align_layer if isinstance(self.align_layer, AlignmentLayer) else None
+        _check_input(x, fl.input_atom_num)
+        if x.dtype != torch.float64:
+            raise TypeError("value_and_metric is float64: call .double() and pass a float64 x (got %s); for float32 %s" % (x.dtype, _METRIC_ROUTE))
+        if al is not None and (al.ref_x.dtype != torch.float64 or al.ref_x.device != x.device):
+            raise RuntimeError("the alignment layer's ref_x must be float64 on %s for a float64 input (got %s on %s): call .double()"
+                               % (x.device, al.ref_x.dtype, al.ref_x.device))
+        x = x.detach()
+        x = x if x.is_contiguous() else x.contiguous()
+        n, d = x.shape[0], fl.output_dimension()
+        weights, y, M = _check_metric_args("value_and_metric", x, fl.input_atom_num, d, weights, into)
+        spec, uav = _feature_spec(fl)
+
+        def build():
+            if al is None:
+                return _capi.Plan(fl.input_atom_num, features=spec, use_angle_value=uav)
+            return _capi.Plan(fl.input_atom_num, align_idx=al._local_align_atom_indices, ref_x=al.ref_x, features=spec, use_angle_value=uav)
+
+        entry = _get_entry(self, x, "features", build)
+        with torch.cuda.device(x.device):
+            if not entry.plan.supports_value_and_metric_f64():
+                raise NotImplementedError("value_and_metric: no single-launch kernel for this module (more than 64 features, or one "
+                                          "frame's rows exceed the LDS of a compute unit); " + _METRIC_ROUTE)
+            if al is not None:
+                entry.sync_ref(_device_buffer(al.ref_x, x))
+            if into is None:
+                y = torch.empty((n, d), dtype=torch.float64, device=x.device)
+                M = torch.empty((n, d, d), dtype=torch.float64, device=x.device)
+            if n > 0:
+                entry.plan.value_and_metric_f64(x, [], [], weights, y, M)
+        return y, M
 
     def __prepare_scriptable__(self):
         if not self._fusable():
@@ -1134,6 +1208,56 @@ class MolANN(_PlanOwner, torch.nn.Module):
                 entry.plan.value_and_jacobian_f64(x, [lin.weight.detach().contiguous() for lin in lins],
                                                   [lin.bias.detach().contiguous() for lin in lins], y, jac)
         return y, jac
+
+    def value_and_metric(self, x, weights=None, into=None):
+        """``(y, M)`` with ``y = self(x)`` [N, d_out] and the metric tensor of the outputs
+        ``M[f, k, l] = sum_a w_a grad_a y_k(x_f) . grad_a y_l(x_f)`` [N, d_out, d_out], float64, in ONE kernel launch
+        (`molann_value_and_metric_f64`, frames_value_metric_f64_kernel): `value_and_jacobian`'s Jacobian contracted with itself over
+        the atoms in the wave that computes it, never stored - with inverse masses the metric of the string method, of
+        temperature-accelerated MD and of effective dynamics along a collective variable; its diagonal is ``|grad y_k|^2``.
+        ``weights``: None (all ones) or a float64 tensor of n_inp values on x's device, any sign.  ``y`` is `value_and_jacobian`'s, bit
+        for bit.  No autograd graph is recorded (parameters are data); ``into=(y, M)`` reuses the caller's buffers.  The terms are
+        summed in a fixed order and M[f, k, l], M[f, l, k] are stored from one value: the same bits on every call, M symmetric bit for
+        bit, ``weights=None`` the bits of ``torch.ones``.  With G the same quantity of the features
+        (`PreprocessingANN.value_and_metric`), ``sum_a w_a |grad_a y_k|^2 = dF_k G dF_k^T``, ``dF = d y / d feat``.
+        `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at most 64 outputs."""
+        route = _METRIC_ROUTE
+        st = self._fast_state(x) if isinstance(x, torch.Tensor) and x.is_cuda else None
+        if st is None or not st["fused"]:
+            raise NotImplementedError("value_and_metric needs a model served by one fused plan on a HIP device (a feature layer and a "
+                                      "Linear / activation head, float64, on a HIP tensor); otherwise " + route)
+        al, fl, lins = st["al"], st["fl"], st["linears"]
+        _check_input(x, fl.input_atom_num)
+        if x.dtype != torch.float64:
+            raise TypeError("value_and_metric is float64: call model.double() and pass a float64 x (got %s); for float32 %s"
+                            % (x.dtype, route))
+        w0 = lins[0].weight
+        if w0.device != x.device or w0.dtype != torch.float64:
+            raise RuntimeError("ann_layers must be float64 on %s for a float64 input (got %s on %s): call .double()"
+                               % (x.device, w0.dtype, w0.device))
+        x = x.detach()
+        x = x if x.is_contiguous() else x.contiguous()
+        n, out_dim = x.shape[0], st["out_dim"]
+        weights, y, M = _check_metric_args("value_and_metric", x, fl.input_atom_num, out_dim, weights, into)
+        if st["op"] is not None:
+            y, M = torch.ops.molann.value_and_metric_h(x, st["handle"], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"],
+                                                       [lin.weight for lin in lins], [lin.bias for lin in lins], weights,
+                                                       list(into) if into is not None else [])
+            return y, M
+        entry = st["entry"]()
+        with torch.cuda.device(x.device):
+            if not entry.plan.supports_value_and_metric_f64():
+                raise NotImplementedError("value_and_metric: no single-launch kernel for this model (more than 64 outputs, or one frame's "
+                                          "rows exceed the LDS of a compute unit); " + route)
+            if al is not None:
+                entry.sync_ref(_device_buffer(al.ref_x, x))
+            if into is None:
+                y = torch.empty((n, out_dim), dtype=torch.float64, device=x.device)
+                M = torch.empty((n, out_dim, out_dim), dtype=torch.float64, device=x.device)
+            if n > 0:
+                entry.plan.value_and_metric_f64(x, [lin.weight.detach().contiguous() for lin in lins],
+                                                [lin.bias.detach().contiguous() for lin in lins], weights, y, M)
+        return y, M
 
     def _tangent_present(self, x):
         if _has_tangent(x):

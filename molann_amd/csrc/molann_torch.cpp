@@ -513,6 +513,76 @@ std::vector<at::Tensor> value_and_jacobian_h_hip(const at::Tensor& x_in, int64_t
     return value_and_jacobian_impl(x_in, *d, ref_x, weights, biases, into);
 }
 
+// {out, metric}: the float64 forward's outputs and the metric tensor metric[N, out_dim, out_dim] = sum_a atom_w[a] (d out_k / d x_a) .
+// (d out_l / d x_a) in ONE launch (molann_value_and_metric_f64 on the float64 Linear tensors).  Parameters are data.  atom_w: n_inp
+// float64 values on x's device, or none for all ones.  `into` as value_and_jacobian's: {out, metric}.
+std::vector<at::Tensor> value_and_metric_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                              const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                                              const c10::optional<at::Tensor>& atom_w_in, const std::vector<at::Tensor>& into) {
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_metric is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_metric: a forward or a features description");
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    at::Tensor atom_w;
+    if (atom_w_in.has_value() && atom_w_in->defined()) {
+        TORCH_CHECK_TYPE(atom_w_in->scalar_type() == at::kDouble, "molann::value_and_metric: `weights` must be float64 (got ", atom_w_in->scalar_type(), ")");
+        TORCH_CHECK_VALUE(atom_w_in->numel() == x.size(1) && atom_w_in->device() == x.device(), "molann::value_and_metric: `weights` must hold ", x.size(1),
+                          " values (one per atom) on ", x.device());
+        atom_w = atom_w_in->detach().reshape({-1}).contiguous();
+    }
+    TORCH_CHECK(into.empty() || into.size() == 2, "molann::value_and_metric: `into` must be a pair of tensors (out, metric)");
+    at::Tensor out, metric;
+    if (into.size() == 2) {
+        out = into[0]; metric = into[1];
+        TORCH_CHECK_TYPE(out.scalar_type() == at::kDouble && metric.scalar_type() == at::kDouble, "molann::value_and_metric: `into` must be float64 like x");
+        TORCH_CHECK_VALUE(out.is_contiguous() && metric.is_contiguous() && out.numel() == n * cols && metric.numel() == n * cols * cols &&
+                              out.device() == x.device() && metric.device() == x.device(),
+                          "molann::value_and_metric: `into` must be contiguous {[N, out_dim], [N, out_dim, out_dim]} on x's device");
+    } else {
+        out = at::empty({n, cols}, x.options());
+        metric = at::empty({n, cols, cols}, x.options());
+    }
+    std::vector<at::Tensor> hold;
+    std::vector<const double*> W, B;
+    if (e->kind == KIND_FORWARD) {
+        TORCH_CHECK((int)weights.size() == e->n_layers && (int)biases.size() == e->n_layers, "molann::value_and_metric: expected ", e->n_layers,
+                    " weight and bias tensors");
+        for (int l = 0; l < e->n_layers; ++l) {
+            TORCH_CHECK(weights[l].scalar_type() == at::kDouble && biases[l].scalar_type() == at::kDouble && weights[l].device() == x.device() &&
+                            biases[l].device() == x.device(),
+                        "molann::value_and_metric: ann_layers must be float64 on ", x.device(), " for a float64 input: call .double()");
+            hold.push_back(weights[l].detach().contiguous()); W.push_back(hold.back().data_ptr<double>());
+            hold.push_back(biases[l].detach().contiguous()); B.push_back(hold.back().data_ptr<double>());
+        }
+    }
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_metric_f64(e->plan) == 1,
+                                "molann::value_and_metric: no single-launch kernel for this model (more than 64 outputs, or one frame's rows exceed "
+                                "the LDS of a compute unit); use value_and_jacobian and torch.einsum(\"fkai,a,flai->fkl\", jac, w, jac)");
+    if (n == 0) return {out, metric};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_metric_f64(e->plan, x.data_ptr<double>(), n, W.data(), B.data(), atom_w.defined() ? atom_w.data_ptr<double>() : nullptr,
+                                      out.data_ptr<double>(), metric.data_ptr<double>(), stream),
+          "molann_value_and_metric_f64");
+    return {out, metric};
+}
+std::vector<at::Tensor> value_and_metric_h_hip(const at::Tensor& x_in, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                               std::vector<at::Tensor> biases, const c10::optional<at::Tensor>& atom_w, std::vector<at::Tensor> into) {
+    std::shared_ptr<const std::vector<int64_t>> d;
+    {
+        std::lock_guard<std::mutex> lock(g_handle_mu);
+        TORCH_CHECK(handle >= 0 && (size_t)handle < g_handles.size(), "molann::value_and_metric_h: unknown handle ", handle);
+        d = g_handles[(size_t)handle];
+    }
+    return value_and_metric_impl(x_in, *d, ref_x, weights, biases, atom_w, into);
+}
+
 // The fused forward that also keeps the features: {out, features} - or {out, empty} where the plan has no such twin of its
 // kernel (molann_plan_backward_kind != 1 ... != 2 plans recompute in molann_backward_f32).  float32 fused plans.
 std::vector<at::Tensor> run_train_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -1135,6 +1205,7 @@ TORCH_LIBRARY(molann, m) {
     m.def("value_and_vjp(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor grad_out, Tensor[] into) -> Tensor[]");
     m.def("value_and_jacobian_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor[] into) -> Tensor[]");
     m.def("value_and_jacobian(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor[] into) -> Tensor[]");
+    m.def("value_and_metric_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? atom_w, Tensor[] into) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
     m.def("run_head(Tensor feat, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases) -> Tensor", run_head);
@@ -1158,6 +1229,7 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_vjp_h", value_and_vjp_h_hip);
     m.impl("value_and_jacobian", value_and_jacobian_hip);
     m.impl("value_and_jacobian_h", value_and_jacobian_h_hip);
+    m.impl("value_and_metric_h", value_and_metric_h_hip);
 }
 
 TORCH_LIBRARY_IMPL(molann, Autograd, m) { m.impl("run", run_autograd); }
