@@ -168,6 +168,12 @@ def _i32_array(values):
     return arr
 
 
+def _layer_pointers(weights, biases):
+    """The Linear tensors as the two host arrays of device pointers the C ABI takes (one null entry each for no layers)."""
+    kind = ctypes.c_void_p * max(1, len(weights))
+    return kind(*[w.data_ptr() for w in weights]), kind(*[b.data_ptr() for b in biases])
+
+
 class Plan(object):
     """Owns one ``molann_plan``.  All index lists are positions inside the n_inp axis."""
 
@@ -246,9 +252,7 @@ class Plan(object):
         return self._run("molann_features_f64", x, out, x.shape[0])
 
     def forward_f64(self, x, weights, biases, work, out):
-        n = len(weights)
-        W = (ctypes.c_void_p * n)(*[w.data_ptr() for w in weights])
-        B = (ctypes.c_void_p * n)(*[b.data_ptr() for b in biases])
+        W, B = _layer_pointers(weights, biases)
         _check(lib().molann_forward_f64(self._handle, x.data_ptr(), x.shape[0], W, B, work.data_ptr(), out.data_ptr(),
                                         self._stream()), "molann_forward_f64")
         return out
@@ -286,16 +290,12 @@ class Plan(object):
             raise MolannHipError(code, "molann_features_hvp_f64")
 
     def mlp_f64(self, f, weights, biases, out):
-        n = len(weights)
-        W = (ctypes.c_void_p * n)(*[w.data_ptr() for w in weights])
-        B = (ctypes.c_void_p * n)(*[b.data_ptr() for b in biases])
+        W, B = _layer_pointers(weights, biases)
         _check(lib().molann_mlp_f64(self._handle, f.data_ptr(), f.shape[0], W, B, out.data_ptr(), self._stream()), "molann_mlp_f64")
         return out
 
     def update_mlp(self, weights, biases):
-        n = len(weights)
-        W = (ctypes.c_void_p * n)(*[w.data_ptr() for w in weights])
-        B = (ctypes.c_void_p * n)(*[b.data_ptr() for b in biases])
+        W, B = _layer_pointers(weights, biases)
         _check(lib().molann_plan_update_mlp(self._handle, W, B, self._stream()), "molann_plan_update_mlp")
 
     def _run(self, fn_name, x, out, n):
@@ -357,16 +357,17 @@ class Plan(object):
         """True when `value_and_vjp_f64` serves this plan: feature items, and a frame's rows fit the LDS (nothing is built)."""
         return lib().molann_plan_supports_value_and_vjp_f64(self._handle) == 1
 
+    def _launch(self, fn_name, *args):
+        """An entry point on this plan and the current stream, `args` between the two; a non-zero code raises."""
+        code = getattr(_lib, fn_name)(self._handle, *args, torch.cuda.current_stream().cuda_stream)
+        if code != 0:
+            raise MolannHipError(code, fn_name)
+
     def value_and_vjp_f64(self, x, grad_out, weights, biases, out, grad_x):
         """`value_and_vjp` in float64, one launch of frames_value_vjp_f64_kernel: `weights` / `biases` are the float64 Linear
         tensors on x's device, read as they are (empty lists for a plan without a head)."""
-        n = len(weights)
-        W = (ctypes.c_void_p * max(1, n))(*[w.data_ptr() for w in weights])
-        B = (ctypes.c_void_p * max(1, n))(*[b.data_ptr() for b in biases])
-        code = _lib.molann_value_and_vjp_f64(self._handle, x.data_ptr(), grad_out.data_ptr(), x.shape[0], W, B, out.data_ptr(),
-                                             grad_x.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if code != 0:
-            raise MolannHipError(code, "molann_value_and_vjp_f64")
+        W, B = _layer_pointers(weights, biases)
+        self._launch("molann_value_and_vjp_f64", x.data_ptr(), grad_out.data_ptr(), x.shape[0], W, B, out.data_ptr(), grad_x.data_ptr())
         return out, grad_x
 
     def supports_value_and_jacobian_f64(self):
@@ -376,13 +377,8 @@ class Plan(object):
     def value_and_jacobian_f64(self, x, weights, biases, out, jac):
         """out[N, d_out] and jac[N, d_out, n_inp, 3] = d out / d x in float64, one launch of frames_value_jac_f64_kernel: `weights` /
         `biases` are the float64 Linear tensors on x's device, read as they are (empty lists for a plan without a head)."""
-        n = len(weights)
-        W = (ctypes.c_void_p * max(1, n))(*[w.data_ptr() for w in weights])
-        B = (ctypes.c_void_p * max(1, n))(*[b.data_ptr() for b in biases])
-        code = _lib.molann_value_and_jacobian_f64(self._handle, x.data_ptr(), x.shape[0], W, B, out.data_ptr(), jac.data_ptr(),
-                                                  torch.cuda.current_stream().cuda_stream)
-        if code != 0:
-            raise MolannHipError(code, "molann_value_and_jacobian_f64")
+        W, B = _layer_pointers(weights, biases)
+        self._launch("molann_value_and_jacobian_f64", x.data_ptr(), x.shape[0], W, B, out.data_ptr(), jac.data_ptr())
         return out, jac
 
     def supports_value_and_metric_f64(self):
@@ -394,14 +390,9 @@ class Plan(object):
         """out[N, d_out] and metric[N, d_out, d_out] = sum_a w_a (d out_k / d x_a) . (d out_l / d x_a) in float64, one launch of
         frames_value_metric_f64_kernel: `weights` / `biases` are the float64 Linear tensors on x's device, read as they are (empty
         lists for a plan without a head); `atom_weights` holds the n_inp float64 values w_a on x's device, or is None for all ones."""
-        n = len(weights)
-        W = (ctypes.c_void_p * max(1, n))(*[w.data_ptr() for w in weights])
-        B = (ctypes.c_void_p * max(1, n))(*[b.data_ptr() for b in biases])
-        code = _lib.molann_value_and_metric_f64(self._handle, x.data_ptr(), x.shape[0], W, B,
-                                                atom_weights.data_ptr() if atom_weights is not None else None, out.data_ptr(),
-                                                metric.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if code != 0:
-            raise MolannHipError(code, "molann_value_and_metric_f64")
+        W, B = _layer_pointers(weights, biases)
+        self._launch("molann_value_and_metric_f64", x.data_ptr(), x.shape[0], W, B,
+                     atom_weights.data_ptr() if atom_weights is not None else None, out.data_ptr(), metric.data_ptr())
         return out, metric
 
     def forward_train(self, x, out, features):

@@ -21,6 +21,8 @@ kernels and runs ``ann_layers`` as the torch module it is.  Forward mode (``torc
 kernel (`_FeaturesJvp`, `_FeaturesTangent`), ``ann_layers`` as the torch module it is.
 """
 
+import math
+
 import torch
 import torch._C._functorch as _functorch
 import pandas as pd
@@ -898,32 +900,120 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
     return out
 
 
+# ---- The calls that give the values and a derivative in one launch: MolANN.value_and_vjp / value_and_jacobian / value_and_metric and
+# PreprocessingANN.value_and_metric.  What differs between them, by kind; the checks and the two ways to the kernel are written once below.
+_VJP, _JACOBIAN, _METRIC = 0, 1, 2
+_JACOBIAN_ROUTE = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
 _METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
+_ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric")
+_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE)       # the route that remains where the call refuses
+_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)")             # what `into` holds
+_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric")          # the dispatcher operator, in MolANN._fast_state
+
+
+def _check_into(name, x, into, dtype, out_dim, second_shape, pair):
+    """`into` of a one-launch call, before any launch: a pair of contiguous tensors of `dtype` on x's device that hold [N, out_dim]
+    and `second_shape`'s elements.  Returns the pair, (None, None) for None."""
+    if into is None:
+        return None, None
+    if len(into) != 2 or not all(isinstance(t, torch.Tensor) for t in into):
+        raise TypeError("%s: `into` must be a pair of tensors %s" % (name, pair))
+    y, second = into
+    if y.dtype != dtype or second.dtype != dtype:
+        raise TypeError("%s: `into` must be %s like x; got %s, %s" % (name, str(dtype)[6:], y.dtype, second.dtype))
+    if not (y.is_contiguous() and second.is_contiguous()) or y.numel() != x.shape[0] * out_dim or second.numel() != math.prod(second_shape) \
+            or y.device != x.device or second.device != x.device:
+        raise ValueError("%s: `into` must be contiguous {[%d, %d], %s} on %s" % (name, x.shape[0], out_dim, list(second_shape), x.device))
+    return y, second
+
+
+def _check_grad_out(name, x, out_dim, grad_out):
+    if not isinstance(grad_out, torch.Tensor) or grad_out.numel() != x.shape[0] * out_dim or grad_out.device != x.device:
+        raise ValueError("%s: grad_out must hold [%d, %d] values on %s" % (name, x.shape[0], out_dim, x.device))
+
+
+def _check_atom_weights(name, x, n_inp, weights):
+    """The atom weights of value_and_metric: None, or n_inp float64 values on x's device, returned flat and contiguous."""
+    if weights is None:
+        return None
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64:
+        raise TypeError("%s: `weights` must be None or a float64 tensor of %d values; got %s"
+                        % (name, n_inp, weights.dtype if isinstance(weights, torch.Tensor) else type(weights).__name__))
+    if weights.numel() != n_inp or weights.device != x.device:
+        raise ValueError("%s: `weights` must hold %d values (one per atom) on %s; got %d on %s"
+                         % (name, n_inp, x.device, weights.numel(), weights.device))
+    return weights.detach().reshape(-1).contiguous()
 
 
 def _check_metric_args(name, x, n_inp, out_dim, weights, into):
     """The `weights` and `into` checks of value_and_metric (before any launch); returns (weights or None, y, M) with y, M None where
     `into` is."""
-    if weights is not None:
-        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64:
-            raise TypeError("%s: `weights` must be None or a float64 tensor of %d values; got %s"
-                            % (name, n_inp, weights.dtype if isinstance(weights, torch.Tensor) else type(weights).__name__))
-        if weights.numel() != n_inp or weights.device != x.device:
-            raise ValueError("%s: `weights` must hold %d values (one per atom) on %s; got %d on %s"
-                             % (name, n_inp, x.device, weights.numel(), weights.device))
-        weights = weights.detach().reshape(-1).contiguous()
-    y = M = None
-    if into is not None:
-        if len(into) != 2 or not all(isinstance(t, torch.Tensor) for t in into):
-            raise TypeError("%s: `into` must be a pair of tensors (y, M)" % name)
-        y, M = into
-        if y.dtype != torch.float64 or M.dtype != torch.float64:
-            raise TypeError("%s: `into` must be float64 like x; got %s, %s" % (name, y.dtype, M.dtype))
-        n = x.shape[0]
-        if not (y.is_contiguous() and M.is_contiguous()) or y.numel() != n * out_dim or M.numel() != n * out_dim * out_dim \
-                or y.device != x.device or M.device != x.device:
-            raise ValueError("%s: `into` must be contiguous {[%d, %d], [%d, %d, %d]} on %s" % (name, n, out_dim, n, out_dim, out_dim, x.device))
-    return weights, y, M
+    weights = _check_atom_weights(name, x, n_inp, weights)
+    return (weights,) + _check_into(name, x, into, torch.float64, out_dim, (x.shape[0], out_dim, out_dim), _ONE_LAUNCH_PAIR[_METRIC])
+
+
+def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al):
+    """The float64 one-launch calls after the caller's gate (a HIP tensor, modules one plan serves), in this order: x's shape, float64
+    x, float64 head (the alignment's ref_x where there is no head) on x's device, x detached and contiguous, the extra argument
+    (`grad_out`, the metric's atom weights), `into`.  Returns (x, extra, y, second, second's shape), y and second None without `into`."""
+    name = _ONE_LAUNCH_NAME[kind]
+    _check_input(x, n_inp)
+    if x.dtype != torch.float64:
+        raise TypeError("%s is float64: call %s and pass a float64 x (got %s); for float32 %s"
+                        % (name, "model.double()" if lins else ".double()", x.dtype, _ONE_LAUNCH_ROUTE[kind]))
+    if lins:
+        w0 = lins[0].weight
+        if w0.device != x.device or w0.dtype != torch.float64:
+            raise RuntimeError("ann_layers must be float64 on %s for a float64 input (got %s on %s): call .double()"
+                               % (x.device, w0.dtype, w0.device))
+    elif al is not None and (al.ref_x.dtype != torch.float64 or al.ref_x.device != x.device):
+        raise RuntimeError("the alignment layer's ref_x must be float64 on %s for a float64 input (got %s on %s): call .double()"
+                           % (x.device, al.ref_x.dtype, al.ref_x.device))
+    x = x.detach()
+    x = x if x.is_contiguous() else x.contiguous()
+    n = x.shape[0]
+    if kind == _VJP:
+        shape = (n, n_inp, 3)
+        _check_grad_out(name, x, out_dim, extra)
+        if not extra.dtype.is_floating_point:
+            raise TypeError("%s: grad_out must be a floating-point tensor; got %s" % (name, extra.dtype))
+    elif kind == _JACOBIAN:
+        shape = (n, out_dim, n_inp, 3)
+    else:
+        shape = (n, out_dim, out_dim)
+        extra = _check_atom_weights(name, x, n_inp, extra)
+    y, second = _check_into(name, x, into, torch.float64, out_dim, shape, _ONE_LAUNCH_PAIR[kind])
+    if kind == _VJP and not (extra.dtype == torch.float64 and extra.is_contiguous()):
+        extra = extra.double().contiguous()
+    return x, extra, y, second, shape
+
+
+def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, al):
+    """The ctypes way to the kernel of a float64 one-launch call whose arguments `_one_launch_arguments` has checked."""
+    plan = entry.plan
+    with torch.cuda.device(x.device):
+        if kind != _VJP and not (plan.supports_value_and_jacobian_f64() if kind == _JACOBIAN else plan.supports_value_and_metric_f64()):
+            if kind == _JACOBIAN:
+                raise NotImplementedError("value_and_jacobian: one frame's rows exceed the LDS of a compute unit for this model; "
+                                          + _JACOBIAN_ROUTE)
+            raise NotImplementedError("value_and_metric: no single-launch kernel for this %s (more than 64 %s, or one frame's rows exceed "
+                                      "the LDS of a compute unit); " % (("model", "outputs") if lins else ("module", "features"))
+                                      + _METRIC_ROUTE)
+        if al is not None:
+            entry.sync_ref(_device_buffer(al.ref_x, x))
+        if y is None:
+            y = torch.empty((x.shape[0], out_dim), dtype=torch.float64, device=x.device)
+            second = torch.empty(shape, dtype=torch.float64, device=x.device)
+        if x.shape[0] > 0:
+            W = [lin.weight.detach().contiguous() for lin in lins]
+            B = [lin.bias.detach().contiguous() for lin in lins]
+            if kind == _VJP:
+                plan.value_and_vjp_f64(x, extra, W, B, y, second)
+            elif kind == _JACOBIAN:
+                plan.value_and_jacobian_f64(x, W, B, y, second)
+            else:
+                plan.value_and_metric_f64(x, W, B, extra, y, second)
+    return y, second
 
 
 class PreprocessingANN(_PlanOwner, torch.nn.Module):
@@ -967,16 +1057,8 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
                                       "otherwise " + _METRIC_ROUTE)
         fl = self.feature_layer
         al = self.align_layer if isinstance(self.align_layer, AlignmentLayer) else None
-        _check_input(x, fl.input_atom_num)
-        if x.dtype != torch.float64:
-            raise TypeError("value_and_metric is float64: call .double() and pass a float64 x (got %s); for float32 %s" % (x.dtype, _METRIC_ROUTE))
-        if al is not None and (al.ref_x.dtype != torch.float64 or al.ref_x.device != x.device):
-            raise RuntimeError("the alignment layer's ref_x must be float64 on %s for a float64 input (got %s on %s): call .double()"
-                               % (x.device, al.ref_x.dtype, al.ref_x.device))
-        x = x.detach()
-        x = x if x.is_contiguous() else x.contiguous()
-        n, d = x.shape[0], fl.output_dimension()
-        weights, y, M = _check_metric_args("value_and_metric", x, fl.input_atom_num, d, weights, into)
+        d = fl.output_dimension()
+        x, weights, y, M, shape = _one_launch_arguments(_METRIC, x, weights, into, fl.input_atom_num, d, (), al)
         spec, uav = _feature_spec(fl)
 
         def build():
@@ -984,19 +1066,7 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
                 return _capi.Plan(fl.input_atom_num, features=spec, use_angle_value=uav)
             return _capi.Plan(fl.input_atom_num, align_idx=al._local_align_atom_indices, ref_x=al.ref_x, features=spec, use_angle_value=uav)
 
-        entry = _get_entry(self, x, "features", build)
-        with torch.cuda.device(x.device):
-            if not entry.plan.supports_value_and_metric_f64():
-                raise NotImplementedError("value_and_metric: no single-launch kernel for this module (more than 64 features, or one "
-                                          "frame's rows exceed the LDS of a compute unit); " + _METRIC_ROUTE)
-            if al is not None:
-                entry.sync_ref(_device_buffer(al.ref_x, x))
-            if into is None:
-                y = torch.empty((n, d), dtype=torch.float64, device=x.device)
-                M = torch.empty((n, d, d), dtype=torch.float64, device=x.device)
-            if n > 0:
-                entry.plan.value_and_metric_f64(x, [], [], weights, y, M)
-        return y, M
+        return _one_launch_ctypes(_METRIC, _get_entry(self, x, "features", build), x, weights, y, M, shape, d, (), al)
 
     def __prepare_scriptable__(self):
         if not self._fusable():
@@ -1071,14 +1141,11 @@ class MolANN(_PlanOwner, torch.nn.Module):
         float64 (`model.double()` and a float64 x; `molann_value_and_vjp_f64`, one launch of frames_value_vjp_f64_kernel): every
         model served by one fused plan - any frame size, with or without an alignment, a head of any width with any of the
         nine activations.  Each row of dx is stored once, its terms summed in a fixed order: the same bits on every call."""
-        st = self._fast_state(x) if isinstance(x, torch.Tensor) and x.is_cuda else None
-        if st is None or not st["fused"]:
-            raise NotImplementedError("value_and_vjp needs a model served by one fused plan on a HIP device (a feature layer and a "
-                                      "Linear / activation head, float32 or float64, on a HIP tensor)")
+        st = self._one_launch_state(x, _VJP, "float32 or float64")
+        if x.dtype == torch.float64:
+            return self._one_launch_f64(_VJP, st, x, grad_out, into)
         al, fl = st["al"], st["fl"]
         _check_input(x, fl.input_atom_num)
-        if x.dtype == torch.float64:
-            return self._value_and_vjp_f64(st, x, grad_out, into)
         if x.dtype != torch.float32:
             raise TypeError("value_and_vjp is float32 / float64; got %s" % x.dtype)
         x = x.detach()
@@ -1089,17 +1156,8 @@ class MolANN(_PlanOwner, torch.nn.Module):
                                  [lin.weight for lin in lins], [lin.bias for lin in lins], grad_out, list(into) if into is not None else [])
             return y, dx
         n, out_dim = x.shape[0], st["out_dim"]
-        if not isinstance(grad_out, torch.Tensor) or grad_out.numel() != n * out_dim or grad_out.device != x.device:
-            raise ValueError("value_and_vjp: grad_out must hold [%d, %d] values on %s" % (n, out_dim, x.device))
-        if into is not None:
-            if len(into) != 2 or not all(isinstance(t, torch.Tensor) for t in into):
-                raise TypeError("value_and_vjp: `into` must be a pair of tensors (y, dx)")
-            y, dx = into
-            if y.dtype != torch.float32 or dx.dtype != torch.float32:
-                raise TypeError("value_and_vjp: `into` must be float32; got %s, %s" % (y.dtype, dx.dtype))
-            if not (y.is_contiguous() and dx.is_contiguous()) or y.numel() != n * out_dim or dx.numel() != x.numel() \
-                    or y.device != x.device or dx.device != x.device:
-                raise ValueError("value_and_vjp: `into` must be contiguous {[%d, %d], %s} on %s" % (n, out_dim, tuple(x.shape), x.device))
+        _check_grad_out("value_and_vjp", x, out_dim, grad_out)
+        y, dx = _check_into("value_and_vjp", x, into, torch.float32, out_dim, x.shape, _ONE_LAUNCH_PAIR[_VJP])
         entry = st["entry"]()
         with torch.cuda.device(x.device):
             if al is not None:
@@ -1115,45 +1173,27 @@ class MolANN(_PlanOwner, torch.nn.Module):
             entry.plan.value_and_vjp(x, g, y, dx)
         return y, dx
 
-    def _value_and_vjp_f64(self, st, x, grad_out, into):
-        """`value_and_vjp` of a float64 model: the arguments are checked here for both ways to the kernel (the dispatcher
-        operator where that library is built, else the ctypes plan)."""
-        al, lins = st["al"], st["linears"]
-        w0 = lins[0].weight
-        if w0.device != x.device or w0.dtype != torch.float64:
-            raise RuntimeError("ann_layers must be float64 on %s for a float64 input (got %s on %s): call .double()"
-                               % (x.device, w0.dtype, w0.device))
-        x = x.detach()
-        x = x if x.is_contiguous() else x.contiguous()
-        n, out_dim = x.shape[0], st["out_dim"]
-        if not isinstance(grad_out, torch.Tensor) or grad_out.numel() != n * out_dim or grad_out.device != x.device:
-            raise ValueError("value_and_vjp: grad_out must hold [%d, %d] values on %s" % (n, out_dim, x.device))
-        if not grad_out.dtype.is_floating_point:
-            raise TypeError("value_and_vjp: grad_out must be a floating-point tensor; got %s" % grad_out.dtype)
-        if into is not None:
-            if len(into) != 2 or not all(isinstance(t, torch.Tensor) for t in into):
-                raise TypeError("value_and_vjp: `into` must be a pair of tensors (y, dx)")
-            y, dx = into
-            if y.dtype != torch.float64 or dx.dtype != torch.float64:
-                raise TypeError("value_and_vjp: `into` must be float64 like x; got %s, %s" % (y.dtype, dx.dtype))
-            if not (y.is_contiguous() and dx.is_contiguous()) or y.numel() != n * out_dim or dx.numel() != x.numel() \
-                    or y.device != x.device or dx.device != x.device:
-                raise ValueError("value_and_vjp: `into` must be contiguous {[%d, %d], %s} on %s" % (n, out_dim, tuple(x.shape), x.device))
-        g = grad_out if (grad_out.dtype == torch.float64 and grad_out.is_contiguous()) else grad_out.double().contiguous()
-        if st["op"] is not None:
-            y, dx = st["op_vjp"](x, st["handle"], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"],
-                                 [lin.weight for lin in lins], [lin.bias for lin in lins], g, list(into) if into is not None else [])
-            return y, dx
-        entry = st["entry"]()
-        with torch.cuda.device(x.device):
-            if al is not None:
-                entry.sync_ref(_device_buffer(al.ref_x, x))
-            if into is None:
-                y, dx = torch.empty((n, out_dim), dtype=torch.float64, device=x.device), torch.empty_like(x)
-            if n > 0:
-                entry.plan.value_and_vjp_f64(x, g, [lin.weight.detach().contiguous() for lin in lins],
-                                             [lin.bias.detach().contiguous() for lin in lins], y, dx)
-        return y, dx
+    def _one_launch_state(self, x, kind, dtypes):
+        """The fused-plan gate of the one-launch calls: this model's state on x's device, or the refusal that names the route that
+        remains."""
+        st = self._fast_state(x) if isinstance(x, torch.Tensor) and x.is_cuda else None
+        if st is None or not st["fused"]:
+            route = _ONE_LAUNCH_ROUTE[kind]
+            raise NotImplementedError("%s needs a model served by one fused plan on a HIP device (a feature layer and a Linear / activation "
+                                      "head, %s, on a HIP tensor)%s" % (_ONE_LAUNCH_NAME[kind], dtypes, "; otherwise " + route if route else ""))
+        return st
+
+    def _one_launch_f64(self, kind, st, x, extra, into):
+        """A float64 one-launch call of a model the gate has passed: the arguments are checked once for both ways to the kernel (the
+        dispatcher operator where that library is built, else the ctypes plan)."""
+        al, lins, out_dim = st["al"], st["linears"], st["out_dim"]
+        x, extra, y, second, shape = _one_launch_arguments(kind, x, extra, into, st["fl"].input_atom_num, out_dim, lins, al)
+        if st["op"] is None:
+            return _one_launch_ctypes(kind, st["entry"](), x, extra, y, second, shape, out_dim, lins, al)
+        op, ref = st[_ONE_LAUNCH_OP[kind]], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"]
+        W, B, into = [lin.weight for lin in lins], [lin.bias for lin in lins], list(into) if into is not None else []
+        y, second = op(x, st["handle"], ref, W, B, into) if kind == _JACOBIAN else op(x, st["handle"], ref, W, B, extra, into)
+        return y, second
 
     def value_and_jacobian(self, x, into=None):
         """``(y, jac)`` with ``y = self(x)`` [N, d_out] and ``jac[f, k] = d y[f, k] / d x[f]`` [N, d_out, n_inp, 3], float64, in ONE
@@ -1163,51 +1203,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
         bit.  No autograd graph is recorded (parameters are data); ``into=(y, jac)`` reuses the caller's buffers.  Every row of
         ``jac`` is stored once, its terms summed in a fixed order: the same bits on every call.  `model.double()` and a float64 x
         on a HIP device; a model served by one fused plan."""
-        route = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
-        st = self._fast_state(x) if isinstance(x, torch.Tensor) and x.is_cuda else None
-        if st is None or not st["fused"]:
-            raise NotImplementedError("value_and_jacobian needs a model served by one fused plan on a HIP device (a feature layer and a "
-                                      "Linear / activation head, float64, on a HIP tensor); otherwise " + route)
-        al, fl, lins = st["al"], st["fl"], st["linears"]
-        _check_input(x, fl.input_atom_num)
-        if x.dtype != torch.float64:
-            raise TypeError("value_and_jacobian is float64: call model.double() and pass a float64 x (got %s); for float32 %s"
-                            % (x.dtype, route))
-        w0 = lins[0].weight
-        if w0.device != x.device or w0.dtype != torch.float64:
-            raise RuntimeError("ann_layers must be float64 on %s for a float64 input (got %s on %s): call .double()"
-                               % (x.device, w0.dtype, w0.device))
-        x = x.detach()
-        x = x if x.is_contiguous() else x.contiguous()
-        n, out_dim = x.shape[0], st["out_dim"]
-        if into is not None:
-            if len(into) != 2 or not all(isinstance(t, torch.Tensor) for t in into):
-                raise TypeError("value_and_jacobian: `into` must be a pair of tensors (y, jac)")
-            y, jac = into
-            if y.dtype != torch.float64 or jac.dtype != torch.float64:
-                raise TypeError("value_and_jacobian: `into` must be float64 like x; got %s, %s" % (y.dtype, jac.dtype))
-            if not (y.is_contiguous() and jac.is_contiguous()) or y.numel() != n * out_dim or jac.numel() != out_dim * x.numel() \
-                    or y.device != x.device or jac.device != x.device:
-                raise ValueError("value_and_jacobian: `into` must be contiguous {[%d, %d], [%d, %d, %d, 3]} on %s"
-                                 % (n, out_dim, n, out_dim, x.shape[1], x.device))
-        if st["op"] is not None:
-            y, jac = torch.ops.molann.value_and_jacobian_h(x, st["handle"], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"],
-                                                           [lin.weight for lin in lins], [lin.bias for lin in lins],
-                                                           list(into) if into is not None else [])
-            return y, jac
-        entry = st["entry"]()
-        with torch.cuda.device(x.device):
-            if not entry.plan.supports_value_and_jacobian_f64():
-                raise NotImplementedError("value_and_jacobian: one frame's rows exceed the LDS of a compute unit for this model; " + route)
-            if al is not None:
-                entry.sync_ref(_device_buffer(al.ref_x, x))
-            if into is None:
-                y = torch.empty((n, out_dim), dtype=torch.float64, device=x.device)
-                jac = torch.empty((n, out_dim, x.shape[1], 3), dtype=torch.float64, device=x.device)
-            if n > 0:
-                entry.plan.value_and_jacobian_f64(x, [lin.weight.detach().contiguous() for lin in lins],
-                                                  [lin.bias.detach().contiguous() for lin in lins], y, jac)
-        return y, jac
+        return self._one_launch_f64(_JACOBIAN, self._one_launch_state(x, _JACOBIAN, "float64"), x, None, into)
 
     def value_and_metric(self, x, weights=None, into=None):
         """``(y, M)`` with ``y = self(x)`` [N, d_out] and the metric tensor of the outputs
@@ -1221,43 +1217,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
         bit, ``weights=None`` the bits of ``torch.ones``.  With G the same quantity of the features
         (`PreprocessingANN.value_and_metric`), ``sum_a w_a |grad_a y_k|^2 = dF_k G dF_k^T``, ``dF = d y / d feat``.
         `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at most 64 outputs."""
-        route = _METRIC_ROUTE
-        st = self._fast_state(x) if isinstance(x, torch.Tensor) and x.is_cuda else None
-        if st is None or not st["fused"]:
-            raise NotImplementedError("value_and_metric needs a model served by one fused plan on a HIP device (a feature layer and a "
-                                      "Linear / activation head, float64, on a HIP tensor); otherwise " + route)
-        al, fl, lins = st["al"], st["fl"], st["linears"]
-        _check_input(x, fl.input_atom_num)
-        if x.dtype != torch.float64:
-            raise TypeError("value_and_metric is float64: call model.double() and pass a float64 x (got %s); for float32 %s"
-                            % (x.dtype, route))
-        w0 = lins[0].weight
-        if w0.device != x.device or w0.dtype != torch.float64:
-            raise RuntimeError("ann_layers must be float64 on %s for a float64 input (got %s on %s): call .double()"
-                               % (x.device, w0.dtype, w0.device))
-        x = x.detach()
-        x = x if x.is_contiguous() else x.contiguous()
-        n, out_dim = x.shape[0], st["out_dim"]
-        weights, y, M = _check_metric_args("value_and_metric", x, fl.input_atom_num, out_dim, weights, into)
-        if st["op"] is not None:
-            y, M = torch.ops.molann.value_and_metric_h(x, st["handle"], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"],
-                                                       [lin.weight for lin in lins], [lin.bias for lin in lins], weights,
-                                                       list(into) if into is not None else [])
-            return y, M
-        entry = st["entry"]()
-        with torch.cuda.device(x.device):
-            if not entry.plan.supports_value_and_metric_f64():
-                raise NotImplementedError("value_and_metric: no single-launch kernel for this model (more than 64 outputs, or one frame's "
-                                          "rows exceed the LDS of a compute unit); " + route)
-            if al is not None:
-                entry.sync_ref(_device_buffer(al.ref_x, x))
-            if into is None:
-                y = torch.empty((n, out_dim), dtype=torch.float64, device=x.device)
-                M = torch.empty((n, out_dim, out_dim), dtype=torch.float64, device=x.device)
-            if n > 0:
-                entry.plan.value_and_metric_f64(x, [lin.weight.detach().contiguous() for lin in lins],
-                                                [lin.bias.detach().contiguous() for lin in lins], weights, y, M)
-        return y, M
+        return self._one_launch_f64(_METRIC, self._one_launch_state(x, _METRIC, "float64"), x, weights, into)
 
     def _tangent_present(self, x):
         if _has_tangent(x):
@@ -1311,7 +1271,8 @@ class MolANN(_PlanOwner, torch.nn.Module):
             # ctypes for a 1024-frame batch (tools/latency_c1.py)
             st["op"] = _run_op()
             if st["op"] is not None:
-                st["op_vjp"] = torch.ops.molann.value_and_vjp_h
+                st["op_vjp"], st["op_jacobian"], st["op_metric"] = (torch.ops.molann.value_and_vjp_h, torch.ops.molann.value_and_jacobian_h,
+                                                                    torch.ops.molann.value_and_metric_h)
                 from . import script
                 st["desc"] = script.make_desc(script.KIND_FORWARD, fl.input_atom_num,
                                               align_idx=al._local_align_atom_indices if al is not None else None,

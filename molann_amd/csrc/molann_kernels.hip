@@ -70,6 +70,4 @@ using namespace molann;
 #include "molann_capi.inc"
 #include "molann_jvp.inc"
 #include "molann_hvp.inc"
-#include "molann_vjp_f64.inc"
-#include "molann_jac_f64.inc"
-#include "molann_metric_f64.inc"
+#include "molann_value_f64.inc"

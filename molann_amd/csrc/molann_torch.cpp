@@ -281,14 +281,54 @@ int64_t register_desc(std::vector<int64_t> desc) {
     return (int64_t)g_handles.size() - 1;
 }
 
-at::Tensor run_h_hip(const at::Tensor& x, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights, std::vector<at::Tensor> biases) {
-    std::shared_ptr<const std::vector<int64_t>> d;
-    {
-        std::lock_guard<std::mutex> lock(g_handle_mu);
-        TORCH_CHECK(handle >= 0 && (size_t)handle < g_handles.size(), "molann::run_h: unknown handle ", handle);
-        d = g_handles[(size_t)handle];
+// the description behind a handle (shared: a later register_desc may move the list)
+std::shared_ptr<const std::vector<int64_t>> desc_of(int64_t handle, const char* op) {
+    std::lock_guard<std::mutex> lock(g_handle_mu);
+    TORCH_CHECK(handle >= 0 && (size_t)handle < g_handles.size(), op, ": unknown handle ", handle);
+    return g_handles[(size_t)handle];
+}
+
+// The float64 Linear tensors of a forward plan as the float64 entry points take them, read as they are: `hold` keeps the contiguous
+// tensors alive, W / B point into them.  Nothing for a plan without a head.
+struct F64Linears {
+    std::vector<at::Tensor> hold;
+    std::vector<const double*> W, B;
+};
+void f64_linears(const char* op, const Entry& e, const at::Tensor& x, const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                 F64Linears& lin, const char* hint = "") {
+    if (e.kind != KIND_FORWARD) return;
+    TORCH_CHECK((int)weights.size() == e.n_layers && (int)biases.size() == e.n_layers, op, ": expected ", e.n_layers, " weight and bias tensors");
+    for (int l = 0; l < e.n_layers; ++l) {
+        TORCH_CHECK(weights[l].scalar_type() == at::kDouble && biases[l].scalar_type() == at::kDouble && weights[l].device() == x.device() &&
+                        biases[l].device() == x.device(),
+                    op, ": ann_layers must be float64 on ", x.device(), " for a float64 input", hint);
+        lin.hold.push_back(weights[l].detach().contiguous()); lin.W.push_back(lin.hold.back().data_ptr<double>());
+        lin.hold.push_back(biases[l].detach().contiguous()); lin.B.push_back(lin.hold.back().data_ptr<double>());
     }
-    return run_impl(x, *d, ref_x, weights, biases);
+}
+
+// The two outputs of a one-launch operator: the caller's `into` pair - x's dtype, contiguous, the element counts of the two shapes, on
+// x's device - or fresh tensors of those shapes.  `names` ("(out, jac)") makes the refusals typed: any count but 0 and 2 is refused,
+// a wrong dtype is a TypeError, the rest a ValueError.  Without it (value_and_vjp, which predates them) every fault is a plain Error
+// and any other count means none.
+std::pair<at::Tensor, at::Tensor> into_pair(const char* op, const std::vector<at::Tensor>& into, const at::Tensor& x, at::IntArrayRef shape0,
+                                            at::IntArrayRef shape1, const char* names, const char* shapes) {
+    if (names) TORCH_CHECK(into.empty() || into.size() == 2, op, ": `into` must be a pair of tensors ", names);
+    if (into.size() != 2) return {at::empty(shape0, x.options()), at::empty(shape1, x.options())};
+    const at::Tensor &a = into[0], &b = into[1];
+    const bool dtype = a.scalar_type() == x.scalar_type() && b.scalar_type() == x.scalar_type();
+    const bool rest = a.is_contiguous() && b.is_contiguous() && a.numel() == c10::multiply_integers(shape0) &&
+                      b.numel() == c10::multiply_integers(shape1) && a.device() == x.device() && b.device() == x.device();
+    if (names) {
+        TORCH_CHECK_TYPE(dtype, op, ": `into` must be float64 like x");
+        TORCH_CHECK_VALUE(rest, op, ": `into` must be contiguous ", shapes, " on x's device");
+    } else
+        TORCH_CHECK(dtype && rest, op, ": `into` must be contiguous ", shapes, " on x's device");
+    return {a, b};
+}
+
+at::Tensor run_h_hip(const at::Tensor& x, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights, std::vector<at::Tensor> biases) {
+    return run_impl(x, *desc_of(handle, "molann::run_h"), ref_x, weights, biases);
 }
 
 at::Tensor run_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -314,18 +354,10 @@ at::Tensor run_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, co
         if (e->kind == KIND_ALIGN) check(molann_align_f64(e->plan, xd, n, od, stream), "molann_align_f64");
         else if (e->kind == KIND_FEATURES) check(molann_features_f64(e->plan, xd, n, od, stream), "molann_features_f64");
         else {
-            TORCH_CHECK((int)weights.size() == e->n_layers && (int)biases.size() == e->n_layers, "molann::run: expected ", e->n_layers,
-                        " weight and bias tensors");
-            std::vector<at::Tensor> hold;
-            std::vector<const double*> W, B;
-            for (int l = 0; l < e->n_layers; ++l) {
-                TORCH_CHECK(weights[l].scalar_type() == at::kDouble && biases[l].scalar_type() == at::kDouble && weights[l].device() == x.device(),
-                            "molann::run: ann_layers must be float64 on ", x.device(), " for a float64 input");
-                hold.push_back(weights[l].detach().contiguous()); W.push_back(hold.back().data_ptr<double>());
-                hold.push_back(biases[l].detach().contiguous()); B.push_back(hold.back().data_ptr<double>());
-            }
+            F64Linears lin;
+            f64_linears("molann::run", *e, x, weights, biases, lin);
             at::Tensor work = at::empty({n, e->feature_dim}, x.options());
-            check(molann_forward_f64(e->plan, xd, n, W.data(), B.data(), work.data_ptr<double>(), od, stream), "molann_forward_f64");
+            check(molann_forward_f64(e->plan, xd, n, lin.W.data(), lin.B.data(), work.data_ptr<double>(), od, stream), "molann_forward_f64");
         }
         return out;
     }
@@ -389,13 +421,7 @@ std::vector<at::Tensor> value_and_vjp_hip(const at::Tensor& x_in, std::vector<in
 }
 std::vector<at::Tensor> value_and_vjp_h_hip(const at::Tensor& x_in, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
                                             std::vector<at::Tensor> biases, const at::Tensor& grad_out, std::vector<at::Tensor> into) {
-    std::shared_ptr<const std::vector<int64_t>> d;
-    {
-        std::lock_guard<std::mutex> lock(g_handle_mu);
-        TORCH_CHECK(handle >= 0 && (size_t)handle < g_handles.size(), "molann::value_and_vjp_h: unknown handle ", handle);
-        d = g_handles[(size_t)handle];
-    }
-    return value_and_vjp_impl(x_in, *d, ref_x, weights, biases, grad_out, into);
+    return value_and_vjp_impl(x_in, *desc_of(handle, "molann::value_and_vjp_h"), ref_x, weights, biases, grad_out, into);
 }
 std::vector<at::Tensor> value_and_vjp_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x, const std::vector<at::Tensor>& weights,
                                            const std::vector<at::Tensor>& biases, const at::Tensor& grad_out, const std::vector<at::Tensor>& into) {
@@ -410,35 +436,16 @@ std::vector<at::Tensor> value_and_vjp_impl(const at::Tensor& x_in, const std::ve
     const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
     at::Tensor g = grad_out.scalar_type() == st && grad_out.is_contiguous() ? grad_out : grad_out.to(st).contiguous();
     TORCH_CHECK(g.numel() == n * cols && g.device() == x.device(), "molann::value_and_vjp: grad_out must be [", n, ", ", cols, "] on ", x.device());
-    at::Tensor out, gx;
-    if (into.size() == 2) {
-        out = into[0]; gx = into[1];
-        TORCH_CHECK(out.is_contiguous() && gx.is_contiguous() && out.scalar_type() == st && gx.scalar_type() == st &&
-                    out.numel() == n * cols && gx.numel() == x.numel() && out.device() == x.device() && gx.device() == x.device(),
-                    "molann::value_and_vjp: `into` must be contiguous ", f64 ? "float64" : "float32", " {[N, out_dim], [N, n_inp, 3]} on x's device");
-    } else {
-        out = at::empty({n, cols}, x.options());
-        gx = at::empty_like(x);
-    }
-    std::vector<at::Tensor> hold;
-    std::vector<const double*> W, B;
-    if (f64 && e->kind == KIND_FORWARD) {
-        TORCH_CHECK((int)weights.size() == e->n_layers && (int)biases.size() == e->n_layers, "molann::value_and_vjp: expected ", e->n_layers,
-                    " weight and bias tensors");
-        for (int l = 0; l < e->n_layers; ++l) {
-            TORCH_CHECK(weights[l].scalar_type() == at::kDouble && biases[l].scalar_type() == at::kDouble && weights[l].device() == x.device() &&
-                            biases[l].device() == x.device(),
-                        "molann::value_and_vjp: ann_layers must be float64 on ", x.device(), " for a float64 input");
-            hold.push_back(weights[l].detach().contiguous()); W.push_back(hold.back().data_ptr<double>());
-            hold.push_back(biases[l].detach().contiguous()); B.push_back(hold.back().data_ptr<double>());
-        }
-    }
+    const auto [out, gx] = into_pair("molann::value_and_vjp", into, x, {n, cols}, x.sizes(), nullptr,
+                                     f64 ? "float64 {[N, out_dim], [N, n_inp, 3]}" : "float32 {[N, out_dim], [N, n_inp, 3]}");
+    F64Linears lin;
+    if (f64) f64_linears("molann::value_and_vjp", *e, x, weights, biases, lin);
     if (n == 0) return {out, gx};
     hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
     std::lock_guard<std::mutex> lock(e->mu);
     sync_live(*e, x, ref_x, weights, biases, stream);
     if (f64) {
-        check(molann_value_and_vjp_f64(e->plan, x.data_ptr<double>(), g.data_ptr<double>(), n, W.data(), B.data(), out.data_ptr<double>(),
+        check(molann_value_and_vjp_f64(e->plan, x.data_ptr<double>(), g.data_ptr<double>(), n, lin.W.data(), lin.B.data(), out.data_ptr<double>(),
                                        gx.data_ptr<double>(), stream),
               "molann_value_and_vjp_f64");
         return {out, gx};
@@ -462,31 +469,10 @@ std::vector<at::Tensor> value_and_jacobian_impl(const at::Tensor& x_in, const st
     auto e = entry_for(desc, x, ref_x);
     const int64_t n = x.size(0);
     const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
-    TORCH_CHECK(into.empty() || into.size() == 2, "molann::value_and_jacobian: `into` must be a pair of tensors (out, jac)");
-    at::Tensor out, jac;
-    if (into.size() == 2) {
-        out = into[0]; jac = into[1];
-        TORCH_CHECK_TYPE(out.scalar_type() == at::kDouble && jac.scalar_type() == at::kDouble, "molann::value_and_jacobian: `into` must be float64 like x");
-        TORCH_CHECK_VALUE(out.is_contiguous() && jac.is_contiguous() && out.numel() == n * cols && jac.numel() == cols * x.numel() &&
-                              out.device() == x.device() && jac.device() == x.device(),
-                          "molann::value_and_jacobian: `into` must be contiguous {[N, out_dim], [N, out_dim, n_inp, 3]} on x's device");
-    } else {
-        out = at::empty({n, cols}, x.options());
-        jac = at::empty({n, cols, x.size(1), 3}, x.options());
-    }
-    std::vector<at::Tensor> hold;
-    std::vector<const double*> W, B;
-    if (e->kind == KIND_FORWARD) {
-        TORCH_CHECK((int)weights.size() == e->n_layers && (int)biases.size() == e->n_layers, "molann::value_and_jacobian: expected ", e->n_layers,
-                    " weight and bias tensors");
-        for (int l = 0; l < e->n_layers; ++l) {
-            TORCH_CHECK(weights[l].scalar_type() == at::kDouble && biases[l].scalar_type() == at::kDouble && weights[l].device() == x.device() &&
-                            biases[l].device() == x.device(),
-                        "molann::value_and_jacobian: ann_layers must be float64 on ", x.device(), " for a float64 input: call .double()");
-            hold.push_back(weights[l].detach().contiguous()); W.push_back(hold.back().data_ptr<double>());
-            hold.push_back(biases[l].detach().contiguous()); B.push_back(hold.back().data_ptr<double>());
-        }
-    }
+    const auto [out, jac] = into_pair("molann::value_and_jacobian", into, x, {n, cols}, {n, cols, x.size(1), 3}, "(out, jac)",
+                                      "{[N, out_dim], [N, out_dim, n_inp, 3]}");
+    F64Linears lin;
+    f64_linears("molann::value_and_jacobian", *e, x, weights, biases, lin, ": call .double()");
     std::lock_guard<std::mutex> lock(e->mu);
     TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_jacobian_f64(e->plan) == 1,
                                 "molann::value_and_jacobian: one frame's rows exceed the LDS of a compute unit for this model; use value_and_vjp "
@@ -494,7 +480,8 @@ std::vector<at::Tensor> value_and_jacobian_impl(const at::Tensor& x_in, const st
     if (n == 0) return {out, jac};
     hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
     sync_live(*e, x, ref_x, weights, biases, stream);
-    check(molann_value_and_jacobian_f64(e->plan, x.data_ptr<double>(), n, W.data(), B.data(), out.data_ptr<double>(), jac.data_ptr<double>(), stream),
+    check(molann_value_and_jacobian_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), out.data_ptr<double>(), jac.data_ptr<double>(),
+                                        stream),
           "molann_value_and_jacobian_f64");
     return {out, jac};
 }
@@ -504,13 +491,7 @@ std::vector<at::Tensor> value_and_jacobian_hip(const at::Tensor& x_in, std::vect
 }
 std::vector<at::Tensor> value_and_jacobian_h_hip(const at::Tensor& x_in, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
                                                  std::vector<at::Tensor> biases, std::vector<at::Tensor> into) {
-    std::shared_ptr<const std::vector<int64_t>> d;
-    {
-        std::lock_guard<std::mutex> lock(g_handle_mu);
-        TORCH_CHECK(handle >= 0 && (size_t)handle < g_handles.size(), "molann::value_and_jacobian_h: unknown handle ", handle);
-        d = g_handles[(size_t)handle];
-    }
-    return value_and_jacobian_impl(x_in, *d, ref_x, weights, biases, into);
+    return value_and_jacobian_impl(x_in, *desc_of(handle, "molann::value_and_jacobian_h"), ref_x, weights, biases, into);
 }
 
 // {out, metric}: the float64 forward's outputs and the metric tensor metric[N, out_dim, out_dim] = sum_a atom_w[a] (d out_k / d x_a) .
@@ -535,31 +516,10 @@ std::vector<at::Tensor> value_and_metric_impl(const at::Tensor& x_in, const std:
                           " values (one per atom) on ", x.device());
         atom_w = atom_w_in->detach().reshape({-1}).contiguous();
     }
-    TORCH_CHECK(into.empty() || into.size() == 2, "molann::value_and_metric: `into` must be a pair of tensors (out, metric)");
-    at::Tensor out, metric;
-    if (into.size() == 2) {
-        out = into[0]; metric = into[1];
-        TORCH_CHECK_TYPE(out.scalar_type() == at::kDouble && metric.scalar_type() == at::kDouble, "molann::value_and_metric: `into` must be float64 like x");
-        TORCH_CHECK_VALUE(out.is_contiguous() && metric.is_contiguous() && out.numel() == n * cols && metric.numel() == n * cols * cols &&
-                              out.device() == x.device() && metric.device() == x.device(),
-                          "molann::value_and_metric: `into` must be contiguous {[N, out_dim], [N, out_dim, out_dim]} on x's device");
-    } else {
-        out = at::empty({n, cols}, x.options());
-        metric = at::empty({n, cols, cols}, x.options());
-    }
-    std::vector<at::Tensor> hold;
-    std::vector<const double*> W, B;
-    if (e->kind == KIND_FORWARD) {
-        TORCH_CHECK((int)weights.size() == e->n_layers && (int)biases.size() == e->n_layers, "molann::value_and_metric: expected ", e->n_layers,
-                    " weight and bias tensors");
-        for (int l = 0; l < e->n_layers; ++l) {
-            TORCH_CHECK(weights[l].scalar_type() == at::kDouble && biases[l].scalar_type() == at::kDouble && weights[l].device() == x.device() &&
-                            biases[l].device() == x.device(),
-                        "molann::value_and_metric: ann_layers must be float64 on ", x.device(), " for a float64 input: call .double()");
-            hold.push_back(weights[l].detach().contiguous()); W.push_back(hold.back().data_ptr<double>());
-            hold.push_back(biases[l].detach().contiguous()); B.push_back(hold.back().data_ptr<double>());
-        }
-    }
+    const auto [out, metric] = into_pair("molann::value_and_metric", into, x, {n, cols}, {n, cols, cols}, "(out, metric)",
+                                         "{[N, out_dim], [N, out_dim, out_dim]}");
+    F64Linears lin;
+    f64_linears("molann::value_and_metric", *e, x, weights, biases, lin, ": call .double()");
     std::lock_guard<std::mutex> lock(e->mu);
     TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_metric_f64(e->plan) == 1,
                                 "molann::value_and_metric: no single-launch kernel for this model (more than 64 outputs, or one frame's rows exceed "
@@ -567,20 +527,14 @@ std::vector<at::Tensor> value_and_metric_impl(const at::Tensor& x_in, const std:
     if (n == 0) return {out, metric};
     hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
     sync_live(*e, x, ref_x, weights, biases, stream);
-    check(molann_value_and_metric_f64(e->plan, x.data_ptr<double>(), n, W.data(), B.data(), atom_w.defined() ? atom_w.data_ptr<double>() : nullptr,
+    check(molann_value_and_metric_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), atom_w.defined() ? atom_w.data_ptr<double>() : nullptr,
                                       out.data_ptr<double>(), metric.data_ptr<double>(), stream),
           "molann_value_and_metric_f64");
     return {out, metric};
 }
 std::vector<at::Tensor> value_and_metric_h_hip(const at::Tensor& x_in, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
                                                std::vector<at::Tensor> biases, const c10::optional<at::Tensor>& atom_w, std::vector<at::Tensor> into) {
-    std::shared_ptr<const std::vector<int64_t>> d;
-    {
-        std::lock_guard<std::mutex> lock(g_handle_mu);
-        TORCH_CHECK(handle >= 0 && (size_t)handle < g_handles.size(), "molann::value_and_metric_h: unknown handle ", handle);
-        d = g_handles[(size_t)handle];
-    }
-    return value_and_metric_impl(x_in, *d, ref_x, weights, biases, atom_w, into);
+    return value_and_metric_impl(x_in, *desc_of(handle, "molann::value_and_metric_h"), ref_x, weights, biases, atom_w, into);
 }
 
 // The fused forward that also keeps the features: {out, features} - or {out, empty} where the plan has no such twin of its

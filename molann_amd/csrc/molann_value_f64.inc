@@ -1,0 +1,210 @@
+// molann_value_f64.inc - part of libmolann_hip.so, included by molann_kernels.hip after molann_hvp.inc.  The float64 calls that give the
+// values and a derivative in one launch (see include/molann_hip.h): molann_value_and_vjp_f64 (forces, frames_value_vjp_f64_kernel of
+// molann_dev_vjp_f64.inc), molann_value_and_jacobian_f64 (frames_value_jac_f64_kernel, molann_dev_jac_f64.inc) and
+// molann_value_and_metric_f64 (frames_value_metric_f64_kernel, molann_dev_metric_f64.inc).  One argument front end, one launch and
+// one dispatch over the lane group serve the three; an entry names its kernel, its pointers and its rows.
+namespace {
+
+constexpr size_t VJP64_LDS_DEFAULT = 65536;    // dynamic LDS a launch may ask for as it is
+constexpr size_t VJP64_LDS_CU = 163840;        // the LDS of a gfx950 compute unit (one block of one wave may take all of it)
+// the widest output the metric kernel's chunk pairs serve: d_out / JAC64_KC chunks, every pair of them a pass over the frame's atoms
+constexpr int METRIC64_MAX_D_OUT = 64;
+
+enum F64Entry { F64_VJP, F64_JACOBIAN, F64_METRIC };
+
+struct Vjp64Geom {
+    int G, block;       // lanes per frame, threads per block
+    size_t lds;         // dynamic LDS of a block, bytes
+    bool ok;
+};
+
+// doubles of LDS per frame: the feature row, the hidden layers' pre-activations, two rows of the widest layer input
+inline void vjp64_rows(const molann_plan* p, int& max_w, int& per_frame) {
+    max_w = 0; per_frame = 0;
+    if (p->n_layers <= 0) return;
+    long z = 0;
+    for (int l = 0; l < p->n_layers; ++l) {
+        max_w = std::max(max_w, p->dims[l]);
+        if (l > 0) z += p->dims[l];
+    }
+    const long total = (long)p->d_feat + z + 2l * max_w;
+    per_frame = total > (1l << 28) ? (1 << 28) : (int)total;
+}
+
+// doubles of LDS per frame of the Jacobian and the metric (whose accumulators of a chunk pair live in registers): with a head the
+// feature row, the hidden layers' act'(z), two buffers of d_out rows of the widest layer input (the forward's two activation rows
+// live in them first); with an alignment 12 per output (G_R and gsum, then G_H and cen)
+inline void jac64_rows(const molann_plan* p, int& max_w, int& z_w, int& per_frame) {
+    int vjp_rows;
+    vjp64_rows(p, max_w, vjp_rows);
+    const long d_out = p->n_layers > 0 ? p->dims[p->n_layers] : p->d_feat;
+    long z = 0, total = 0;
+    for (int l = 1; l < p->n_layers; ++l) z += p->dims[l];
+    if (p->n_layers > 0) total = (long)p->d_feat + z + 2l * d_out * max_w;
+    if (p->n_align > 0) total += 12l * d_out;
+    z_w = (int)std::min(z, 1l << 28);
+    per_frame = total > (1l << 28) ? (1 << 28) : (int)total;
+}
+
+// lanes per frame: the smallest group that covers the atoms, the items, the align atoms and the head's widest layer in one round
+// (8/4/2 frames per wave), a whole wave from 33 on; fewer waves per block, then one wave per frame, where the rows ask for it
+// (the rows are the entry's: the Jacobian sizes its own and steps down the same way)
+inline Vjp64Geom vjp64_geometry_rows(const molann_plan* p, int max_w, int per_frame) {
+    int work = std::max(std::max(p->n_inp, p->n_items), std::max(p->n_align, max_w));
+    for (int l = 1; l <= p->n_layers; ++l) work = std::max(work, p->dims[l]);
+    Vjp64Geom g;
+    g.G = work <= 8 ? 8 : work <= 16 ? 16 : work <= 32 ? 32 : 64;
+    const size_t bytes = (size_t)per_frame * sizeof(double);
+    g.ok = p->n_items > 0 && bytes <= VJP64_LDS_CU;
+    if ((size_t)(64 / g.G) * bytes > VJP64_LDS_DEFAULT) g.G = 64;
+    int waves = 4;
+    while (waves > 1 && (size_t)waves * (64 / g.G) * bytes > VJP64_LDS_DEFAULT) waves >>= 1;
+    g.block = 64 * waves;
+    g.lds = (size_t)(g.block / g.G) * bytes;
+    return g;
+}
+
+// the kernel arguments' rows, by the struct that carries them
+inline void f64_entry_rows(const molann_plan* p, VjpF64Args& a) { vjp64_rows(p, a.max_w, a.lds_per_frame); }
+inline void f64_entry_rows(const molann_plan* p, JacF64Args& a) { jac64_rows(p, a.max_w, a.z_w, a.lds_per_frame); }
+
+// geometry for this entry: the forces' rows or the Jacobian's, and the metric's cap on the outputs
+inline Vjp64Geom f64_entry_geometry(const molann_plan* p, F64Entry entry) {
+    int max_w, z_w, per_frame;
+    if (entry == F64_VJP) vjp64_rows(p, max_w, per_frame);
+    else jac64_rows(p, max_w, z_w, per_frame);
+    Vjp64Geom g = vjp64_geometry_rows(p, max_w, per_frame);
+    if (entry == F64_METRIC && (p->n_layers > 0 ? p->dims[p->n_layers] : p->d_feat) > METRIC64_MAX_D_OUT) g.ok = false;
+    return g;
+}
+
+template <class Args>
+struct F64Call {    // what a launch takes besides the caller's pointers
+    Vjp64Geom g;
+    Args a;
+    F64Mlp m;
+};
+
+// The argument front end of the three entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
+// must be there (`required`), their and `optional`'s 8-byte alignment (a null `optional` passes), items, the head's tensors layer
+// by layer, geometry.  Nothing is dereferenced but W and b.
+template <class Args>
+int f64_entry_arguments(const molann_plan* p, F64Entry entry, int64_t n, std::initializer_list<const void*> required, const void* optional,
+                        const double* const* W, const double* const* b, F64Call<Args>& c) {
+    if (!p) return MOLANN_E_NULL;
+    if (n < 0) return MOLANN_E_DESC;
+    if (n == 0) return MOLANN_OK;
+    uintptr_t low_bits = (uintptr_t)optional;
+    for (const void* ptr : required) {
+        if (!ptr) return MOLANN_E_NULL;
+        low_bits |= (uintptr_t)ptr;
+    }
+    if (low_bits & 7) return MOLANN_E_ALIGNMENT;
+    if (p->n_items <= 0) return MOLANN_E_STAGE;
+    F64Mlp& m = c.m;
+    memset(&m, 0, sizeof(m));
+    m.n_layers = p->n_layers; m.act = p->act;
+    if (p->n_layers > 0) {
+        if (!W || !b) return MOLANN_E_NULL;
+        for (int i = 0; i <= p->n_layers; ++i) m.dims[i] = p->dims[i];
+        for (int l = 0; l < p->n_layers; ++l) {
+            if (!W[l] || !b[l]) return MOLANN_E_NULL;
+            if ((((uintptr_t)W[l]) & 7) || (((uintptr_t)b[l]) & 7)) return MOLANN_E_ALIGNMENT;
+            m.W[l] = W[l]; m.b[l] = b[l];
+        }
+    }
+    c.g = f64_entry_geometry(p, entry);
+    if (!c.g.ok) return MOLANN_E_UNSUPPORTED;
+    Args& a = c.a;
+    a.n_frames = (long)n;
+    a.n_inp = p->n_inp; a.n_align = p->n_align; a.n_items = p->n_items; a.d_feat = p->d_feat;
+    a.d_out = p->n_layers > 0 ? p->dims[p->n_layers] : p->d_feat;
+    f64_entry_rows(p, a);
+    m.max_w = a.max_w;
+    return MOLANN_OK;
+}
+
+// The kernel's instance for a lane group (named in this order: it is the order of the instances in the code object), and its launch on
+// the entry's own pointers (`lead`, the kernel's first arguments) and the plan's tables.  `what` completes the launch info.
+#define F64_ENTRY_KERNEL(KERNEL, G) f64_entry_kernel(G, KERNEL<8>, KERNEL<16>, KERNEL<32>, KERNEL<64>)
+template <class Kernel>
+Kernel* f64_entry_kernel(int G, Kernel* k8, Kernel* k16, Kernel* k32, Kernel* k64) { return G == 8 ? k8 : G == 16 ? k16 : G == 32 ? k32 : k64; }
+
+template <class Kernel, class Args, class... Lead>
+int f64_entry_launch(Kernel* kernel, const char* name, const char* what, molann_plan* p, const F64Call<Args>& c, molann_stream_t stream, Lead... lead) {
+    const Vjp64Geom& g = c.g;
+    const int grid = grid_for(p, c.a.n_frames, g.block / g.G, 8);
+    if (g.lds > VJP64_LDS_DEFAULT) {   // one wave, one frame, more than a launch may ask for by default: raise the kernel's limit
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(g.block), g.lds, (hipStream_t)stream, lead..., p->d_align_idx, p->d_ref64, p->d_items, p->d_hv_ptr,
+                       p->d_hv_list, c.a, c.m);
+    const int rc = (int)hipGetLastError();
+    snprintf(p->last_info, sizeof(p->last_info), "%s (values + %s in one launch; %d lanes per frame) grid=%d block=%d lds=%d", name, what, g.G, grid,
+             g.block, (int)g.lds);
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int molann_plan_supports_value_and_vjp_f64(const molann_plan* p) {
+    if (!p) return MOLANN_E_NULL;
+    return f64_entry_geometry(p, F64_VJP).ok ? 1 : 0;
+}
+
+int molann_value_and_vjp_f64(molann_plan* p, const double* x, const double* grad_out, int64_t n, const double* const* W, const double* const* b,
+                             double* out, double* grad_x, molann_stream_t stream) {
+    F64Call<VjpF64Args> c;
+    const int e = f64_entry_arguments(p, F64_VJP, n, {x, grad_out, out, grad_x}, nullptr, W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_vjp_f64_kernel, c.g.G), "frames_value_vjp_f64_kernel", "vjp", p, c, stream, x, grad_out, out,
+                            grad_x);
+}
+
+int molann_plan_supports_value_and_jacobian_f64(const molann_plan* p) {
+    if (!p) return MOLANN_E_NULL;
+    return f64_entry_geometry(p, F64_JACOBIAN).ok ? 1 : 0;
+}
+
+int molann_value_and_jacobian_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b, double* out, double* jac,
+                                  molann_stream_t stream) {
+    F64Call<JacF64Args> c;
+    const int e = f64_entry_arguments(p, F64_JACOBIAN, n, {x, out, jac}, nullptr, W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_jac_f64_kernel, c.g.G), "frames_value_jac_f64_kernel", "Jacobian", p, c, stream, x, out, jac);
+}
+
+int molann_plan_supports_value_and_metric_f64(const molann_plan* p) {
+    if (!p) return MOLANN_E_NULL;
+    return f64_entry_geometry(p, F64_METRIC).ok ? 1 : 0;
+}
+
+int molann_value_and_metric_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b, const double* atom_w,
+                                double* out, double* metric, molann_stream_t stream) {
+    F64Call<JacF64Args> c;
+    const int e = f64_entry_arguments(p, F64_METRIC, n, {x, out, metric}, atom_w, W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_metric_f64_kernel, c.g.G), "frames_value_metric_f64_kernel", "metric", p, c, stream, x, out,
+                            metric, atom_w);
+}
+
+double molann_selftest_act_derivative_f64(int act, double z) { return act_derivative_f64(act, z); }
+
+int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* a, double* jac36) {
+    if (!a || !jac36) return MOLANN_E_NULL;
+    const int it = selftest_item_type(type, use_angle_value);
+    if (it < 0) return MOLANN_E_FEATURE;
+    const int w = item_width(it);
+    for (int c = 0; c < 3; ++c) {
+        V3d u[4] = {v3d(0., 0., 0.), v3d(0., 0., 0.), v3d(0., 0., 0.), v3d(0., 0., 0.)};
+        if (c < w)
+            item_unit_backward_f64(it, v3d(a[0], a[1], a[2]), v3d(a[3], a[4], a[5]), v3d(a[6], a[7], a[8]), v3d(a[9], a[10], a[11]), c, u);
+        for (int j = 0; j < 4; ++j) { jac36[12 * c + 3 * j] = u[j].x; jac36[12 * c + 3 * j + 1] = u[j].y; jac36[12 * c + 3 * j + 2] = u[j].z; }
+    }
+    return w;
+}
+
+} // extern "C"
