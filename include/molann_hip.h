@@ -310,6 +310,30 @@ int molann_value_and_metric_f64(molann_plan* plan, const double* x, int64_t n_fr
 /* 1 when molann_value_and_metric_f64 serves the plan (molann_value_and_jacobian_f64 serves it and out_dim <= 64), 0 otherwise. */
 int molann_plan_supports_value_and_metric_f64(const molann_plan* plan);
 
+/* Values, the energy of a harmonic restraint on them AND its gradient in ONE launch of frames_value_restraint_f64_kernel (ahead of
+ * time: no hipRTC): out[N, out_dim] = molann_value_and_vjp_f64's out, bit for bit (out_dim = feature_dim for a plan without an MLP),
+ *   energy[f] = 1/2 sum_k kappa[k] d_k^2,   d_k = out[f, k] - center[f * center_stride + k],
+ * and grad_x[N, n_inp, 3] = d energy / d x = J^T (kappa d) - the gradient, as molann_value_and_vjp_f64's grad_x: forces are its
+ * negative - everything in double.  Where period[k] > 0 output k is periodic and d_k is wrapped to d_k - period[k] rint(d_k /
+ * period[k]) (ties to even); period[k] <= 0: not periodic, so one row serves angles next to distances.  Where flat[k] > 0 the well
+ * has a flat bottom of that half-width: d_k = 0 for |d_k| <= flat[k], copysign(|d_k| - flat[k], d_k) beyond it.  A NaN stays a NaN
+ * (in its frame's out, energy and grad_x only).  center: out_dim doubles for all frames (center_stride 0) or a row per frame
+ * (center_stride = out_dim); any other stride: MOLANN_E_DESC.  kappa: out_dim doubles, any sign.  period, flat: out_dim doubles
+ * each, or NULL for none.  All on the device.  The cotangent kappa d is formed in the lanes that computed out - what
+ * molann_value_and_vjp_f64 cannot do, because its cotangent must exist before the launch; with period and flat NULL grad_x has the
+ * bits of molann_value_and_vjp_f64 for grad_out = kappa * (out - center).  W, b as molann_value_and_vjp_f64 takes them.  Parameters,
+ * centres and stiffnesses are data.  energy[f] is one sum in a fixed order, every row of grad_x is stored once (zeros for atoms the
+ * plan does not touch): no atomics, the same bits on every run.  Every plan molann_value_and_vjp_f64 serves, unless one frame's rows
+ * (that call's + out_dim, in doubles) exceed the LDS of a compute unit: MOLANN_E_UNSUPPORTED; MOLANN_E_STAGE for a plan without
+ * items.  n_frames < 0: MOLANN_E_DESC; n_frames == 0: nothing is read or launched.  All pointers 8-byte aligned, contiguous.  The
+ * call only enqueues on `stream` (no workspace, no event): thread-safe and capturable. */
+int molann_value_and_restraint_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                                   const double* center, int64_t center_stride, const double* kappa, const double* period,
+                                   const double* flat, double* out, double* energy, double* grad_x, molann_stream_t stream);
+
+/* 1 when molann_value_and_restraint_f64 serves the plan (feature items, and a frame's rows fit the LDS), 0 otherwise. */
+int molann_plan_supports_value_and_restraint_f64(const molann_plan* plan);
+
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
  * is fused into the lane kernel, and large-frame plans with a head within the fused MLP's limits (the features are written
@@ -370,6 +394,9 @@ int molann_selftest_kabsch_backward(const double* H9, const float* R9, const flo
 float molann_selftest_act_derivative(int act, float z);
 /* the float64 head's derivative of activation `act` at the pre-activation z (all nine codes) */
 double molann_selftest_act_derivative_f64(int act, double z);
+/* one output's term of molann_value_and_restraint_f64, the function its kernel calls: returns 1/2 kappa d^2 and stores dy = kappa d
+ * (d = y - z, wrapped where period > 0, cut where flat > 0); dy may be NULL */
+double molann_selftest_restraint_f64(double y, double z, double kappa, double period, double flat, double* dy);
 /* the unit-cotangent local Jacobian frames_value_jac_f64_kernel combines: jac36[c][j][xyz] = d(output column c of the item) /
  * d(atom j) for the item's 4 atoms (rows past the item's width are 0); returns the width */
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* atoms_xyz, double* jac36);

@@ -107,6 +107,8 @@ def lib():
             "molann_plan_supports_value_and_jacobian_f64": (i32, [vp]),
             "molann_value_and_metric_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp, vp]),
             "molann_plan_supports_value_and_metric_f64": (i32, [vp]),
+            "molann_value_and_restraint_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+            "molann_plan_supports_value_and_restraint_f64": (i32, [vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -121,6 +123,7 @@ def lib():
             "molann_selftest_kabsch_backward": (i32, [vp, vp, vp, vp]),
             "molann_selftest_act_derivative": (f32, [i32, f32]),
             "molann_selftest_act_derivative_f64": (ctypes.c_double, [i32, ctypes.c_double]),
+            "molann_selftest_restraint_f64": (ctypes.c_double, [ctypes.c_double] * 5 + [ctypes.POINTER(ctypes.c_double)]),
             "molann_selftest_item_jacobian_f64": (i32, [i32, i32, vp, vp]),
             "molann_features_jvp_f32": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
             "molann_features_jvp_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
@@ -394,6 +397,25 @@ class Plan(object):
         self._launch("molann_value_and_metric_f64", x.data_ptr(), x.shape[0], W, B,
                      atom_weights.data_ptr() if atom_weights is not None else None, out.data_ptr(), metric.data_ptr())
         return out, metric
+
+    def supports_value_and_restraint_f64(self):
+        """True when `value_and_restraint_f64` serves this plan: feature items, and a frame's rows (the forces' and one cotangent
+        row of d_out) fit the LDS (nothing is built)."""
+        return lib().molann_plan_supports_value_and_restraint_f64(self._handle) == 1
+
+    def value_and_restraint_f64(self, x, weights, biases, center, kappa, period, flat, out, energy, grad_x, center_stride=None):
+        """out[N, d_out], energy[N] = 1/2 sum_k kappa_k d_k^2 (d = out - center, wrapped by `period`, cut by `flat`) and grad_x[N, n_inp, 3]
+        = d energy / d x in float64, one launch of frames_value_restraint_f64_kernel.  `weights` / `biases` as `value_and_vjp_f64`
+        takes them; `center` holds d_out float64 values for all frames or [N, d_out] (`center_stride`: 0 or d_out, by default told from
+        center's size); `kappa` d_out values; `period`, `flat` d_out values or None.  All on x's device."""
+        W, B = _layer_pointers(weights, biases)
+        d_out = out.numel() // max(x.shape[0], 1)
+        if center_stride is None:
+            center_stride = 0 if center.numel() == d_out else d_out
+        self._launch("molann_value_and_restraint_f64", x.data_ptr(), x.shape[0], W, B, center.data_ptr(), center_stride, kappa.data_ptr(),
+                     period.data_ptr() if period is not None else None, flat.data_ptr() if flat is not None else None, out.data_ptr(),
+                     energy.data_ptr(), grad_x.data_ptr())
+        return out, energy, grad_x
 
     def forward_train(self, x, out, features):
         """`forward_packed` that also keeps the features (for `mlp_backward` + `features_backward`)."""

@@ -624,6 +624,7 @@ class _PlanOwner(object):
         state.pop("_plan_cache", None)
         state.pop("_fast", None)
         state.pop("_fp", None)
+        state.pop("_flat_key", None)
         return state
 
     def __deepcopy__(self, memo):
@@ -632,7 +633,7 @@ class _PlanOwner(object):
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k not in ("_plan_cache", "_fast", "_fp"):
+            if k not in ("_plan_cache", "_fast", "_fp", "_flat_key"):
                 new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
@@ -900,15 +901,18 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
     return out
 
 
-# ---- The calls that give the values and a derivative in one launch: MolANN.value_and_vjp / value_and_jacobian / value_and_metric and
-# PreprocessingANN.value_and_metric.  What differs between them, by kind; the checks and the two ways to the kernel are written once below.
-_VJP, _JACOBIAN, _METRIC = 0, 1, 2
+# ---- The calls that give the values and a derivative in one launch: MolANN.value_and_vjp / value_and_jacobian / value_and_metric /
+# value_and_restraint and PreprocessingANN.value_and_metric / value_and_restraint.  What differs between them, by kind; the checks and
+# the two ways to the kernel are written once below.
+_VJP, _JACOBIAN, _METRIC, _RESTRAINT = 0, 1, 2, 3
 _JACOBIAN_ROUTE = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
 _METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
-_ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric")
-_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE)       # the route that remains where the call refuses
-_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)")             # what `into` holds
-_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric")          # the dispatcher operator, in MolANN._fast_state
+_RESTRAINT_ROUTE = "use `model(x)`, form `kappa * d` and the energy with torch, then `value_and_vjp`"
+_RESTRAINT_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, form the energy with torch and take torch.autograd.grad"
+_ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint")
+_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE)       # the route that remains where the call refuses
+_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)")            # what `into` holds
+_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint")            # the dispatcher operator, in MolANN._fast_state
 
 
 def _check_into(name, x, into, dtype, out_dim, second_shape, pair):
@@ -925,6 +929,66 @@ def _check_into(name, x, into, dtype, out_dim, second_shape, pair):
             or y.device != x.device or second.device != x.device:
         raise ValueError("%s: `into` must be contiguous {[%d, %d], %s} on %s" % (name, x.shape[0], out_dim, list(second_shape), x.device))
     return y, second
+
+
+def _check_into_triple(name, x, into, out_dim):
+    """`into` of value_and_restraint, before any launch, with `_check_into`'s checks: a triple of contiguous float64 tensors on x's
+    device that hold [N, out_dim], [N] and x's elements.  Returns the triple, (None, None, None) for None."""
+    if into is None:
+        return None, None, None
+    if len(into) != 3 or not all(isinstance(t, torch.Tensor) for t in into):
+        raise TypeError("%s: `into` must be a triple of tensors %s" % (name, _ONE_LAUNCH_PAIR[_RESTRAINT]))
+    if any(t.dtype != torch.float64 for t in into):
+        raise TypeError("%s: `into` must be float64 like x; got %s" % (name, ", ".join(str(t.dtype) for t in into)))
+    n = x.shape[0]
+    counts = (n * out_dim, n, x.numel())
+    if not all(t.is_contiguous() and t.numel() == c and t.device == x.device for t, c in zip(into, counts)):
+        raise ValueError("%s: `into` must be contiguous {[%d, %d], [%d], %s} on %s" % (name, n, out_dim, n, list(x.shape), x.device))
+    return tuple(into)
+
+
+def _restraint_row(name, what, v, x, shapes):
+    """One argument of value_and_restraint on its way to what the kernel reads (float64, contiguous, on x's device, of one of
+    `shapes`): a float64 tensor on x's device passes as it is; a tensor of another floating dtype, a number (filling the row) or a
+    sequence will be converted, which costs a launch.  This is the check: `_check_restraint_args` converts after all of them."""
+    if isinstance(v, torch.Tensor):
+        if not v.dtype.is_floating_point:
+            raise TypeError("%s: `%s` must be a floating-point tensor; got %s" % (name, what, v.dtype))
+        if v.device != x.device:
+            raise ValueError("%s: `%s` must be on %s; got %s" % (name, what, x.device, v.device))
+        t = v.detach()
+    elif isinstance(v, (int, float)) and not isinstance(v, bool):
+        t = torch.full(shapes[0], float(v), dtype=torch.float64)
+    else:
+        try:
+            t = torch.as_tensor(v, dtype=torch.float64)
+        except (TypeError, ValueError, RuntimeError):
+            raise TypeError("%s: `%s` must be a tensor, a number or a sequence of numbers; got %s" % (name, what, type(v).__name__))
+    if tuple(t.shape) not in shapes:
+        raise ValueError("%s: `%s` must have shape %s; got %s" % (name, what, " or ".join(str(list(sh)) for sh in shapes), list(t.shape)))
+    return t
+
+
+def _check_restraint_args(name, x, out_dim, center, kappa, period, flat, into, owner=None):
+    """The `center`, `kappa`, `period`, `flat` and `into` checks of value_and_restraint, all before any launch on x's device; returns
+    (center, kappa, period, flat, y, energy, dx) as the kernel takes them (None where they are).  A negative `flat` is a ValueError:
+    host values are looked at as they are, a device tensor is read back once and remembered on `owner` until it is written to."""
+    n = x.shape[0]
+    rows = [_restraint_row(name, "center", center, x, ((out_dim,), (n, out_dim))),
+            _restraint_row(name, "kappa", kappa, x, ((out_dim,),)),
+            None if period is None else _restraint_row(name, "period", period, x, ((out_dim,),)),
+            None if flat is None else _restraint_row(name, "flat", flat, x, ((out_dim,),))]
+    if flat is not None:
+        key = owner.__dict__.get("_flat_key") if owner is not None and isinstance(flat, torch.Tensor) else None
+        if key is None or not key.matches(flat):
+            if bool((rows[3] < 0).any()):
+                raise ValueError("%s: `flat` holds the half-widths of the flat bottoms and must not be negative" % name)
+            if owner is not None and isinstance(flat, torch.Tensor) and flat.is_cuda:
+                owner.__dict__["_flat_key"] = _TensorKey(flat)
+    triple = _check_into_triple(name, x, into, out_dim)
+    rows = [t if t is None or (t.dtype == torch.float64 and t.device == x.device and t.is_contiguous())
+            else t.to(device=x.device, dtype=torch.float64).contiguous() for t in rows]
+    return tuple(rows) + triple
 
 
 def _check_grad_out(name, x, out_dim, grad_out):
@@ -952,10 +1016,11 @@ def _check_metric_args(name, x, n_inp, out_dim, weights, into):
     return (weights,) + _check_into(name, x, into, torch.float64, out_dim, (x.shape[0], out_dim, out_dim), _ONE_LAUNCH_PAIR[_METRIC])
 
 
-def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al):
+def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=None):
     """The float64 one-launch calls after the caller's gate (a HIP tensor, modules one plan serves), in this order: x's shape, float64
     x, float64 head (the alignment's ref_x where there is no head) on x's device, x detached and contiguous, the extra argument
-    (`grad_out`, the metric's atom weights), `into`.  Returns (x, extra, y, second, second's shape), y and second None without `into`."""
+    (`grad_out`, the metric's atom weights, the restraint's (center, kappa, period, flat)), `into`.  Returns (x, extra, y, second,
+    second's shape), y and second None without `into`; the restraint's second is the pair (energy, dx)."""
     name = _ONE_LAUNCH_NAME[kind]
     _check_input(x, n_inp)
     if x.dtype != torch.float64:
@@ -979,6 +1044,9 @@ def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al):
             raise TypeError("%s: grad_out must be a floating-point tensor; got %s" % (name, extra.dtype))
     elif kind == _JACOBIAN:
         shape = (n, out_dim, n_inp, 3)
+    elif kind == _RESTRAINT:
+        checked = _check_restraint_args(name, x, out_dim, *extra, into, owner=owner)
+        return x, checked[:4], checked[4], (checked[5], checked[6]) if checked[4] is not None else None, (n, n_inp, 3)
     else:
         shape = (n, out_dim, out_dim)
         extra = _check_atom_weights(name, x, n_inp, extra)
@@ -992,7 +1060,11 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
     """The ctypes way to the kernel of a float64 one-launch call whose arguments `_one_launch_arguments` has checked."""
     plan = entry.plan
     with torch.cuda.device(x.device):
-        if kind != _VJP and not (plan.supports_value_and_jacobian_f64() if kind == _JACOBIAN else plan.supports_value_and_metric_f64()):
+        if kind == _RESTRAINT:
+            if not plan.supports_value_and_restraint_f64():
+                raise NotImplementedError("value_and_restraint: one frame's rows exceed the LDS of a compute unit for this model; "
+                                          + _RESTRAINT_ROUTE)
+        elif kind != _VJP and not (plan.supports_value_and_jacobian_f64() if kind == _JACOBIAN else plan.supports_value_and_metric_f64()):
             if kind == _JACOBIAN:
                 raise NotImplementedError("value_and_jacobian: one frame's rows exceed the LDS of a compute unit for this model; "
                                           + _JACOBIAN_ROUTE)
@@ -1004,6 +1076,13 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
         if y is None:
             y = torch.empty((x.shape[0], out_dim), dtype=torch.float64, device=x.device)
             second = torch.empty(shape, dtype=torch.float64, device=x.device)
+            if kind == _RESTRAINT:
+                second = (torch.empty((x.shape[0],), dtype=torch.float64, device=x.device), second)
+        if kind == _RESTRAINT:
+            if x.shape[0] > 0:
+                plan.value_and_restraint_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
+                                             *extra, y, *second, center_stride=out_dim if extra[0].dim() == 2 else 0)
+            return (y,) + tuple(second)
         if x.shape[0] > 0:
             W = [lin.weight.detach().contiguous() for lin in lins]
             B = [lin.bias.detach().contiguous() for lin in lins]
@@ -1067,6 +1146,32 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
             return _capi.Plan(fl.input_atom_num, align_idx=al._local_align_atom_indices, ref_x=al.ref_x, features=spec, use_angle_value=uav)
 
         return _one_launch_ctypes(_METRIC, _get_entry(self, x, "features", build), x, weights, y, M, shape, d, (), al)
+
+    def value_and_restraint(self, x, center, kappa, period=None, flat=None, into=None):
+        """``(feat, energy, dx)``: `MolANN.value_and_restraint` on the features themselves, float64, in ONE kernel launch
+        (`molann_value_and_restraint_f64`, frames_value_restraint_f64_kernel, on this module's float64 feature plan; no head).
+        ``energy[f] = 1/2 sum_k kappa_k d_k^2`` with ``d = feat - center`` and ``dx = d energy / d x``; forces are ``-dx``.  Umbrella
+        sampling on raw dihedral angles: ``use_angle_value=True`` and ``period = 2 pi``.  ``center`` [d_feat] or [N, d_feat], ``kappa``
+        a float or [d_feat], ``period`` / ``flat`` None or [d_feat], as `MolANN.value_and_restraint` takes them (a float64 tensor on
+        x's device passes as it is; every conversion costs a launch).  No autograd graph is recorded; ``into=(feat, energy, dx)``
+        reuses the caller's buffers.  The same bits on every call.  Out of scope: float32, a `GraphedForces` replay, other bias shapes,
+        gradients with respect to centres or stiffnesses."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and self._fusable()):
+            raise NotImplementedError("value_and_restraint needs a FeatureLayer behind an AlignmentLayer or none, float64, on a HIP tensor; "
+                                      "otherwise " + _RESTRAINT_FEATURES_ROUTE)
+        fl = self.feature_layer
+        al = self.align_layer if isinstance(self.align_layer, AlignmentLayer) else None
+        d = fl.output_dimension()
+        x, extra, y, second, shape = _one_launch_arguments(_RESTRAINT, x, (center, kappa, period, flat), into, fl.input_atom_num, d, (), al,
+                                                           owner=self)
+        spec, uav = _feature_spec(fl)
+
+        def build():
+            if al is None:
+                return _capi.Plan(fl.input_atom_num, features=spec, use_angle_value=uav)
+            return _capi.Plan(fl.input_atom_num, align_idx=al._local_align_atom_indices, ref_x=al.ref_x, features=spec, use_angle_value=uav)
+
+        return _one_launch_ctypes(_RESTRAINT, _get_entry(self, x, "features", build), x, extra, y, second, shape, d, (), al)
 
     def __prepare_scriptable__(self):
         if not self._fusable():
@@ -1187,11 +1292,13 @@ class MolANN(_PlanOwner, torch.nn.Module):
         """A float64 one-launch call of a model the gate has passed: the arguments are checked once for both ways to the kernel (the
         dispatcher operator where that library is built, else the ctypes plan)."""
         al, lins, out_dim = st["al"], st["linears"], st["out_dim"]
-        x, extra, y, second, shape = _one_launch_arguments(kind, x, extra, into, st["fl"].input_atom_num, out_dim, lins, al)
+        x, extra, y, second, shape = _one_launch_arguments(kind, x, extra, into, st["fl"].input_atom_num, out_dim, lins, al, owner=self)
         if st["op"] is None:
             return _one_launch_ctypes(kind, st["entry"](), x, extra, y, second, shape, out_dim, lins, al)
         op, ref = st[_ONE_LAUNCH_OP[kind]], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"]
         W, B, into = [lin.weight for lin in lins], [lin.bias for lin in lins], list(into) if into is not None else []
+        if kind == _RESTRAINT:
+            return tuple(op(x, st["handle"], ref, W, B, *extra, into))
         y, second = op(x, st["handle"], ref, W, B, into) if kind == _JACOBIAN else op(x, st["handle"], ref, W, B, extra, into)
         return y, second
 
@@ -1218,6 +1325,26 @@ class MolANN(_PlanOwner, torch.nn.Module):
         (`PreprocessingANN.value_and_metric`), ``sum_a w_a |grad_a y_k|^2 = dF_k G dF_k^T``, ``dF = d y / d feat``.
         `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at most 64 outputs."""
         return self._one_launch_f64(_METRIC, self._one_launch_state(x, _METRIC, "float64"), x, weights, into)
+
+    def value_and_restraint(self, x, center, kappa, period=None, flat=None, into=None):
+        """``(y, energy, dx)`` with ``y = self(x)`` [N, d_out], the energy of a harmonic restraint on it
+        ``energy[f] = 1/2 sum_k kappa_k d_k^2``, ``d_k = y[f, k] - center[f, k]`` [N], and ``dx = d energy / d x = J^T (kappa d)``
+        [N, n_inp, 3] (the gradient, like `value_and_vjp`'s dx: forces are ``-dx``), float64, in ONE kernel launch
+        (`molann_value_and_restraint_f64`, frames_value_restraint_f64_kernel): what umbrella sampling, steered MD, the string method's
+        restrained replicas and TAMD's extended variable do with a collective variable at every step.  The cotangent ``kappa d``
+        depends on y, so `value_and_vjp` needs a forward, four or five elementwise launches and then computes the forward again; here
+        it is formed in the lanes that hold y.  ``center``: [d_out] (all frames) or [N, d_out]; ``kappa``: a float or [d_out], any
+        sign; ``period``: None or [d_out], an entry > 0 wraps that output's d to ``d - P rint(d / P)`` (angles), an entry <= 0 leaves it;
+        ``flat``: None or [d_out], an entry h > 0 gives that output a flat-bottomed well (``d = 0`` for ``|d| <= h``,
+        ``copysign(|d| - h, d)`` beyond), a negative entry raises ValueError.  A float64 tensor on x's device passes as it is; a tensor
+        of another floating dtype, a Python number or a sequence is converted, and each conversion costs a launch (a device ``flat``
+        is read back once, when it is first seen or after it was written to).  ``y`` is `value_and_vjp`'s, bit for bit, and with
+        ``period=None, flat=None`` so is ``dx`` for the cotangent ``kappa * (y - center)``.  A NaN poisons its own frame only.  No
+        autograd graph is recorded (parameters are data); ``into=(y, energy, dx)`` reuses the caller's buffers.  The energy is summed
+        in a fixed order and every row of dx is stored once: the same bits on every call.  `model.double()` and a float64 x on a HIP
+        device; a model served by one fused plan.  Out of scope: float32, a `GraphedForces` replay of this launch, bias shapes other
+        than this one, gradients with respect to parameters, centres or stiffnesses."""
+        return self._one_launch_f64(_RESTRAINT, self._one_launch_state(x, _RESTRAINT, "float64"), x, (center, kappa, period, flat), into)
 
     def _tangent_present(self, x):
         if _has_tangent(x):
@@ -1273,6 +1400,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
             if st["op"] is not None:
                 st["op_vjp"], st["op_jacobian"], st["op_metric"] = (torch.ops.molann.value_and_vjp_h, torch.ops.molann.value_and_jacobian_h,
                                                                     torch.ops.molann.value_and_metric_h)
+                st["op_restraint"] = torch.ops.molann.value_and_restraint_h
                 from . import script
                 st["desc"] = script.make_desc(script.KIND_FORWARD, fl.input_atom_num,
                                               align_idx=al._local_align_atom_indices if al is not None else None,

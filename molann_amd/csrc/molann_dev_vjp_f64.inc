@@ -20,7 +20,8 @@ namespace {
 //      stored once, untouched atoms as zeros: no atomics, no zeroing pass, the same bits on every run.
 // The lanes of a frame exchange data through LDS only inside their own wave: lds_wave_sync() orders it, there is no block barrier.
 // Steps 1-3 are the device functions frame_rotation_f64 / frame_features_f64 / frame_head_forward_f64 below, shared with
-// frames_value_jac_f64_kernel (molann_dev_jac_f64.inc).
+// frames_value_jac_f64_kernel (molann_dev_jac_f64.inc); steps 4-6 are frame_head_backward_f64 / frame_rotation_vjp_f64 /
+// frame_atoms_vjp_f64, shared with frames_value_restraint_f64_kernel (molann_dev_restraint_f64.inc).
 // =============================================================================================
 struct VjpF64Args {
     long n_frames;
@@ -122,6 +123,92 @@ __device__ __forceinline__ double* frame_head_forward_f64(const F64Mlp& m, int g
     return zl;
 }
 
+// Steps 4-6 of a frame, shared with frames_value_restraint_f64_kernel (molann_dev_restraint_f64.inc): they take the cotangent row.
+// ---- 4. head backward for x only: g is the cotangent, zl is past the last hidden layer's pre-activations; returns dL/dfeat
+template <int G>
+__device__ __forceinline__ const double* frame_head_backward_f64(const F64Mlp& m, int gl, const double* g, double* zl, double* row0, double* row1) {
+    double* gn = row0;
+    for (int l = m.n_layers - 1; l >= 0; --l) {
+        const int K = m.dims[l], J = m.dims[l + 1];
+        const double* Wl = m.W[l];
+        if (l > 0) zl -= K;
+        for (int k = gl; k < K; k += G) {
+            double acc = 0.;
+            for (int j = 0; j < J; ++j) acc = fma(Wl[(long)j * K + k], g[j], acc);
+            gn[k] = l > 0 ? acc * act_derivative_f64(m.act, zl[k]) : acc;
+        }
+        lds_wave_sync();
+        g = gn;
+        gn = gn == row0 ? row1 : row0;
+    }
+    return g;
+}
+
+// ---- 5. what the items give the rotation's backward: G_H and the centroid's term for dL/dfeat = df
+template <int G>
+__device__ __forceinline__ void frame_rotation_vjp_f64(const double* __restrict__ xf, const double* __restrict__ ref64,
+                                                       const ItemDev* __restrict__ items, int n_items, int n_align, int gl, const double* df, V3d c,
+                                                       const double (&h)[9], const double (&R)[9], double (&GH)[9], V3d& cen) {
+    double GR[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
+    V3d gsum = v3d(0., 0., 0.);
+    for (int it = gl; it < n_items; it += G) {
+        const ItemDev d = items[it];
+        V3d q[4], gy[4];
+        item_backward_f64(d, xf, df, true, c, R, q, gy);
+        const int na = item_atoms(d.type);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < na) { // y = q R :  G_R += q^T g ,  g_p = g R^T
+                const V3d g = gy[j];
+                GR[0] = fma(q[j].x, g.x, GR[0]); GR[1] = fma(q[j].x, g.y, GR[1]); GR[2] = fma(q[j].x, g.z, GR[2]);
+                GR[3] = fma(q[j].y, g.x, GR[3]); GR[4] = fma(q[j].y, g.y, GR[4]); GR[5] = fma(q[j].y, g.z, GR[5]);
+                GR[6] = fma(q[j].z, g.x, GR[6]); GR[7] = fma(q[j].z, g.y, GR[7]); GR[8] = fma(q[j].z, g.z, GR[8]);
+                gsum = gsum + rotate_back(g, R);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) GR[i] = group_sum<G>(GR[i]);
+    gsum = v3d(group_sum<G>(gsum.x), group_sum<G>(gsum.y), group_sum<G>(gsum.z));
+    kabsch_rotation_backward_t<double, double>(h, R, GR, GH);
+    // H = sum_i (a_i - c) ref_i^T also depends on c through every p_i: - G_H (sum_j ref_j) / a per align atom
+    const double inv_a = 1.0 / (double)n_align;
+    const V3d t = mat_ref(GH, ref64[3 * n_align], ref64[3 * n_align + 1], ref64[3 * n_align + 2]);
+    cen = v3d(inv_a * (gsum.x + t.x), inv_a * (gsum.y + t.y), inv_a * (gsum.z + t.z));
+}
+
+// ---- 6. atoms (lanes): every row of gxf once, its terms in plan order
+template <int G>
+__device__ __forceinline__ void frame_atoms_vjp_f64(const double* __restrict__ xf, double* __restrict__ gxf, const double* __restrict__ ref64,
+                                                    const ItemDev* __restrict__ items, const int* __restrict__ hv_ptr,
+                                                    const int* __restrict__ hv_list, int n_inp, int gl, const double* df, bool has_align, V3d c,
+                                                    const double (&R)[9], const double (&GH)[9], V3d cen) {
+    for (int k = gl; k < n_inp; k += G) {
+        V3d acc = v3d(0., 0., 0.);
+        const int e1 = hv_ptr[k + 1];
+        for (int e = hv_ptr[k]; e < e1; ++e) {
+            const int code = hv_list[e];
+            if (code < 0) {
+                const int i = -code - 1;
+                acc = acc + (mat_ref(GH, ref64[3 * i], ref64[3 * i + 1], ref64[3 * i + 2]) - cen);
+            } else {
+                const ItemDev d = items[code >> 2];
+                const int j = code & 3;
+                V3d q[4], gy[4];
+                item_backward_f64(d, xf, df, has_align, c, R, q, gy);
+                V3d t = gy[3];   // slot j (selects, not an indexed load: gy stays in registers)
+                if (j == 2) t = gy[2];
+                if (j == 1) t = gy[1];
+                if (j == 0) t = gy[0];
+                acc = acc + (has_align ? rotate_back(t, R) : t);
+            }
+        }
+        gxf[3 * k] = acc.x;
+        gxf[3 * k + 1] = acc.y;
+        gxf[3 * k + 2] = acc.z;
+    }
+}
+
 template <int G>
 __global__ __launch_bounds__(256) void frames_value_vjp_f64_kernel(const double* __restrict__ x, const double* __restrict__ gout,
                                                                    double* __restrict__ out, double* __restrict__ gx,
@@ -158,79 +245,14 @@ __global__ __launch_bounds__(256) void frames_value_vjp_f64_kernel(const double*
             // ---- 3. head forward
             double* zl = frame_head_forward_f64<G>(m, gl, feat, zrows, row0, row1, of);
             // ---- 4. head backward: zl is past the last hidden layer's pre-activations
-            const double* g = gf;
-            double* gn = row0;
-            for (int l = m.n_layers - 1; l >= 0; --l) {
-                const int K = m.dims[l], J = m.dims[l + 1];
-                const double* Wl = m.W[l];
-                if (l > 0) zl -= K;
-                for (int k = gl; k < K; k += G) {
-                    double acc = 0.;
-                    for (int j = 0; j < J; ++j) acc = fma(Wl[(long)j * K + k], g[j], acc);
-                    gn[k] = l > 0 ? acc * act_derivative_f64(m.act, zl[k]) : acc;
-                }
-                lds_wave_sync();
-                g = gn;
-                gn = gn == row0 ? row1 : row0;
-            }
-            df = g;
+            df = frame_head_backward_f64<G>(m, gl, gf, zl, row0, row1);
         }
         // ---- 5. what the items give the rotation's backward
         double GH[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
         V3d cen = v3d(0., 0., 0.);
-        if (has_align) {
-            double GR[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
-            V3d gsum = v3d(0., 0., 0.);
-            for (int it = gl; it < a.n_items; it += G) {
-                const ItemDev d = items[it];
-                V3d q[4], gy[4];
-                item_backward_f64(d, xf, df, true, c, R, q, gy);
-                const int na = item_atoms(d.type);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (j < na) { // y = q R :  G_R += q^T g ,  g_p = g R^T
-                        const V3d g = gy[j];
-                        GR[0] = fma(q[j].x, g.x, GR[0]); GR[1] = fma(q[j].x, g.y, GR[1]); GR[2] = fma(q[j].x, g.z, GR[2]);
-                        GR[3] = fma(q[j].y, g.x, GR[3]); GR[4] = fma(q[j].y, g.y, GR[4]); GR[5] = fma(q[j].y, g.z, GR[5]);
-                        GR[6] = fma(q[j].z, g.x, GR[6]); GR[7] = fma(q[j].z, g.y, GR[7]); GR[8] = fma(q[j].z, g.z, GR[8]);
-                        gsum = gsum + rotate_back(g, R);
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 9; ++i) GR[i] = group_sum<G>(GR[i]);
-            gsum = v3d(group_sum<G>(gsum.x), group_sum<G>(gsum.y), group_sum<G>(gsum.z));
-            kabsch_rotation_backward_t<double, double>(h, R, GR, GH);
-            // H = sum_i (a_i - c) ref_i^T also depends on c through every p_i: - G_H (sum_j ref_j) / a per align atom
-            const double inv_a = 1.0 / (double)a.n_align;
-            const V3d t = mat_ref(GH, ref64[3 * a.n_align], ref64[3 * a.n_align + 1], ref64[3 * a.n_align + 2]);
-            cen = v3d(inv_a * (gsum.x + t.x), inv_a * (gsum.y + t.y), inv_a * (gsum.z + t.z));
-        }
+        if (has_align) frame_rotation_vjp_f64<G>(xf, ref64, items, a.n_items, a.n_align, gl, df, c, h, R, GH, cen);
         // ---- 6. atoms (lanes): every row once, its terms in plan order
-        for (int k = gl; k < a.n_inp; k += G) {
-            V3d acc = v3d(0., 0., 0.);
-            const int e1 = hv_ptr[k + 1];
-            for (int e = hv_ptr[k]; e < e1; ++e) {
-                const int code = hv_list[e];
-                if (code < 0) {
-                    const int i = -code - 1;
-                    acc = acc + (mat_ref(GH, ref64[3 * i], ref64[3 * i + 1], ref64[3 * i + 2]) - cen);
-                } else {
-                    const ItemDev d = items[code >> 2];
-                    const int j = code & 3;
-                    V3d q[4], gy[4];
-                    item_backward_f64(d, xf, df, has_align, c, R, q, gy);
-                    V3d t = gy[3];   // slot j (selects, not an indexed load: gy stays in registers)
-                    if (j == 2) t = gy[2];
-                    if (j == 1) t = gy[1];
-                    if (j == 0) t = gy[0];
-                    acc = acc + (has_align ? rotate_back(t, R) : t);
-                }
-            }
-            gxf[3 * k] = acc.x;
-            gxf[3 * k + 1] = acc.y;
-            gxf[3 * k + 2] = acc.z;
-        }
+        frame_atoms_vjp_f64<G>(xf, gxf, ref64, items, hv_ptr, hv_list, a.n_inp, gl, df, has_align, c, R, GH, cen);
         if (has_head) lds_wave_sync();   // the next frame's rows are this frame's
     }
 }

@@ -514,6 +514,28 @@ MOLANN_HD double act_derivative_f64(int act, double z) {
     }
 }
 
+// One output's term of a harmonic restraint E = 1/2 sum_k kappa_k d_k^2 (umbrella sampling, steered MD, the string method's replicas):
+// d = y - z, wrapped into [-P/2, P/2] where the output is periodic (period > 0; rint: ties to even), moved to the wall of a flat-bottomed
+// well where flat > 0 (d = 0 inside |d| <= flat, copysign(|d| - flat, d) outside; a NaN d stays NaN).  Returns 1/2 kappa d^2 and
+// dy = kappa d, the term's derivative with respect to y; kappa may have any sign.  Nothing is contracted: every operation rounds once,
+// so with no period and no flat dy is the rounded product of kappa and the rounded y - z, on the host and on the device.
+MOLANN_HD double restraint_term_f64(double y, double z, double kappa, double period, double flat, double& dy) {
+#pragma clang fp contract(off)
+    double d = y - z;
+    if (period > 0.0) {
+        const double turns = rint(d / period);
+        const double whole = period * turns;
+        d = d - whole;
+    }
+    if (flat > 0.0) {
+        const double a = fabs(d) - flat;
+        if (a > 0.0) d = copysign(a, d);
+        else if (a <= 0.0) d = 0.0;     // neither holds for a NaN, which stays
+    }
+    dy = kappa * d;
+    return 0.5 * dy * d;
+}
+
 // Backward of kabsch_rotation: given H, the rotation R it produced and G_R = dL/dR, returns G_H = dL/dH.
 // With S = R^T H (symmetric at the optimum) a perturbation dH turns R by dR = R [w]x where
 // (tr(S) I - S) w = vee(R^T dH - dH^T R); hence G_H = R [n]x, n = (tr(S) I - S)^-1 vee(M - M^T), M = R^T G_R.

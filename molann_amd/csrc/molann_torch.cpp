@@ -537,6 +537,77 @@ std::vector<at::Tensor> value_and_metric_h_hip(const at::Tensor& x_in, int64_t h
     return value_and_metric_impl(x_in, *desc_of(handle, "molann::value_and_metric_h"), ref_x, weights, biases, atom_w, into);
 }
 
+// {out, energy, grad_x}: the float64 forward's outputs, the energy of a harmonic restraint on them, energy[N] = 1/2 sum_k kappa_k d_k^2 with
+// d = out - center (wrapped where period > 0, cut where flat > 0), and its gradient grad_x[N, n_inp, 3] in ONE launch
+// (molann_value_and_restraint_f64 on the float64 Linear tensors).  Parameters, centres and stiffnesses are data.  center: [out_dim] or
+// [N, out_dim]; kappa, period, flat: [out_dim]; all float64 on x's device (the Python methods convert what is not).  `into`: none or
+// {out, energy, grad_x}.
+at::Tensor restraint_row(const char* what, const at::Tensor& t, const at::Tensor& x, int64_t cols, int64_t rows) {
+    TORCH_CHECK_TYPE(t.scalar_type() == at::kDouble, "molann::value_and_restraint: `", what, "` must be float64 (got ", t.scalar_type(), ")");
+    const bool row = t.dim() == 1 && t.size(0) == cols, per_frame = rows >= 0 && t.dim() == 2 && t.size(0) == rows && t.size(1) == cols;
+    TORCH_CHECK_VALUE((row || per_frame) && t.device() == x.device(), "molann::value_and_restraint: `", what, "` must be [", cols,
+                      rows >= 0 ? "] or [N, out_dim]" : "]", " on ", x.device());
+    return t.detach().contiguous();
+}
+std::vector<at::Tensor> value_and_restraint_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                                 const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                                                 const at::Tensor& center_in, const at::Tensor& kappa_in, const c10::optional<at::Tensor>& period_in,
+                                                 const c10::optional<at::Tensor>& flat_in, const std::vector<at::Tensor>& into) {
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_restraint is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_restraint: a forward or a features description");
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    const at::Tensor center = restraint_row("center", center_in, x, cols, n), kappa = restraint_row("kappa", kappa_in, x, cols, -1);
+    at::Tensor period, flat;
+    if (period_in.has_value() && period_in->defined()) period = restraint_row("period", *period_in, x, cols, -1);
+    if (flat_in.has_value() && flat_in->defined()) flat = restraint_row("flat", *flat_in, x, cols, -1);
+    TORCH_CHECK(into.empty() || into.size() == 3, "molann::value_and_restraint: `into` must be a triple of tensors (out, energy, grad_x)");
+    at::Tensor out, energy, gx;
+    if (into.empty()) {
+        out = at::empty({n, cols}, x.options()); energy = at::empty({n}, x.options()); gx = at::empty_like(x);
+    } else {
+        out = into[0]; energy = into[1]; gx = into[2];
+        const int64_t counts[3] = {n * cols, n, x.numel()};
+        for (int i = 0; i < 3; ++i) {
+            TORCH_CHECK_TYPE(into[i].scalar_type() == at::kDouble, "molann::value_and_restraint: `into` must be float64 like x");
+            TORCH_CHECK_VALUE(into[i].is_contiguous() && into[i].numel() == counts[i] && into[i].device() == x.device(),
+                              "molann::value_and_restraint: `into` must be contiguous {[N, out_dim], [N], [N, n_inp, 3]} on x's device");
+        }
+    }
+    F64Linears lin;
+    f64_linears("molann::value_and_restraint", *e, x, weights, biases, lin, ": call .double()");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_restraint_f64(e->plan) == 1,
+                                "molann::value_and_restraint: one frame's rows exceed the LDS of a compute unit for this model; use run, form "
+                                "kappa * d and the energy with torch, then value_and_vjp");
+    if (n == 0) return {out, energy, gx};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_restraint_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), center.data_ptr<double>(),
+                                         center.dim() == 2 ? cols : 0, kappa.data_ptr<double>(), period.defined() ? period.data_ptr<double>() : nullptr,
+                                         flat.defined() ? flat.data_ptr<double>() : nullptr, out.data_ptr<double>(), energy.data_ptr<double>(),
+                                         gx.data_ptr<double>(), stream),
+          "molann_value_and_restraint_f64");
+    return {out, energy, gx};
+}
+std::vector<at::Tensor> value_and_restraint_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                                std::vector<at::Tensor> biases, const at::Tensor& center, const at::Tensor& kappa,
+                                                const c10::optional<at::Tensor>& period, const c10::optional<at::Tensor>& flat,
+                                                std::vector<at::Tensor> into) {
+    return value_and_restraint_impl(x_in, desc, ref_x, weights, biases, center, kappa, period, flat, into);
+}
+std::vector<at::Tensor> value_and_restraint_h_hip(const at::Tensor& x_in, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                                  std::vector<at::Tensor> biases, const at::Tensor& center, const at::Tensor& kappa,
+                                                  const c10::optional<at::Tensor>& period, const c10::optional<at::Tensor>& flat,
+                                                  std::vector<at::Tensor> into) {
+    return value_and_restraint_impl(x_in, *desc_of(handle, "molann::value_and_restraint_h"), ref_x, weights, biases, center, kappa, period, flat, into);
+}
+
 // The fused forward that also keeps the features: {out, features} - or {out, empty} where the plan has no such twin of its
 // kernel (molann_plan_backward_kind != 1 ... != 2 plans recompute in molann_backward_f32).  float32 fused plans.
 std::vector<at::Tensor> run_train_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -1160,6 +1231,10 @@ TORCH_LIBRARY(molann, m) {
     m.def("value_and_jacobian_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor[] into) -> Tensor[]");
     m.def("value_and_jacobian(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor[] into) -> Tensor[]");
     m.def("value_and_metric_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? atom_w, Tensor[] into) -> Tensor[]");
+    m.def("value_and_restraint_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor center, Tensor kappa, Tensor? period, "
+          "Tensor? flat, Tensor[] into) -> Tensor[]");
+    m.def("value_and_restraint(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor center, Tensor kappa, Tensor? period, "
+          "Tensor? flat, Tensor[] into) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
     m.def("run_head(Tensor feat, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases) -> Tensor", run_head);
@@ -1184,6 +1259,8 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_jacobian", value_and_jacobian_hip);
     m.impl("value_and_jacobian_h", value_and_jacobian_h_hip);
     m.impl("value_and_metric_h", value_and_metric_h_hip);
+    m.impl("value_and_restraint", value_and_restraint_hip);
+    m.impl("value_and_restraint_h", value_and_restraint_h_hip);
 }
 
 TORCH_LIBRARY_IMPL(molann, Autograd, m) { m.impl("run", run_autograd); }

@@ -1,8 +1,9 @@
 // molann_value_f64.inc - part of libmolann_hip.so, included by molann_kernels.hip after molann_hvp.inc.  The float64 calls that give the
 // values and a derivative in one launch (see include/molann_hip.h): molann_value_and_vjp_f64 (forces, frames_value_vjp_f64_kernel of
-// molann_dev_vjp_f64.inc), molann_value_and_jacobian_f64 (frames_value_jac_f64_kernel, molann_dev_jac_f64.inc) and
-// molann_value_and_metric_f64 (frames_value_metric_f64_kernel, molann_dev_metric_f64.inc).  One argument front end, one launch and
-// one dispatch over the lane group serve the three; an entry names its kernel, its pointers and its rows.
+// molann_dev_vjp_f64.inc), molann_value_and_jacobian_f64 (frames_value_jac_f64_kernel, molann_dev_jac_f64.inc),
+// molann_value_and_metric_f64 (frames_value_metric_f64_kernel, molann_dev_metric_f64.inc) and molann_value_and_restraint_f64
+// (frames_value_restraint_f64_kernel, molann_dev_restraint_f64.inc).  One argument front end, one launch and one dispatch over the
+// lane group serve the four; an entry names its kernel, its pointers and its rows.
 namespace {
 
 constexpr size_t VJP64_LDS_DEFAULT = 65536;    // dynamic LDS a launch may ask for as it is
@@ -10,7 +11,7 @@ constexpr size_t VJP64_LDS_CU = 163840;        // the LDS of a gfx950 compute un
 // the widest output the metric kernel's chunk pairs serve: d_out / JAC64_KC chunks, every pair of them a pass over the frame's atoms
 constexpr int METRIC64_MAX_D_OUT = 64;
 
-enum F64Entry { F64_VJP, F64_JACOBIAN, F64_METRIC };
+enum F64Entry { F64_VJP, F64_JACOBIAN, F64_METRIC, F64_RESTRAINT };
 
 struct Vjp64Geom {
     int G, block;       // lanes per frame, threads per block
@@ -28,6 +29,13 @@ inline void vjp64_rows(const molann_plan* p, int& max_w, int& per_frame) {
         if (l > 0) z += p->dims[l];
     }
     const long total = (long)p->d_feat + z + 2l * max_w;
+    per_frame = total > (1l << 28) ? (1 << 28) : (int)total;
+}
+
+// doubles of LDS per frame of the restraint: the forces' rows and the cotangent row of d_out, which it has with or without a head
+inline void restraint64_rows(const molann_plan* p, int& max_w, int& per_frame) {
+    vjp64_rows(p, max_w, per_frame);
+    const long total = (long)per_frame + (p->n_layers > 0 ? p->dims[p->n_layers] : p->d_feat);
     per_frame = total > (1l << 28) ? (1 << 28) : (int)total;
 }
 
@@ -67,11 +75,13 @@ inline Vjp64Geom vjp64_geometry_rows(const molann_plan* p, int max_w, int per_fr
 // the kernel arguments' rows, by the struct that carries them
 inline void f64_entry_rows(const molann_plan* p, VjpF64Args& a) { vjp64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, JacF64Args& a) { jac64_rows(p, a.max_w, a.z_w, a.lds_per_frame); }
+inline void f64_entry_rows(const molann_plan* p, RestraintF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
 
-// geometry for this entry: the forces' rows or the Jacobian's, and the metric's cap on the outputs
+// geometry for this entry: the forces' rows, the restraint's or the Jacobian's, and the metric's cap on the outputs
 inline Vjp64Geom f64_entry_geometry(const molann_plan* p, F64Entry entry) {
     int max_w, z_w, per_frame;
     if (entry == F64_VJP) vjp64_rows(p, max_w, per_frame);
+    else if (entry == F64_RESTRAINT) restraint64_rows(p, max_w, per_frame);
     else jac64_rows(p, max_w, z_w, per_frame);
     Vjp64Geom g = vjp64_geometry_rows(p, max_w, per_frame);
     if (entry == F64_METRIC && (p->n_layers > 0 ? p->dims[p->n_layers] : p->d_feat) > METRIC64_MAX_D_OUT) g.ok = false;
@@ -85,16 +95,17 @@ struct F64Call {    // what a launch takes besides the caller's pointers
     F64Mlp m;
 };
 
-// The argument front end of the three entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
-// must be there (`required`), their and `optional`'s 8-byte alignment (a null `optional` passes), items, the head's tensors layer
-// by layer, geometry.  Nothing is dereferenced but W and b.
+// The argument front end of the four entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
+// must be there (`required`), their and the `optional` ones' 8-byte alignment (a null optional pointer passes), items, the head's
+// tensors layer by layer, geometry.  Nothing is dereferenced but W and b.
 template <class Args>
-int f64_entry_arguments(const molann_plan* p, F64Entry entry, int64_t n, std::initializer_list<const void*> required, const void* optional,
-                        const double* const* W, const double* const* b, F64Call<Args>& c) {
+int f64_entry_arguments(const molann_plan* p, F64Entry entry, int64_t n, std::initializer_list<const void*> required,
+                        std::initializer_list<const void*> optional, const double* const* W, const double* const* b, F64Call<Args>& c) {
     if (!p) return MOLANN_E_NULL;
     if (n < 0) return MOLANN_E_DESC;
     if (n == 0) return MOLANN_OK;
-    uintptr_t low_bits = (uintptr_t)optional;
+    uintptr_t low_bits = 0;
+    for (const void* ptr : optional) low_bits |= (uintptr_t)ptr;
     for (const void* ptr : required) {
         if (!ptr) return MOLANN_E_NULL;
         low_bits |= (uintptr_t)ptr;
@@ -158,7 +169,7 @@ int molann_plan_supports_value_and_vjp_f64(const molann_plan* p) {
 int molann_value_and_vjp_f64(molann_plan* p, const double* x, const double* grad_out, int64_t n, const double* const* W, const double* const* b,
                              double* out, double* grad_x, molann_stream_t stream) {
     F64Call<VjpF64Args> c;
-    const int e = f64_entry_arguments(p, F64_VJP, n, {x, grad_out, out, grad_x}, nullptr, W, b, c);
+    const int e = f64_entry_arguments(p, F64_VJP, n, {x, grad_out, out, grad_x}, {}, W, b, c);
     if (e != MOLANN_OK || n == 0) return e;
     return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_vjp_f64_kernel, c.g.G), "frames_value_vjp_f64_kernel", "vjp", p, c, stream, x, grad_out, out,
                             grad_x);
@@ -172,7 +183,7 @@ int molann_plan_supports_value_and_jacobian_f64(const molann_plan* p) {
 int molann_value_and_jacobian_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b, double* out, double* jac,
                                   molann_stream_t stream) {
     F64Call<JacF64Args> c;
-    const int e = f64_entry_arguments(p, F64_JACOBIAN, n, {x, out, jac}, nullptr, W, b, c);
+    const int e = f64_entry_arguments(p, F64_JACOBIAN, n, {x, out, jac}, {}, W, b, c);
     if (e != MOLANN_OK || n == 0) return e;
     return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_jac_f64_kernel, c.g.G), "frames_value_jac_f64_kernel", "Jacobian", p, c, stream, x, out, jac);
 }
@@ -185,13 +196,37 @@ int molann_plan_supports_value_and_metric_f64(const molann_plan* p) {
 int molann_value_and_metric_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b, const double* atom_w,
                                 double* out, double* metric, molann_stream_t stream) {
     F64Call<JacF64Args> c;
-    const int e = f64_entry_arguments(p, F64_METRIC, n, {x, out, metric}, atom_w, W, b, c);
+    const int e = f64_entry_arguments(p, F64_METRIC, n, {x, out, metric}, {atom_w}, W, b, c);
     if (e != MOLANN_OK || n == 0) return e;
     return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_metric_f64_kernel, c.g.G), "frames_value_metric_f64_kernel", "metric", p, c, stream, x, out,
                             metric, atom_w);
 }
 
+int molann_plan_supports_value_and_restraint_f64(const molann_plan* p) {
+    if (!p) return MOLANN_E_NULL;
+    return f64_entry_geometry(p, F64_RESTRAINT).ok ? 1 : 0;
+}
+
+int molann_value_and_restraint_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b, const double* center,
+                                   int64_t center_stride, const double* kappa, const double* period, const double* flat, double* out, double* energy,
+                                   double* grad_x, molann_stream_t stream) {
+    F64Call<RestraintF64Args> c;
+    const int e = f64_entry_arguments(p, F64_RESTRAINT, n, {x, center, kappa, out, energy, grad_x}, {period, flat}, W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    if (center_stride != 0 && center_stride != c.a.d_out) return MOLANN_E_DESC;
+    c.a.center_stride = (long)center_stride;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_restraint_f64_kernel, c.g.G), "frames_value_restraint_f64_kernel", "restraint", p, c, stream,
+                            x, center, kappa, period, flat, out, energy, grad_x);
+}
+
 double molann_selftest_act_derivative_f64(int act, double z) { return act_derivative_f64(act, z); }
+
+double molann_selftest_restraint_f64(double y, double z, double kappa, double period, double flat, double* dy) {
+    double cot;
+    const double e = restraint_term_f64(y, z, kappa, period, flat, cot);
+    if (dy) *dy = cot;
+    return e;
+}
 
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* a, double* jac36) {
     if (!a || !jac36) return MOLANN_E_NULL;
