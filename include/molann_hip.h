@@ -334,6 +334,31 @@ int molann_value_and_restraint_f64(molann_plan* plan, const double* x, int64_t n
 /* 1 when molann_value_and_restraint_f64 serves the plan (feature items, and a frame's rows fit the LDS), 0 otherwise. */
 int molann_plan_supports_value_and_restraint_f64(const molann_plan* plan);
 
+/* Values, a metadynamics bias on them - a sum of Gaussian hills - AND its gradient in ONE launch of frames_value_hills_f64_kernel
+ * (ahead of time: no hipRTC): out[N, out_dim] = molann_value_and_vjp_f64's out, bit for bit (out_dim = feature_dim for a plan
+ * without an MLP),
+ *   bias[f] = sum_h heights[h] exp(-1/2 sum_k (d_hk / sigma_hk)^2),   d_hk = out[f, k] - centers[h * out_dim + k],
+ * and grad_x[N, n_inp, 3] = d bias / d x = J^T (d bias / d out) - the gradient, as molann_value_and_vjp_f64's grad_x: forces are its
+ * negative - everything in double.  Where period[k] > 0 output k is periodic and d_hk is wrapped to d - period[k] rint(d /
+ * period[k]) (ties to even, molann_value_and_restraint_f64's rule); period[k] <= 0: not periodic.  centers: n_hills rows of out_dim
+ * doubles; heights: n_hills doubles of any sign; sigma_hk = sigma[h * sigma_stride + k] > 0 (not checked here): one row of out_dim
+ * widths for every hill (sigma_stride 0) or a row per hill (sigma_stride = out_dim, adaptive widths); any other stride:
+ * MOLANN_E_DESC.  period: out_dim doubles, or NULL for none.  All on the device; the caller appends hills to its own table between
+ * steps and passes the count - the table is read at launch, nothing is cached.  n_hills == 0 (the first step of a run) stores out,
+ * bias = 0 and grad_x = 0, and centers, heights and sigma may then be NULL; n_hills < 0: MOLANN_E_DESC.  No cutoff: a far hill's exp
+ * underflows to 0.  A NaN in a frame's out makes that frame's bias and grad_x NaN and no other's.  A frame's hills are summed in a
+ * fixed order, every row of grad_x is stored once (zeros for atoms the plan does not touch): no atomics, the same bits on every run,
+ * whatever n_frames.  W, b as molann_value_and_vjp_f64 takes them; parameters and hills are data.  Every plan
+ * molann_value_and_restraint_f64 serves with out_dim <= 8 (the cotangent sums of a lane live in registers): MOLANN_E_UNSUPPORTED
+ * otherwise; MOLANN_E_STAGE for a plan without items.  n_frames < 0: MOLANN_E_DESC; n_frames == 0: nothing is read or launched.  All
+ * pointers 8-byte aligned, contiguous.  The call only enqueues on `stream` (no workspace, no event): thread-safe and capturable. */
+int molann_value_and_hills_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                               const double* centers, const double* heights, int64_t n_hills, const double* sigma, int64_t sigma_stride,
+                               const double* period, double* out, double* bias, double* grad_x, molann_stream_t stream);
+
+/* 1 when molann_value_and_hills_f64 serves the plan (molann_value_and_restraint_f64 serves it and out_dim <= 8), 0 otherwise. */
+int molann_plan_supports_value_and_hills_f64(const molann_plan* plan);
+
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
  * is fused into the lane kernel, and large-frame plans with a head within the fused MLP's limits (the features are written
@@ -397,6 +422,11 @@ double molann_selftest_act_derivative_f64(int act, double z);
 /* one output's term of molann_value_and_restraint_f64, the function its kernel calls: returns 1/2 kappa d^2 and stores dy = kappa d
  * (d = y - z, wrapped where period > 0, cut where flat > 0); dy may be NULL */
 double molann_selftest_restraint_f64(double y, double z, double kappa, double period, double flat, double* dy);
+/* one frame's hill sum of molann_value_and_hills_f64 on the host, through the function its kernel calls per hill: returns the bias
+ * of y[d] under the table and stores dy[k] = d bias / d y_k (dy may be NULL); hills are added in ascending order.  d outside 1..8, a
+ * negative n_hills or a missing pointer: NaN, dy untouched */
+double molann_selftest_hills_f64(const double* y, int d, const double* centers, const double* heights, int64_t n_hills, const double* sigma,
+                                 int64_t sigma_stride, const double* period, double* dy);
 /* the unit-cotangent local Jacobian frames_value_jac_f64_kernel combines: jac36[c][j][xyz] = d(output column c of the item) /
  * d(atom j) for the item's 4 atoms (rows past the item's width are 0); returns the width */
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* atoms_xyz, double* jac36);

@@ -109,6 +109,8 @@ def lib():
             "molann_plan_supports_value_and_metric_f64": (i32, [vp]),
             "molann_value_and_restraint_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, i64, vp, vp, vp, vp, vp, vp, vp]),
             "molann_plan_supports_value_and_restraint_f64": (i32, [vp]),
+            "molann_value_and_hills_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+            "molann_plan_supports_value_and_hills_f64": (i32, [vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -124,6 +126,7 @@ def lib():
             "molann_selftest_act_derivative": (f32, [i32, f32]),
             "molann_selftest_act_derivative_f64": (ctypes.c_double, [i32, ctypes.c_double]),
             "molann_selftest_restraint_f64": (ctypes.c_double, [ctypes.c_double] * 5 + [ctypes.POINTER(ctypes.c_double)]),
+            "molann_selftest_hills_f64": (ctypes.c_double, [vp, i32, vp, vp, i64, vp, i64, vp, vp]),
             "molann_selftest_item_jacobian_f64": (i32, [i32, i32, vp, vp]),
             "molann_features_jvp_f32": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
             "molann_features_jvp_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
@@ -416,6 +419,27 @@ class Plan(object):
                      period.data_ptr() if period is not None else None, flat.data_ptr() if flat is not None else None, out.data_ptr(),
                      energy.data_ptr(), grad_x.data_ptr())
         return out, energy, grad_x
+
+    def supports_value_and_hills_f64(self):
+        """True when `value_and_hills_f64` serves this plan: `value_and_restraint_f64` serves it and it has at most 8 outputs (nothing
+        is built)."""
+        return lib().molann_plan_supports_value_and_hills_f64(self._handle) == 1
+
+    def value_and_hills_f64(self, x, weights, biases, centers, heights, sigma, period, out, bias, grad_x, n_hills=None, sigma_stride=None):
+        """out[N, d_out], bias[N] = sum_h heights_h exp(-1/2 sum_k (d_hk / sigma_hk)^2) (d_h = out - centers_h, wrapped by `period`) and
+        grad_x[N, n_inp, 3] = d bias / d x in float64, one launch of frames_value_hills_f64_kernel.  `weights` / `biases` as
+        `value_and_vjp_f64` takes them; `centers` [H, d_out] and `heights` [H] float64 (None where there are no hills; `n_hills` by default
+        heights' size); `sigma` d_out float64 values for all hills or [H, d_out] (`sigma_stride`: 0 or d_out, by default told from sigma's
+        dimensions); `period` d_out values or None.  All on x's device."""
+        W, B = _layer_pointers(weights, biases)
+        if n_hills is None:
+            n_hills = heights.numel() if heights is not None else 0
+        if sigma_stride is None:
+            sigma_stride = sigma.shape[-1] if sigma.dim() == 2 else 0
+        self._launch("molann_value_and_hills_f64", x.data_ptr(), x.shape[0], W, B, centers.data_ptr() if centers is not None else None,
+                     heights.data_ptr() if heights is not None else None, n_hills, sigma.data_ptr(), sigma_stride,
+                     period.data_ptr() if period is not None else None, out.data_ptr(), bias.data_ptr(), grad_x.data_ptr())
+        return out, bias, grad_x
 
     def forward_train(self, x, out, features):
         """`forward_packed` that also keeps the features (for `mlp_backward` + `features_backward`)."""

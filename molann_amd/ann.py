@@ -625,6 +625,7 @@ class _PlanOwner(object):
         state.pop("_fast", None)
         state.pop("_fp", None)
         state.pop("_flat_key", None)
+        state.pop("_sigma_key", None)
         return state
 
     def __deepcopy__(self, memo):
@@ -633,7 +634,7 @@ class _PlanOwner(object):
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k not in ("_plan_cache", "_fast", "_fp", "_flat_key"):
+            if k not in ("_plan_cache", "_fast", "_fp", "_flat_key", "_sigma_key"):
                 new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
@@ -649,6 +650,23 @@ class _TensorKey(object):
 
     def matches(self, t):
         return self.ref() is t and self.ptr == t.data_ptr() and self.version == t._version
+
+
+class _PrefixKey(object):
+    """Which rows of a table were checked: the `_TensorKey` of the tensor that owns the storage (the table itself for a view such as
+    ``table[:h]``, whose version counter every view shares) and the checked view's address and size.  A later view of the same table
+    from the same address with no more elements matches until the table is written to - a caller that appends a row writes to it."""
+    __slots__ = ("base", "ptr", "numel")
+
+    @staticmethod
+    def _owner(t):
+        return t._base if t._base is not None else t
+
+    def __init__(self, t):
+        self.base, self.ptr, self.numel = _TensorKey(self._owner(t)), t.data_ptr(), t.numel()
+
+    def matches(self, t):
+        return self.base.matches(self._owner(t)) and self.ptr == t.data_ptr() and t.numel() <= self.numel
 
 
 class _PlanEntry(object):
@@ -902,17 +920,20 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
 
 
 # ---- The calls that give the values and a derivative in one launch: MolANN.value_and_vjp / value_and_jacobian / value_and_metric /
-# value_and_restraint and PreprocessingANN.value_and_metric / value_and_restraint.  What differs between them, by kind; the checks and
-# the two ways to the kernel are written once below.
-_VJP, _JACOBIAN, _METRIC, _RESTRAINT = 0, 1, 2, 3
+# value_and_restraint / value_and_hills and PreprocessingANN.value_and_metric / value_and_restraint / value_and_hills.  What differs
+# between them, by kind; the checks and the two ways to the kernel are written once below.
+_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS = 0, 1, 2, 3, 4
+_HILLS_MAX_D_OUT = 8      # HILLS64_MAX_D_OUT of csrc/molann_value_f64.inc: the kernel's cotangent sums are a register array
 _JACOBIAN_ROUTE = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
 _METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
 _RESTRAINT_ROUTE = "use `model(x)`, form `kappa * d` and the energy with torch, then `value_and_vjp`"
 _RESTRAINT_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, form the energy with torch and take torch.autograd.grad"
-_ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint")
-_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE)       # the route that remains where the call refuses
-_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)")            # what `into` holds
-_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint")            # the dispatcher operator, in MolANN._fast_state
+_HILLS_ROUTE = "use `model(x)`, form the hill sum and its derivative with torch, then `value_and_vjp`"
+_HILLS_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, form the hill sum with torch and take torch.autograd.grad"
+_ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint", "value_and_hills")
+_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE)     # the route that remains where the call refuses
+_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)")       # what `into` holds
+_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills")            # the dispatcher operator, in MolANN._fast_state
 
 
 def _check_into(name, x, into, dtype, out_dim, second_shape, pair):
@@ -931,13 +952,13 @@ def _check_into(name, x, into, dtype, out_dim, second_shape, pair):
     return y, second
 
 
-def _check_into_triple(name, x, into, out_dim):
-    """`into` of value_and_restraint, before any launch, with `_check_into`'s checks: a triple of contiguous float64 tensors on x's
+def _check_into_triple(name, x, into, out_dim, kind=_RESTRAINT):
+    """`into` of value_and_restraint and value_and_hills, before any launch, with `_check_into`'s checks: a triple of contiguous float64 tensors on x's
     device that hold [N, out_dim], [N] and x's elements.  Returns the triple, (None, None, None) for None."""
     if into is None:
         return None, None, None
     if len(into) != 3 or not all(isinstance(t, torch.Tensor) for t in into):
-        raise TypeError("%s: `into` must be a triple of tensors %s" % (name, _ONE_LAUNCH_PAIR[_RESTRAINT]))
+        raise TypeError("%s: `into` must be a triple of tensors %s" % (name, _ONE_LAUNCH_PAIR[kind]))
     if any(t.dtype != torch.float64 for t in into):
         raise TypeError("%s: `into` must be float64 like x; got %s" % (name, ", ".join(str(t.dtype) for t in into)))
     n = x.shape[0]
@@ -991,6 +1012,39 @@ def _check_restraint_args(name, x, out_dim, center, kappa, period, flat, into, o
     return tuple(rows) + triple
 
 
+def _check_hills_args(name, x, out_dim, centers, heights, sigma, period, into, owner=None):
+    """The `centers`, `heights`, `sigma`, `period` and `into` checks of value_and_hills, all before any launch on x's device, with
+    `_restraint_row`'s rules for what passes as it is and what is converted; returns (centers, heights, sigma, period, y, bias, dx) as
+    the kernel takes them (None where they are).  More than 8 outputs: NotImplementedError.  The number of hills H is centers' first
+    dimension and may be 0.  A `sigma` that is not > 0 everywhere (a NaN too) is a ValueError: host values are looked at as they are, a
+    device tensor is read back once and remembered on `owner` until it - or, for a view like ``table[:h]``, the table it is a view
+    of - is written to (`_PrefixKey`)."""
+    if out_dim > _HILLS_MAX_D_OUT:
+        raise NotImplementedError("%s: the one-launch kernel serves at most %d outputs (got %d); %s" % (name, _HILLS_MAX_D_OUT, out_dim, _HILLS_ROUTE))
+    if isinstance(centers, torch.Tensor):
+        n_hills = centers.shape[0] if centers.dim() == 2 else 0
+    elif hasattr(centers, "__len__"):
+        n_hills = len(centers)
+    else:
+        raise TypeError("%s: `centers` must be a tensor or a sequence of rows [H, %d]; got %s" % (name, out_dim, type(centers).__name__))
+    if not isinstance(centers, torch.Tensor) and n_hills == 0:
+        centers = torch.empty((0, out_dim), dtype=torch.float64)
+    rows = [_restraint_row(name, "centers", centers, x, ((n_hills, out_dim),)),
+            _restraint_row(name, "heights", heights, x, ((n_hills,),)),
+            _restraint_row(name, "sigma", sigma, x, ((out_dim,), (n_hills, out_dim))),
+            None if period is None else _restraint_row(name, "period", period, x, ((out_dim,),))]
+    key = owner.__dict__.get("_sigma_key") if owner is not None and isinstance(sigma, torch.Tensor) else None
+    if key is None or not key.matches(sigma):
+        if not bool((rows[2] > 0).all()):
+            raise ValueError("%s: `sigma` holds the hills' widths and must be > 0 everywhere" % name)
+        if owner is not None and isinstance(sigma, torch.Tensor) and sigma.is_cuda:
+            owner.__dict__["_sigma_key"] = _PrefixKey(sigma)
+    triple = _check_into_triple(name, x, into, out_dim, _HILLS)
+    rows = [t if t is None or (t.dtype == torch.float64 and t.device == x.device and t.is_contiguous())
+            else t.to(device=x.device, dtype=torch.float64).contiguous() for t in rows]
+    return tuple(rows) + triple
+
+
 def _check_grad_out(name, x, out_dim, grad_out):
     if not isinstance(grad_out, torch.Tensor) or grad_out.numel() != x.shape[0] * out_dim or grad_out.device != x.device:
         raise ValueError("%s: grad_out must hold [%d, %d] values on %s" % (name, x.shape[0], out_dim, x.device))
@@ -1019,8 +1073,9 @@ def _check_metric_args(name, x, n_inp, out_dim, weights, into):
 def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=None):
     """The float64 one-launch calls after the caller's gate (a HIP tensor, modules one plan serves), in this order: x's shape, float64
     x, float64 head (the alignment's ref_x where there is no head) on x's device, x detached and contiguous, the extra argument
-    (`grad_out`, the metric's atom weights, the restraint's (center, kappa, period, flat)), `into`.  Returns (x, extra, y, second,
-    second's shape), y and second None without `into`; the restraint's second is the pair (energy, dx)."""
+    (`grad_out`, the metric's atom weights, the restraint's (center, kappa, period, flat), the hills' (centers, heights, sigma,
+    period)), `into`.  Returns (x, extra, y, second, second's shape), y and second None without `into`; the restraint's second is the
+    pair (energy, dx), the hills' (bias, dx)."""
     name = _ONE_LAUNCH_NAME[kind]
     _check_input(x, n_inp)
     if x.dtype != torch.float64:
@@ -1044,8 +1099,8 @@ def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=
             raise TypeError("%s: grad_out must be a floating-point tensor; got %s" % (name, extra.dtype))
     elif kind == _JACOBIAN:
         shape = (n, out_dim, n_inp, 3)
-    elif kind == _RESTRAINT:
-        checked = _check_restraint_args(name, x, out_dim, *extra, into, owner=owner)
+    elif kind in (_RESTRAINT, _HILLS):
+        checked = (_check_restraint_args if kind == _RESTRAINT else _check_hills_args)(name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:4], checked[4], (checked[5], checked[6]) if checked[4] is not None else None, (n, n_inp, 3)
     else:
         shape = (n, out_dim, out_dim)
@@ -1060,10 +1115,10 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
     """The ctypes way to the kernel of a float64 one-launch call whose arguments `_one_launch_arguments` has checked."""
     plan = entry.plan
     with torch.cuda.device(x.device):
-        if kind == _RESTRAINT:
-            if not plan.supports_value_and_restraint_f64():
-                raise NotImplementedError("value_and_restraint: one frame's rows exceed the LDS of a compute unit for this model; "
-                                          + _RESTRAINT_ROUTE)
+        if kind in (_RESTRAINT, _HILLS):
+            if not (plan.supports_value_and_restraint_f64() if kind == _RESTRAINT else plan.supports_value_and_hills_f64()):
+                raise NotImplementedError("%s: one frame's rows exceed the LDS of a compute unit for this model; %s"
+                                          % (_ONE_LAUNCH_NAME[kind], _ONE_LAUNCH_ROUTE[kind]))
         elif kind != _VJP and not (plan.supports_value_and_jacobian_f64() if kind == _JACOBIAN else plan.supports_value_and_metric_f64()):
             if kind == _JACOBIAN:
                 raise NotImplementedError("value_and_jacobian: one frame's rows exceed the LDS of a compute unit for this model; "
@@ -1076,12 +1131,17 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
         if y is None:
             y = torch.empty((x.shape[0], out_dim), dtype=torch.float64, device=x.device)
             second = torch.empty(shape, dtype=torch.float64, device=x.device)
-            if kind == _RESTRAINT:
+            if kind in (_RESTRAINT, _HILLS):
                 second = (torch.empty((x.shape[0],), dtype=torch.float64, device=x.device), second)
         if kind == _RESTRAINT:
             if x.shape[0] > 0:
                 plan.value_and_restraint_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
                                              *extra, y, *second, center_stride=out_dim if extra[0].dim() == 2 else 0)
+            return (y,) + tuple(second)
+        if kind == _HILLS:
+            if x.shape[0] > 0:
+                plan.value_and_hills_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
+                                         *extra, y, *second)
             return (y,) + tuple(second)
         if x.shape[0] > 0:
             W = [lin.weight.detach().contiguous() for lin in lins]
@@ -1156,14 +1216,27 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
         x's device passes as it is; every conversion costs a launch).  No autograd graph is recorded; ``into=(feat, energy, dx)``
         reuses the caller's buffers.  The same bits on every call.  Out of scope: float32, a `GraphedForces` replay, other bias shapes,
         gradients with respect to centres or stiffnesses."""
+        return self._bias_on_features(_RESTRAINT, x, (center, kappa, period, flat), into)
+
+    def value_and_hills(self, x, centers, heights, sigma, period=None, into=None):
+        """``(feat, bias, dx)``: `MolANN.value_and_hills` on the features themselves, float64, in ONE kernel launch
+        (`molann_value_and_hills_f64`, frames_value_hills_f64_kernel, on this module's float64 feature plan; no head): a metadynamics
+        bias ``bias[f] = sum_h heights_h exp(-1/2 sum_k (d_hk / sigma_hk)^2)``, ``d_h = feat - centers_h``, and ``dx = d bias / d x``;
+        forces are ``-dx``.  Metadynamics on raw dihedral angles: ``use_angle_value=True`` and ``period = 2 pi``.  ``centers``
+        [H, d_feat], ``heights`` [H] or a float, ``sigma`` a float, [d_feat] or [H, d_feat], ``period`` None or [d_feat], as
+        `MolANN.value_and_hills` takes them; at most 8 features.  No autograd graph is recorded; ``into=(feat, bias, dx)`` reuses the
+        caller's buffers.  The same bits on every call."""
+        return self._bias_on_features(_HILLS, x, (centers, heights, sigma, period), into)
+
+    def _bias_on_features(self, kind, x, extra, into):
+        """value_and_restraint / value_and_hills of this module: the gate, the checks and the ctypes plan of the features."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and self._fusable()):
-            raise NotImplementedError("value_and_restraint needs a FeatureLayer behind an AlignmentLayer or none, float64, on a HIP tensor; "
-                                      "otherwise " + _RESTRAINT_FEATURES_ROUTE)
+            raise NotImplementedError("%s needs a FeatureLayer behind an AlignmentLayer or none, float64, on a HIP tensor; "
+                                      "otherwise %s" % (_ONE_LAUNCH_NAME[kind], _RESTRAINT_FEATURES_ROUTE if kind == _RESTRAINT else _HILLS_FEATURES_ROUTE))
         fl = self.feature_layer
         al = self.align_layer if isinstance(self.align_layer, AlignmentLayer) else None
         d = fl.output_dimension()
-        x, extra, y, second, shape = _one_launch_arguments(_RESTRAINT, x, (center, kappa, period, flat), into, fl.input_atom_num, d, (), al,
-                                                           owner=self)
+        x, extra, y, second, shape = _one_launch_arguments(kind, x, extra, into, fl.input_atom_num, d, (), al, owner=self)
         spec, uav = _feature_spec(fl)
 
         def build():
@@ -1171,7 +1244,7 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
                 return _capi.Plan(fl.input_atom_num, features=spec, use_angle_value=uav)
             return _capi.Plan(fl.input_atom_num, align_idx=al._local_align_atom_indices, ref_x=al.ref_x, features=spec, use_angle_value=uav)
 
-        return _one_launch_ctypes(_RESTRAINT, _get_entry(self, x, "features", build), x, extra, y, second, shape, d, (), al)
+        return _one_launch_ctypes(kind, _get_entry(self, x, "features", build), x, extra, y, second, shape, d, (), al)
 
     def __prepare_scriptable__(self):
         if not self._fusable():
@@ -1297,7 +1370,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
             return _one_launch_ctypes(kind, st["entry"](), x, extra, y, second, shape, out_dim, lins, al)
         op, ref = st[_ONE_LAUNCH_OP[kind]], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"]
         W, B, into = [lin.weight for lin in lins], [lin.bias for lin in lins], list(into) if into is not None else []
-        if kind == _RESTRAINT:
+        if kind in (_RESTRAINT, _HILLS):
             return tuple(op(x, st["handle"], ref, W, B, *extra, into))
         y, second = op(x, st["handle"], ref, W, B, into) if kind == _JACOBIAN else op(x, st["handle"], ref, W, B, extra, into)
         return y, second
@@ -1345,6 +1418,29 @@ class MolANN(_PlanOwner, torch.nn.Module):
         device; a model served by one fused plan.  Out of scope: float32, a `GraphedForces` replay of this launch, bias shapes other
         than this one, gradients with respect to parameters, centres or stiffnesses."""
         return self._one_launch_f64(_RESTRAINT, self._one_launch_state(x, _RESTRAINT, "float64"), x, (center, kappa, period, flat), into)
+
+    def value_and_hills(self, x, centers, heights, sigma, period=None, into=None):
+        """``(y, bias, dx)`` with ``y = self(x)`` [N, d_out], a metadynamics bias on it - a sum of H Gaussian hills -
+        ``bias[f] = sum_h heights_h exp(-1/2 sum_k (d_hk / sigma_hk)^2)``, ``d_hk = y[f, k] - centers[h, k]`` [N], and
+        ``dx = d bias / d x = J^T (d bias / d y)`` [N, n_inp, 3] (the gradient, like `value_and_vjp`'s dx: forces are ``-dx``), float64,
+        in ONE kernel launch (`molann_value_and_hills_f64`, frames_value_hills_f64_kernel): what metadynamics does with a collective
+        variable at every step, and what reweighting a stored trajectory under a final bias does on a large batch.  The cotangent
+        depends on y, so `value_and_vjp` needs a forward, a dozen launches over an [N, H, d_out] temporary and then computes the forward
+        again; here the lanes that hold y walk the hill table.  ``centers``: [H, d_out]; ``heights``: [H] or a float, any sign;
+        ``sigma``: a float, [d_out] (all hills) or [H, d_out] (adaptive widths), > 0 everywhere or ValueError; ``period``: None or
+        [d_out], an entry > 0 wraps that output's d to ``d - P rint(d / P)`` (angles), an entry <= 0 leaves it.  H may be 0 (the first
+        step of a run): the bias and dx are zeros.  A float64 contiguous tensor on x's device passes as it is - the prefix
+        ``centers[:h]`` of a preallocated table is one; a tensor of another floating dtype, a Python number or a sequence is converted,
+        and each conversion costs a launch (a device ``sigma`` is read back once, when it is first seen or after it was written to:
+        pass the same tensor every step, or views ``widths[:h]`` of the same table - adaptive widths are then read back after each
+        deposit, which writes a row, and not on the steps between).  No cutoff: a far hill's exp underflows to 0.  ``y`` is `value_and_vjp`'s, bit for
+        bit.  A NaN poisons its own frame only.  No autograd graph is recorded (parameters and hills are data);
+        ``into=(y, bias, dx)`` reuses the caller's buffers.  Every sum has a fixed order and every row of dx is stored once: the same
+        bits on every call, whatever N.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at
+        most 8 outputs (NotImplementedError beyond).  Out of scope: float32, a `GraphedForces` replay of this launch, depositing hills
+        (append rows to your own tensors; well-tempered scaling uses the returned bias), bias grids and cutoffs, gradients with
+        respect to parameters or hills."""
+        return self._one_launch_f64(_HILLS, self._one_launch_state(x, _HILLS, "float64"), x, (centers, heights, sigma, period), into)
 
     def _tangent_present(self, x):
         if _has_tangent(x):
@@ -1400,7 +1496,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
             if st["op"] is not None:
                 st["op_vjp"], st["op_jacobian"], st["op_metric"] = (torch.ops.molann.value_and_vjp_h, torch.ops.molann.value_and_jacobian_h,
                                                                     torch.ops.molann.value_and_metric_h)
-                st["op_restraint"] = torch.ops.molann.value_and_restraint_h
+                st["op_restraint"], st["op_hills"] = torch.ops.molann.value_and_restraint_h, torch.ops.molann.value_and_hills_h
                 from . import script
                 st["desc"] = script.make_desc(script.KIND_FORWARD, fl.input_atom_num,
                                               align_idx=al._local_align_atom_indices if al is not None else None,

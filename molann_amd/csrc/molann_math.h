@@ -536,6 +536,48 @@ MOLANN_HD double restraint_term_f64(double y, double z, double kappa, double per
     return 0.5 * dy * d;
 }
 
+// One Gaussian hill of a metadynamics bias V(y) = sum_h w_h exp(-1/2 sum_k ((y_k - c_hk) / sigma_hk)^2) on d <= HILLS_MAX_D outputs:
+// d_k = y_k - c_k, wrapped like restraint_term_f64's where period_k > 0 (period may be null), s_k = d_k / sigma_k formed as d_k times
+// the rounded 1 / sigma_k (one division per column, not two), q = 1/2 sum_k s_k^2 with k ascending, g = w exp(-q).  Returns g and adds
+// g s_k / sigma_k to acc[k]: the bias is the sum of the returned values, dV/dy_k the NEGATIVE of acc[k].  w may have any sign; a far
+// hill's exp underflows to 0 and adds exact zeros; a NaN in y or c makes g and every acc[k] NaN.  Nothing is contracted, so the host
+// and the device round alike up to exp.  acc is a fixed array indexed by constants only: registers on the device.  Where one row of
+// widths serves every hill (`shared`) the caller forms the 1 / sigma_k once, with hill_inverse_widths_f64, and sigma is not read here:
+// the same rounded values, so a shared row and the same row repeated per hill give the same bits.
+constexpr int HILLS_MAX_D = 8;
+MOLANN_HD void hill_inverse_widths_f64(const double* sigma, int d, double (&inv)[HILLS_MAX_D]) {
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k) inv[k] = k < d ? 1.0 / sigma[k] : 0.0;
+}
+MOLANN_HD double hill_term_f64(const double* y, const double* c, const double* sigma, const double (&inv_shared)[HILLS_MAX_D], bool shared,
+                               const double* period, double w, int d, double (&acc)[HILLS_MAX_D]) {
+#pragma clang fp contract(off)
+    double t[HILLS_MAX_D];
+    double q = 0.0;
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k) {
+        t[k] = 0.0;
+        if (k < d) {
+            double dk = y[k] - c[k];
+            const double P = period ? period[k] : 0.0;
+            if (P > 0.0) {
+                const double turns = rint(dk / P);
+                const double whole = P * turns;
+                dk = dk - whole;
+            }
+            const double inv = shared ? inv_shared[k] : 1.0 / sigma[k];
+            const double s = dk * inv;
+            q = q + s * s;
+            t[k] = s * inv;
+        }
+    }
+    const double g = w * exp(-(0.5 * q));
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k)
+        if (k < d) acc[k] = acc[k] + g * t[k];
+    return g;
+}
+
 // Backward of kabsch_rotation: given H, the rotation R it produced and G_R = dL/dR, returns G_H = dL/dH.
 // With S = R^T H (symmetric at the optimum) a perturbation dH turns R by dR = R [w]x where
 // (tr(S) I - S) w = vee(R^T dH - dH^T R); hence G_H = R [n]x, n = (tr(S) I - S)^-1 vee(M - M^T), M = R^T G_R.

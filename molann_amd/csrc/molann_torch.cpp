@@ -608,6 +608,77 @@ std::vector<at::Tensor> value_and_restraint_h_hip(const at::Tensor& x_in, int64_
     return value_and_restraint_impl(x_in, *desc_of(handle, "molann::value_and_restraint_h"), ref_x, weights, biases, center, kappa, period, flat, into);
 }
 
+// {out, bias, grad_x}: the float64 forward's outputs, a metadynamics bias on them, bias[N] = sum_h heights_h exp(-1/2 sum_k (d_hk / sigma_hk)^2)
+// with d_h = out - centers_h (wrapped where period > 0), and its gradient grad_x[N, n_inp, 3] in ONE launch (molann_value_and_hills_f64 on
+// the float64 Linear tensors).  Parameters and hills are data.  centers: [H, out_dim]; heights: [H]; sigma: [out_dim] or [H, out_dim];
+// period: [out_dim]; all float64 on x's device (the Python methods convert what is not, and check sigma > 0).  H may be 0.  `into`: none
+// or {out, bias, grad_x}.
+at::Tensor hills_table(const char* what, const at::Tensor& t, const at::Tensor& x, bool ok, const char* shape) {
+    TORCH_CHECK_TYPE(t.scalar_type() == at::kDouble, "molann::value_and_hills: `", what, "` must be float64 (got ", t.scalar_type(), ")");
+    TORCH_CHECK_VALUE(ok && t.device() == x.device(), "molann::value_and_hills: `", what, "` must be ", shape, " on ", x.device());
+    return t.detach().contiguous();
+}
+std::vector<at::Tensor> value_and_hills_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                             const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                                             const at::Tensor& centers_in, const at::Tensor& heights_in, const at::Tensor& sigma_in,
+                                             const c10::optional<at::Tensor>& period_in, const std::vector<at::Tensor>& into) {
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_hills is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_hills: a forward or a features description");
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    const at::Tensor centers = hills_table("centers", centers_in, x, centers_in.dim() == 2 && centers_in.size(1) == cols, "[H, out_dim]");
+    const int64_t n_hills = centers.size(0);
+    const at::Tensor heights = hills_table("heights", heights_in, x, heights_in.dim() == 1 && heights_in.size(0) == n_hills, "[H]");
+    const bool per_hill = sigma_in.dim() == 2 && sigma_in.size(0) == n_hills && sigma_in.size(1) == cols;
+    const at::Tensor sigma = hills_table("sigma", sigma_in, x, per_hill || (sigma_in.dim() == 1 && sigma_in.size(0) == cols), "[out_dim] or [H, out_dim]");
+    at::Tensor period;
+    if (period_in.has_value() && period_in->defined())
+        period = hills_table("period", *period_in, x, period_in->dim() == 1 && period_in->size(0) == cols, "[out_dim]");
+    TORCH_CHECK(into.empty() || into.size() == 3, "molann::value_and_hills: `into` must be a triple of tensors (out, bias, grad_x)");
+    at::Tensor out, bias, gx;
+    if (into.empty()) {
+        out = at::empty({n, cols}, x.options()); bias = at::empty({n}, x.options()); gx = at::empty_like(x);
+    } else {
+        out = into[0]; bias = into[1]; gx = into[2];
+        const int64_t counts[3] = {n * cols, n, x.numel()};
+        for (int i = 0; i < 3; ++i) {
+            TORCH_CHECK_TYPE(into[i].scalar_type() == at::kDouble, "molann::value_and_hills: `into` must be float64 like x");
+            TORCH_CHECK_VALUE(into[i].is_contiguous() && into[i].numel() == counts[i] && into[i].device() == x.device(),
+                              "molann::value_and_hills: `into` must be contiguous {[N, out_dim], [N], [N, n_inp, 3]} on x's device");
+        }
+    }
+    F64Linears lin;
+    f64_linears("molann::value_and_hills", *e, x, weights, biases, lin, ": call .double()");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_hills_f64(e->plan) == 1,
+                                "molann::value_and_hills: more than 8 outputs, or one frame's rows exceed the LDS of a compute unit for this model; "
+                                "use run, form the hill sum and its derivative with torch, then value_and_vjp");
+    if (n == 0) return {out, bias, gx};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_hills_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), n_hills > 0 ? centers.data_ptr<double>() : nullptr,
+                                     n_hills > 0 ? heights.data_ptr<double>() : nullptr, n_hills, sigma.data_ptr<double>(), per_hill ? cols : 0,
+                                     period.defined() ? period.data_ptr<double>() : nullptr, out.data_ptr<double>(), bias.data_ptr<double>(),
+                                     gx.data_ptr<double>(), stream),
+          "molann_value_and_hills_f64");
+    return {out, bias, gx};
+}
+std::vector<at::Tensor> value_and_hills_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                            std::vector<at::Tensor> biases, const at::Tensor& centers, const at::Tensor& heights, const at::Tensor& sigma,
+                                            const c10::optional<at::Tensor>& period, std::vector<at::Tensor> into) {
+    return value_and_hills_impl(x_in, desc, ref_x, weights, biases, centers, heights, sigma, period, into);
+}
+std::vector<at::Tensor> value_and_hills_h_hip(const at::Tensor& x_in, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                              std::vector<at::Tensor> biases, const at::Tensor& centers, const at::Tensor& heights,
+                                              const at::Tensor& sigma, const c10::optional<at::Tensor>& period, std::vector<at::Tensor> into) {
+    return value_and_hills_impl(x_in, *desc_of(handle, "molann::value_and_hills_h"), ref_x, weights, biases, centers, heights, sigma, period, into);
+}
+
 // The fused forward that also keeps the features: {out, features} - or {out, empty} where the plan has no such twin of its
 // kernel (molann_plan_backward_kind != 1 ... != 2 plans recompute in molann_backward_f32).  float32 fused plans.
 std::vector<at::Tensor> run_train_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -1235,6 +1306,10 @@ TORCH_LIBRARY(molann, m) {
           "Tensor? flat, Tensor[] into) -> Tensor[]");
     m.def("value_and_restraint(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor center, Tensor kappa, Tensor? period, "
           "Tensor? flat, Tensor[] into) -> Tensor[]");
+    m.def("value_and_hills_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor centers, Tensor heights, Tensor sigma, "
+          "Tensor? period, Tensor[] into) -> Tensor[]");
+    m.def("value_and_hills(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor centers, Tensor heights, Tensor sigma, "
+          "Tensor? period, Tensor[] into) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
     m.def("run_head(Tensor feat, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases) -> Tensor", run_head);
@@ -1261,6 +1336,8 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_metric_h", value_and_metric_h_hip);
     m.impl("value_and_restraint", value_and_restraint_hip);
     m.impl("value_and_restraint_h", value_and_restraint_h_hip);
+    m.impl("value_and_hills", value_and_hills_hip);
+    m.impl("value_and_hills_h", value_and_hills_h_hip);
 }
 
 TORCH_LIBRARY_IMPL(molann, Autograd, m) { m.impl("run", run_autograd); }

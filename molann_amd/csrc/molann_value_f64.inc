@@ -1,17 +1,20 @@
 // molann_value_f64.inc - part of libmolann_hip.so, included by molann_kernels.hip after molann_hvp.inc.  The float64 calls that give the
 // values and a derivative in one launch (see include/molann_hip.h): molann_value_and_vjp_f64 (forces, frames_value_vjp_f64_kernel of
 // molann_dev_vjp_f64.inc), molann_value_and_jacobian_f64 (frames_value_jac_f64_kernel, molann_dev_jac_f64.inc),
-// molann_value_and_metric_f64 (frames_value_metric_f64_kernel, molann_dev_metric_f64.inc) and molann_value_and_restraint_f64
-// (frames_value_restraint_f64_kernel, molann_dev_restraint_f64.inc).  One argument front end, one launch and one dispatch over the
-// lane group serve the four; an entry names its kernel, its pointers and its rows.
+// molann_value_and_metric_f64 (frames_value_metric_f64_kernel, molann_dev_metric_f64.inc), molann_value_and_restraint_f64
+// (frames_value_restraint_f64_kernel, molann_dev_restraint_f64.inc) and molann_value_and_hills_f64 (frames_value_hills_f64_kernel,
+// molann_dev_hills_f64.inc).  One argument front end, one launch and one dispatch over the lane group serve the five; an entry names
+// its kernel, its pointers and its rows.
 namespace {
 
 constexpr size_t VJP64_LDS_DEFAULT = 65536;    // dynamic LDS a launch may ask for as it is
 constexpr size_t VJP64_LDS_CU = 163840;        // the LDS of a gfx950 compute unit (one block of one wave may take all of it)
 // the widest output the metric kernel's chunk pairs serve: d_out / JAC64_KC chunks, every pair of them a pass over the frame's atoms
 constexpr int METRIC64_MAX_D_OUT = 64;
+// the widest output the hills kernel serves: its cotangent sums are a register array of this size (hill_term_f64 of molann_math.h)
+constexpr int HILLS64_MAX_D_OUT = HILLS_MAX_D;
 
-enum F64Entry { F64_VJP, F64_JACOBIAN, F64_METRIC, F64_RESTRAINT };
+enum F64Entry { F64_VJP, F64_JACOBIAN, F64_METRIC, F64_RESTRAINT, F64_HILLS };
 
 struct Vjp64Geom {
     int G, block;       // lanes per frame, threads per block
@@ -76,15 +79,18 @@ inline Vjp64Geom vjp64_geometry_rows(const molann_plan* p, int max_w, int per_fr
 inline void f64_entry_rows(const molann_plan* p, VjpF64Args& a) { vjp64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, JacF64Args& a) { jac64_rows(p, a.max_w, a.z_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, RestraintF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
+inline void f64_entry_rows(const molann_plan* p, HillsF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
 
-// geometry for this entry: the forces' rows, the restraint's or the Jacobian's, and the metric's cap on the outputs
+// geometry for this entry: the forces' rows, the restraint's (the hills' too) or the Jacobian's, and the metric's and the hills' caps
+// on the outputs
 inline Vjp64Geom f64_entry_geometry(const molann_plan* p, F64Entry entry) {
     int max_w, z_w, per_frame;
     if (entry == F64_VJP) vjp64_rows(p, max_w, per_frame);
-    else if (entry == F64_RESTRAINT) restraint64_rows(p, max_w, per_frame);
+    else if (entry == F64_RESTRAINT || entry == F64_HILLS) restraint64_rows(p, max_w, per_frame);
     else jac64_rows(p, max_w, z_w, per_frame);
     Vjp64Geom g = vjp64_geometry_rows(p, max_w, per_frame);
-    if (entry == F64_METRIC && (p->n_layers > 0 ? p->dims[p->n_layers] : p->d_feat) > METRIC64_MAX_D_OUT) g.ok = false;
+    const int d_out = p->n_layers > 0 ? p->dims[p->n_layers] : p->d_feat;
+    if ((entry == F64_METRIC && d_out > METRIC64_MAX_D_OUT) || (entry == F64_HILLS && d_out > HILLS64_MAX_D_OUT)) g.ok = false;
     return g;
 }
 
@@ -95,7 +101,7 @@ struct F64Call {    // what a launch takes besides the caller's pointers
     F64Mlp m;
 };
 
-// The argument front end of the four entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
+// The argument front end of the five entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
 // must be there (`required`), their and the `optional` ones' 8-byte alignment (a null optional pointer passes), items, the head's
 // tensors layer by layer, geometry.  Nothing is dereferenced but W and b.
 template <class Args>
@@ -219,6 +225,28 @@ int molann_value_and_restraint_f64(molann_plan* p, const double* x, int64_t n, c
                             x, center, kappa, period, flat, out, energy, grad_x);
 }
 
+int molann_plan_supports_value_and_hills_f64(const molann_plan* p) {
+    if (!p) return MOLANN_E_NULL;
+    return f64_entry_geometry(p, F64_HILLS).ok ? 1 : 0;
+}
+
+int molann_value_and_hills_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b, const double* centers,
+                               const double* heights, int64_t n_hills, const double* sigma, int64_t sigma_stride, const double* period, double* out,
+                               double* bias, double* grad_x, molann_stream_t stream) {
+    if (p && n_hills < 0) return MOLANN_E_DESC;
+    F64Call<HillsF64Args> c;
+    // The table - centres, heights and widths - is required where it has rows.  Without rows nothing of it is read, so its three
+    // pointers are optional then; that includes sigma, because a [0, d_out] tensor of per-hill widths has no address.
+    const int e = n_hills > 0 ? f64_entry_arguments(p, F64_HILLS, n, {x, centers, heights, sigma, out, bias, grad_x}, {period}, W, b, c)
+                              : f64_entry_arguments(p, F64_HILLS, n, {x, out, bias, grad_x}, {centers, heights, sigma, period}, W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    if (sigma_stride != 0 && sigma_stride != c.a.d_out) return MOLANN_E_DESC;
+    c.a.n_hills = (long)n_hills;
+    c.a.sigma_stride = (long)sigma_stride;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_hills_f64_kernel, c.g.G), "frames_value_hills_f64_kernel", "hills", p, c, stream, x, centers,
+                            heights, sigma, period, out, bias, grad_x);
+}
+
 double molann_selftest_act_derivative_f64(int act, double z) { return act_derivative_f64(act, z); }
 
 double molann_selftest_restraint_f64(double y, double z, double kappa, double period, double flat, double* dy) {
@@ -226,6 +254,20 @@ double molann_selftest_restraint_f64(double y, double z, double kappa, double pe
     const double e = restraint_term_f64(y, z, kappa, period, flat, cot);
     if (dy) *dy = cot;
     return e;
+}
+
+double molann_selftest_hills_f64(const double* y, int d, const double* centers, const double* heights, int64_t n_hills, const double* sigma,
+                                 int64_t sigma_stride, const double* period, double* dy) {
+    if (!y || d < 1 || d > HILLS64_MAX_D_OUT || n_hills < 0 || (n_hills > 0 && (!centers || !heights || !sigma))) return (double)NAN;
+    double v = 0.;
+    double acc[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.}, inv[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
+    const bool shared = sigma_stride == 0;
+    if (shared && n_hills > 0) hill_inverse_widths_f64(sigma, d, inv);
+    for (int64_t h = 0; h < n_hills; ++h)
+        v += hill_term_f64(y, centers + h * d, sigma + h * sigma_stride, inv, shared, period, heights[h], d, acc);
+    if (dy)
+        for (int k = 0; k < d; ++k) dy[k] = -acc[k];
+    return v;
 }
 
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* a, double* jac36) {
