@@ -117,6 +117,19 @@ extern "C" __global__ __launch_bounds__(64 * (NCONS + NLOAD), 1) void molann_bwd
 #pragma unroll
             for (int u = 0; u < N_SLOTS; ++u) y[u] = a[u];
         }
+        // the backward's atoms of the bond / angle / dihedral items: the rotated differences of the INPUT atoms (align_item_atoms), which
+        // do not carry the rounding of an aligned atom's distance to the centroid; kept over the MLP, where the raw atoms do not stay
+        V3 yd[N_ITEMS > 0 ? N_ITEMS : 1][3];
+        if constexpr (N_ALIGN > 0) {
+#pragma unroll
+            for (int it = 0; it < N_ITEMS; ++it) {
+                if (ITEM_TYPE[it] != IT_POSITION) {
+                    V3 q0 = a[ITEM_IDX[it][0]], q1 = a[ITEM_IDX[it][1]], q2 = a[ITEM_IDX[it][2]], q3 = a[ITEM_IDX[it][3]];
+                    align_item_atoms(ITEM_TYPE[it], q0, q1, q2, q3, c0, dl, R);
+                    yd[it][0] = q0; yd[it][1] = q2; yd[it][2] = q3;
+                }
+            }
+        }
         float f[D_FEAT > 0 ? D_FEAT : 1];
 #pragma unroll
         for (int it = 0; it < N_ITEMS; ++it) {
@@ -158,7 +171,11 @@ float gm[OUTC];
 #pragma unroll
                 for (int j = 0; j < 3; ++j)
                     if (j < item_width(ITEM_TYPE[it])) g3[j] = gf[ITEM_COL[it] + j];
-                eval_item_backward(ITEM_TYPE[it], y[ITEM_IDX[it][0]], y[ITEM_IDX[it][1]], y[ITEM_IDX[it][2]], y[ITEM_IDX[it][3]], g3,
+                V3 q0 = y[ITEM_IDX[it][0]], q1 = y[ITEM_IDX[it][1]], q2 = y[ITEM_IDX[it][2]], q3 = y[ITEM_IDX[it][3]];
+                if constexpr (N_ALIGN > 0) {
+                    if (ITEM_TYPE[it] != IT_POSITION) { q0 = yd[it][0]; q1 = v3(0.f, 0.f, 0.f); q2 = yd[it][1]; q3 = yd[it][2]; }
+                }
+                eval_item_backward(ITEM_TYPE[it], q0, q1, q2, q3, g3,
                                    gy[ITEM_IDX[it][0]], gy[ITEM_IDX[it][1]], gy[ITEM_IDX[it][2]], gy[ITEM_IDX[it][3]]);
             }
             // ---- 5. rotation apply, Kabsch and centring backward: dL / d raw atoms -----------------------

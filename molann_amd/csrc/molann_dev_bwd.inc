@@ -103,10 +103,12 @@ __global__ __launch_bounds__(256) void frames_wave_bwd_kernel(const float* __res
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 pc[j] = load_atom(xf, idx[j]);
+                y[j] = pc[j];
                 if (has_align) pc[j] = (pc[j] - c0) - dl;
-                y[j] = has_align ? rotate(pc[j], R) : pc[j];
                 gy[j] = v3(0.f, 0.f, 0.f);
             }
+            // (bond / angle / dihedral items on the rotated differences of the input atoms, as the forward: align_item_atoms)
+            if (has_align) align_item_atoms(type, y[0], y[1], y[2], y[3], c0, dl, R);
             const int w = item_width(type);
             float g3[3] = {gf[col], w > 1 ? gf[col + 1] : 0.f, w > 2 ? gf[col + 2] : 0.f};
             eval_item_backward(type, y[0], y[1], y[2], y[3], g3, gy[0], gy[1], gy[2], gy[3]);
@@ -227,10 +229,12 @@ __global__ __launch_bounds__(256) void frames_wave_bwd_gather_kernel(const float
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 pc[j] = load_atom(xf, idx[j]);
+                y[j] = pc[j];
                 if (has_align) pc[j] = (pc[j] - c0) - dl;
-                y[j] = has_align ? rotate(pc[j], R) : pc[j];
                 gy[j] = v3(0.f, 0.f, 0.f);
             }
+            // (bond / angle / dihedral items on the rotated differences of the input atoms, as the forward: align_item_atoms)
+            if (has_align) align_item_atoms(type, y[0], y[1], y[2], y[3], c0, dl, R);
             const int w = item_width(type);
             float g3[3] = {gf[col], w > 1 ? gf[col + 1] : 0.f, w > 2 ? gf[col + 2] : 0.f};
             eval_item_backward(type, y[0], y[1], y[2], y[3], g3, gy[0], gy[1], gy[2], gy[3]);
@@ -438,10 +442,11 @@ __global__ __launch_bounds__(256) void frames_group_bwd_kernel(const float* __re
             V3 y[4], gy[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
+                y[j] = pc[j];
                 if (has_align) pc[j] = (pc[j] - c0) - dl;
-                y[j] = has_align ? rotate(pc[j], R) : pc[j];
                 gy[j] = v3(0.f, 0.f, 0.f);
             }
+            if (has_align) align_item_atoms(type, y[0], y[1], y[2], y[3], c0, dl, R);   // as the forward
             eval_item_backward(type, y[0], y[1], y[2], y[3], g3, gy[0], gy[1], gy[2], gy[3]);
             const int na = item_atoms(type);
 #pragma unroll

@@ -218,10 +218,11 @@ extern "C" __global__ __launch_bounds__(64 * WPB) void molann_group_vjp(const fl
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     pc[j] = load_atom(xf, d[2 + j]);
+                    y[j] = pc[j];
                     if constexpr (has_align) pc[j] = (pc[j] - c0) - dl;
-                    y[j] = has_align ? rotate(pc[j], R) : pc[j];
                     gy[j] = v3(0.f, 0.f, 0.f);
                 }
+                if constexpr (has_align) align_item_atoms(type, y[0], y[1], y[2], y[3], c0, dl, R);   // as the forward above
                 eval_item_backward(type, y[0], y[1], y[2], y[3], g3, gy[0], gy[1], gy[2], gy[3]);
                 const int na = item_atoms(type);
 #pragma unroll

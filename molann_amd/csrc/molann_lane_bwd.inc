@@ -136,7 +136,15 @@ extern "C" __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_pe
 #pragma unroll
                 for (int j = 0; j < 3; ++j)
                     if (j < item_width(ITEM_TYPE[it])) g3[j] = gf[ITEM_COL[it] + j];
-                eval_item_backward(ITEM_TYPE[it], y[ITEM_IDX[it][0]], y[ITEM_IDX[it][1]], y[ITEM_IDX[it][2]], y[ITEM_IDX[it][3]], g3,
+                // (bond / angle / dihedral items on the rotated differences of the input atoms: align_item_atoms)
+                V3 q0 = y[ITEM_IDX[it][0]], q1 = y[ITEM_IDX[it][1]], q2 = y[ITEM_IDX[it][2]], q3 = y[ITEM_IDX[it][3]];
+                if constexpr (N_ALIGN > 0) {
+                    if (ITEM_TYPE[it] != IT_POSITION) {
+                        q0 = a[ITEM_IDX[it][0]]; q1 = a[ITEM_IDX[it][1]]; q2 = a[ITEM_IDX[it][2]]; q3 = a[ITEM_IDX[it][3]];
+                        align_item_atoms(ITEM_TYPE[it], q0, q1, q2, q3, v3(0.f, 0.f, 0.f), v3(0.f, 0.f, 0.f), R);   // (no position item here)
+                    }
+                }
+                eval_item_backward(ITEM_TYPE[it], q0, q1, q2, q3, g3,
                                    gy[ITEM_IDX[it][0]], gy[ITEM_IDX[it][1]], gy[ITEM_IDX[it][2]], gy[ITEM_IDX[it][3]]);
             }
             // ---- 6. rotation apply, Kabsch and centring backward: dL / d raw atoms -----------------------

@@ -95,9 +95,13 @@ MOLANN_HD int eval_item(int type, V3 a0, V3 a1, V3 a2, V3 a3, float (&out)[3]) {
     case IT_ANGLE_COS:
         out[0] = feat_angle_cos(a0, a1, a2);
         return 1;
-    case IT_ANGLE_VAL:
-        out[0] = acosf(feat_angle_cos(a0, a1, a2)); // ann.py:330
+    case IT_ANGLE_VAL: {
+        // ann.py:330 takes acos of the cosine, which turns the cosine's rounding into eps / sin(theta) and is NaN once it rounds past
+        // +-1.  atan2(|u x v|, u.v) is the same angle with the rounding of its arguments only, at every angle.
+        const V3 u = a0 - a1, v = a2 - a1, w = cross(u, v);
+        out[0] = atan2f(fast_sqrt(dot(w, w)), dot(u, v));
         return 1;
+    }
     case IT_BOND:
         out[0] = feat_bond(a0, a1);
         return 1;
@@ -332,7 +336,8 @@ MOLANN_HD V3 rotate(V3 p, const float (&R)[9]) {
 // atom, y_k - y_1 = (p_k - p_1) R, so the short vectors between neighbouring atoms are formed from the INPUT coordinates
 // (exact up to the rounding of a vector of a few Angstrom) rather than from aligned coordinates that each carry the
 // rounding of their distance to the centroid - 1e-5 A at 100 A, which is what a 5000-atom frame's outer atoms have, and
-// what an ill-conditioned dihedral then amplifies.  Same values in exact arithmetic; used by the large-frame kernels.
+// what an ill-conditioned dihedral then amplifies.  Same values in exact arithmetic; used by the large-frame forward kernels and,
+// for the atoms handed to eval_item_backward, by every backward kernel.
 MOLANN_HD void align_item_atoms(int type, V3& p0, V3& p1, V3& p2, V3& p3, V3 c0, V3 dl, const float (&R)[9]) {
     if (type == IT_POSITION) {
         p0 = rotate((p0 - c0) - dl, R);
@@ -368,8 +373,12 @@ MOLANN_HD int eval_item_f64(int type, V3d a0, V3d a1, V3d a2, V3d a3, double (&o
     case IT_ANGLE_COS:
     case IT_ANGLE_VAL: {
         const V3d r21 = a0 - a1, r23 = a2 - a1;
-        const double c = dot(r21, r23) / (sqrt(dot(r21, r21)) * sqrt(dot(r23, r23)));   // ann.py:324-328, no clamp
-        out[0] = type == IT_ANGLE_VAL ? acos(c) : c;
+        if (type == IT_ANGLE_VAL) {   // atan2(|u x v|, u.v), as eval_item
+            const V3d w = cross(r21, r23);
+            out[0] = atan2(sqrt(dot(w, w)), dot(r21, r23));
+            return 1;
+        }
+        out[0] = dot(r21, r23) / (sqrt(dot(r21, r21)) * sqrt(dot(r23, r23)));   // ann.py:324-328, no clamp
         return 1;
     }
     case IT_BOND: {
@@ -431,10 +440,22 @@ MOLANN_HD void eval_item_backward(int type, V3 a0, V3 a1, V3 a2, V3 a3, const fl
     case IT_ANGLE_VAL: {
         const V3 u = a0 - a1, v = a2 - a1;
         const float uu = dot(u, u), vv = dot(v, v), uv = dot(u, v);
+        if (type == IT_ANGLE_VAL) {
+            // d theta/du = u x w / (|u|^2 |w|), d theta/dv = w x v / (|v|^2 |w|), w = u x v: each of length 1/|arm| by construction
+            // (u x w is perpendicular to both), at any angle; the only rounding that grows is w's own, eps / sin(theta).  The
+            // chain rule through acos, -dc / sqrt(1 - c^2), cancels twice (eps / sin^2) and, once c rounds to +-1, needs a clamp
+            // that turns the pole into a finite gradient of 1e15.  Here w = 0 gives 0 * inf = NaN, as the reference's autograd does.
+            const V3 w = cross(u, v);
+            const float gw = g[0] * fast_rsq(dot(w, w));
+            const V3 gu = (gw * fast_rcp(uu)) * cross(u, w), gv = (gw * fast_rcp(vv)) * cross(w, v);
+            ga0 = ga0 + gu;
+            ga2 = ga2 + gv;
+            ga1 = ga1 - (gu + gv);
+            return;
+        }
         const float inv_uv = fast_rsq(uu * vv); // 1 / (|u||v|)
         const float c = uv * inv_uv;
-        float gc = g[0];
-        if (type == IT_ANGLE_VAL) gc = -g[0] * fast_rsq(fmaxf(1.0f - c * c, 1e-30f)); // d acos(c) = -dc / sqrt(1 - c^2)
+        const float gc = g[0];
         // dc/du = v/(|u||v|) - c u/|u|^2 ,  dc/dv = u/(|u||v|) - c v/|v|^2
         V3 gu = v3(0.f, 0.f, 0.f), gv = v3(0.f, 0.f, 0.f);
         axpy(gu, gc * inv_uv, v); axpy(gu, -gc * c * fast_rcp(uu), u);
@@ -696,10 +717,18 @@ MOLANN_HD void eval_item_backward_f64(int type, V3d a0, V3d a1, V3d a2, V3d a3, 
     case IT_ANGLE_VAL: {
         const V3d u = a0 - a1, v = a2 - a1;
         const double uu = dot(u, u), vv = dot(v, v), uv = dot(u, v);
+        if (type == IT_ANGLE_VAL) {   // through w = u x v, as eval_item_backward
+            const V3d w = cross(u, v);
+            const double gw = g[0] / sqrt(dot(w, w));
+            const V3d gu = (gw / uu) * cross(u, w), gv = (gw / vv) * cross(w, v);
+            ga0 = ga0 + gu;
+            ga2 = ga2 + gv;
+            ga1 = ga1 - (gu + gv);
+            return;
+        }
         const double inv_uv = 1.0 / (sqrt(uu) * sqrt(vv));
         const double c = uv * inv_uv;
-        double gc = g[0];
-        if (type == IT_ANGLE_VAL) gc = -g[0] / sqrt(1.0 - c * c);
+        const double gc = g[0];
         V3d gu = v3d(0., 0., 0.), gv = v3d(0., 0., 0.);
         axpy(gu, gc * inv_uv, v); axpy(gu, -gc * c / uu, u);
         axpy(gv, gc * inv_uv, u); axpy(gv, -gc * c / vv, v);
@@ -764,8 +793,6 @@ template <> struct VecOf<float> { typedef V3 type; };
 template <> struct VecOf<double> { typedef V3d type; };
 MOLANN_HD float tsqrt(float a) { return sqrtf(a); }
 MOLANN_HD double tsqrt(double a) { return sqrt(a); }
-MOLANN_HD float tacos(float a) { return acosf(a); }
-MOLANN_HD double tacos(double a) { return acos(a); }
 MOLANN_HD float tatan2(float y, float x) { return atan2f(y, x); }
 MOLANN_HD double tatan2(double y, double x) { return atan2(y, x); }
 
@@ -789,9 +816,10 @@ MOLANN_HD int eval_item_tangent_t(int type, V a0, V a1, V a2, V a3, V t0, V t1, 
         const T c = dot(u, v) * inv_uv;
         // dc = (du.v + u.dv) / (|u||v|) - c (u.du / |u|^2 + v.dv / |v|^2)
         const T dc = (dot(du, v) + dot(u, dv)) * inv_uv - c * (dot(u, du) / uu + dot(v, dv) / vv);
-        if (type == IT_ANGLE_VAL) {
-            out[0] = tacos(c);
-            dout[0] = -dc / tsqrt((T)1 - c * c);
+        if (type == IT_ANGLE_VAL) {   // d theta = (u x w . du / |u|^2 + w x v . dv / |v|^2) / |w|, w = u x v: eval_item_backward's vectors
+            const V w = cross(u, v);
+            out[0] = tatan2(tsqrt(dot(w, w)), dot(u, v));
+            dout[0] = (dot(cross(u, w), du) / uu + dot(cross(w, v), dv) / vv) / tsqrt(dot(w, w));
         } else {
             out[0] = c;
             dout[0] = dc;
@@ -942,10 +970,18 @@ MOLANN_HD void eval_item_backward_gen(int type, V a0, V a1, V a2, V a3, const T 
     case IT_ANGLE_VAL: {
         const V u = a0 - a1, v = a2 - a1;
         const T uu = dot(u, u), vv = dot(v, v), uv = dot(u, v);
+        if (type == IT_ANGLE_VAL) {   // through w = u x v, as eval_item_backward_f64
+            const V w = cross(u, v);
+            const T gw = g[0] / tsqrt(dot(w, w));
+            const V gu = (gw / uu) * cross(u, w), gv = (gw / vv) * cross(w, v);
+            ga0 = ga0 + gu;
+            ga2 = ga2 + gv;
+            ga1 = ga1 - (gu + gv);
+            return;
+        }
         const T inv_uv = 1.0 / (tsqrt(uu) * tsqrt(vv));
         const T c = uv * inv_uv;
-        T gc = g[0];
-        if (type == IT_ANGLE_VAL) gc = -(g[0] / tsqrt(1.0 - c * c));
+        const T gc = g[0];
         V gu = zero * u, gv = zero * v;
         axpy(gu, gc * inv_uv, v); axpy(gu, -(gc * c / uu), u);
         axpy(gv, gc * inv_uv, u); axpy(gv, -(gc * c / vv), v);
