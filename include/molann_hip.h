@@ -26,8 +26,14 @@
  *     on small frames) compiles it with hipRTC and may allocate its workspace: make that call outside a graph
  *     capture (molann_plan_backward_kind builds the backward ahead of time).
  *   - x is [n_frames, n_inp, 3] fp32, contiguous, frame-major / atom-major / xyz-minor (the layout of
- *     the tensor the reference's forward receives, ann.py:170).  Any 4-byte aligned pointer works;
- *     16-byte aligned pointers take the wide-load path.
+ *     the tensor the reference's forward receives, ann.py:170).
+ *   - Caller's buffers.  Every DEVICE pointer a call takes - x, cotangents, tangents, outputs, gradients, feature rows, tables, and
+ *     the ref_x / W[i] / b[i] tensors - may point anywhere into a larger array of the caller's, aligned to its element: 4 bytes
+ *     for the float32 entries, 8 for the float64 ones; a pointer that is not is refused with MOLANN_E_ALIGNMENT before anything
+ *     is launched or written.  Nothing more is asked: 16-byte aligned pointers take the wide loads and stores, others the narrow
+ *     ones, each buffer by its own address, with the same bits either way.  A call reads nothing outside its inputs and writes
+ *     exactly its outputs' elements - never a byte before, between or behind them, whatever n_frames, the frame size and the
+ *     output width are (tests/test_gpu_buffer_placement.py holds every entry to this inside guard bands).
  *   - n_frames == 0 is legal and does nothing (the reference returns an empty tensor).
  *   - code object: gfx950 only.
  */
@@ -72,7 +78,7 @@ extern "C" {
 #define MOLANN_E_INDEX (-3)       /* an atom index is outside [0, n_inp) */
 #define MOLANN_E_FEATURE (-4)     /* unknown feature type or wrong atom count for its type */
 #define MOLANN_E_STAGE (-5)       /* the plan lacks the stage this call needs (no align / features / MLP) */
-#define MOLANN_E_ALIGNMENT (-6)   /* pointer not 4-byte aligned */
+#define MOLANN_E_ALIGNMENT (-6)   /* pointer not aligned to its element: 4 bytes (float32 entries), 8 (float64 entries) */
 #define MOLANN_E_UNSUPPORTED (-7) /* shape outside what the kernels cover */
 #define MOLANN_E_NOT_PACKED (-8)  /* forward_packed before any plan_update_mlp */
 #define MOLANN_E_DEVICE (-9)      /* no gfx950 device */
@@ -125,7 +131,7 @@ int molann_plan_out_dim(const molann_plan* plan);
 int molann_plan_kernel_family(const molann_plan* plan);
 
 /* The module's `ref_x` buffer is live state (register_buffer, ann.py:137: load_state_dict / .to()
- * can replace it).  Re-reads it from DEVICE memory [n_align*3], already centred. */
+ * can replace it).  Re-reads it from DEVICE memory [n_align*3], already centred (4-byte aligned, as every float32 pointer). */
 int molann_plan_update_ref(molann_plan* plan, const float* ref_x, molann_stream_t stream);
 
 /* The Linear parameters are live (trainable).  Re-reads W[i] ([dims[i+1], dims[i]] row-major,

@@ -23,7 +23,7 @@ const char* molann_error_string(int code) {
     case MOLANN_E_INDEX: return "atom index outside [0, n_inp)";
     case MOLANN_E_FEATURE: return "unknown feature type or wrong atom count for its type";
     case MOLANN_E_STAGE: return "plan lacks the stage this call needs";
-    case MOLANN_E_ALIGNMENT: return "pointer is not 4-byte aligned";
+    case MOLANN_E_ALIGNMENT: return "pointer is not aligned to its element (4 bytes for the float32 entries, 8 for the float64 ones)";
     case MOLANN_E_UNSUPPORTED: return "shape not covered by the gfx950 kernels";
     case MOLANN_E_NOT_PACKED: return "MLP weights were never packed (call molann_plan_update_mlp)";
     case MOLANN_E_DEVICE: return "no gfx950 device";
@@ -44,6 +44,7 @@ int molann_plan_last_launch_info(const molann_plan* p, char* buf, int cap) {
 int molann_plan_update_ref(molann_plan* p, const float* ref_x, molann_stream_t stream) {
     if (!p || !ref_x) return MOLANN_E_NULL;
     if (p->n_align <= 0) return MOLANN_E_STAGE;
+    if (((uintptr_t)ref_x) & 3) return MOLANN_E_ALIGNMENT;
     hipLaunchKernelGGL(pack_ref_kernel<float>, dim3(1), dim3(256), 0, (hipStream_t)stream, p->d_ref, p->d_ref64, ref_x, p->n_align);
     return (int)hipGetLastError();
 }
@@ -51,6 +52,7 @@ int molann_plan_update_ref(molann_plan* p, const float* ref_x, molann_stream_t s
 int molann_plan_update_ref_f64(molann_plan* p, const double* ref_x, molann_stream_t stream) {
     if (!p || !ref_x) return MOLANN_E_NULL;
     if (p->n_align <= 0) return MOLANN_E_STAGE;
+    if (((uintptr_t)ref_x) & 7) return MOLANN_E_ALIGNMENT;
     hipLaunchKernelGGL(pack_ref_kernel<double>, dim3(1), dim3(256), 0, (hipStream_t)stream, p->d_ref, p->d_ref64, ref_x, p->n_align);
     return (int)hipGetLastError();
 }
@@ -62,8 +64,9 @@ int molann_plan_update_mlp(molann_plan* p, const float* const* W, const float* c
     memset(&a, 0, sizeof(a));
     a.n_layers = p->n_layers;
     for (int i = 0; i <= p->n_layers; ++i) a.dims[i] = p->dims[i];
-    for (int l = 0; l < p->n_layers; ++l) {
+    for (int l = 0; l < p->n_layers; ++l) {   // every tensor is looked at before anything is packed: a refusal leaves the plan's copies as they were
         if (!W[l] || !b[l]) return MOLANN_E_NULL;
+        if ((((uintptr_t)W[l]) & 3) || (((uintptr_t)b[l]) & 3)) return MOLANN_E_ALIGNMENT;
         a.W[l] = W[l]; a.b[l] = b[l];
         a.kp[l] = p->kp[l]; a.jp[l] = p->jp[l]; a.moff[l] = p->moff[l];
     }
@@ -295,24 +298,35 @@ int molann_features_backward_f64(const molann_plan* p, const double* x, const do
     return (int)hipGetLastError();
 }
 
-int molann_mlp_f64(const molann_plan* p, const double* f, int64_t n, const double* const* W, const double* const* b, double* out,
-                   molann_stream_t stream) {
+// The arguments of molann_mlp_f64, all looked at before anything is launched (molann_forward_f64 asks before its first kernel too):
+// MOLANN_OK with the head's description in m and its LDS bytes in lds, or the refusal.
+static int mlp_f64_arguments(const molann_plan* p, const double* f, int64_t n, const double* const* W, const double* const* b, const double* out,
+                             F64Mlp& m, size_t& lds) {
     if (!p || !W || !b) return MOLANN_E_NULL;
     if (p->n_layers <= 0) return MOLANN_E_STAGE;
     const int c = check_io_f64(f, out, n);
     if (c != MOLANN_OK || n == 0) return c;
-    F64Mlp m;
     memset(&m, 0, sizeof(m));
     m.n_layers = p->n_layers; m.act = p->act;
     for (int i = 0; i <= p->n_layers; ++i) { m.dims[i] = p->dims[i]; m.max_w = std::max(m.max_w, p->dims[i]); }
     for (int l = 0; l < p->n_layers; ++l) {
         if (!W[l] || !b[l]) return MOLANN_E_NULL;
+        if ((((uintptr_t)W[l]) & 7) || (((uintptr_t)b[l]) & 7)) return MOLANN_E_ALIGNMENT;
         m.W[l] = W[l]; m.b[l] = b[l];
     }
-    const size_t lds = (size_t)4 * 2 * m.max_w * sizeof(double);
-    if (lds > 65536) return MOLANN_E_UNSUPPORTED;
+    lds = (size_t)4 * 2 * m.max_w * sizeof(double);
+    return lds > 65536 ? MOLANN_E_UNSUPPORTED : MOLANN_OK;
+}
+
+int molann_mlp_f64(const molann_plan* p, const double* f, int64_t n, const double* const* W, const double* const* b, double* out,
+                   molann_stream_t stream) {
+    F64Mlp m;
+    size_t lds = 0;
+    const int c = mlp_f64_arguments(p, f, n, W, b, out, m, lds);
+    if (c != MOLANN_OK || n == 0) return c;
     const int grid = grid_for(p, n, 4, 8);
     hipLaunchKernelGGL(mlp_f64_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, f, out, (long)n, m);
+    snprintf(const_cast<molann_plan*>(p)->last_info, sizeof(p->last_info), "mlp_f64_kernel grid=%d block=256 lds=%zu", grid, lds);
     return (int)hipGetLastError();
 }
 
@@ -321,9 +335,15 @@ int molann_forward_f64(const molann_plan* p, const double* x, int64_t n, const d
     if (!p) return MOLANN_E_NULL;
     if (p->n_layers <= 0 || p->n_items <= 0) return MOLANN_E_STAGE;
     if (n > 0 && !features_work) return MOLANN_E_NULL;
-    int e = molann_features_f64(p, x, n, features_work, stream);
+    int e = check_io_f64(x, features_work, n);
     if (e != MOLANN_OK || n == 0) return e;
-    e = molann_mlp_f64(p, features_work, n, W, b, out, stream);
+    {   // the head's arguments before the features are launched: a refusal writes nothing
+        F64Mlp m;
+        size_t lds = 0;
+        if ((e = mlp_f64_arguments(p, features_work, n, W, b, out, m, lds)) != MOLANN_OK) return e;
+    }
+    if ((e = molann_features_f64(p, x, n, features_work, stream)) != MOLANN_OK) return e;
+    if ((e = molann_mlp_f64(p, features_work, n, W, b, out, stream)) != MOLANN_OK) return e;
     snprintf(const_cast<molann_plan*>(p)->last_info, sizeof(p->last_info), "frames_f64_kernel (features) + mlp_f64_kernel");
     return e;
 }
