@@ -365,6 +365,35 @@ int molann_value_and_hills_f64(molann_plan* plan, const double* x, int64_t n_fra
 /* 1 when molann_value_and_hills_f64 serves the plan (molann_value_and_restraint_f64 serves it and out_dim <= 8), 0 otherwise. */
 int molann_plan_supports_value_and_hills_f64(const molann_plan* plan);
 
+/* Values, a bias interpolated from a TABLE over them AND its gradient in ONE launch of frames_value_grid_f64_kernel (ahead of time: no
+ * hipRTC): out[N, out_dim] = molann_value_and_vjp_f64's out, bit for bit (out_dim = feature_dim for a plan without an MLP),
+ * bias[N] = V(out) and grad_x[N, n_inp, 3] = d bias / d x = J^T (d bias / d out) - the gradient: forces are its negative - everything
+ * in double, 1 <= out_dim <= 3.  The table holds a bias on a regular grid over the outputs - accumulated metadynamics hills, a
+ * free-energy surface, an ABF or OPES estimate, walls - so a call's cost does not depend on what the table was made from.  table: a
+ * DEVICE pointer to prod_k shape[k] doubles, row-major with output 0 the slowest axis (offset (i_0 n_1 + i_1) n_2 + i_2); shape, lower,
+ * spacing, periodic: HOST arrays of out_dim entries, read during the call (periodic may be NULL: no axis is periodic).  Grid point i of
+ * axis k sits at lower[k] + i spacing[k]; a periodic axis has period shape[k] spacing[k], any other spans [lower, lower + (n - 1) h].
+ * V is the cubic-convolution (Catmull-Rom) interpolant: per axis u = (out_k - lower_k) / h_k, wrapped into [0, n_k) where periodic,
+ * else clamped to [0, n_k - 1]; a cell i, t = u - i, four neighbours i - 1 .. i + 2 (wrapped, or the edge's value repeated) with
+ * weights w_0 = ((-t + 2) t - 1) t / 2, w_1 = ((3 t - 5) t^2 + 2) / 2, w_2 = ((-3 t + 4) t + 1) t / 2, w_3 = (t - 1) t^2 / 2;
+ * V = sum over the 4^out_dim stencil points of table[...] prod_k w_jk(t_k), and d bias / d out_k the exact derivative of that sum: V is
+ * C1 inside the range and across a periodic seam and takes the table's value at a grid point.  Outside a non-periodic range the bias is
+ * the edge's value and that axis' derivative exactly 0, so the derivative JUMPS at the range's ends: keep walls inside the range.
+ * Every table index is in range for every bit pattern of out; a frame whose out is not finite gets a NaN bias and grad_x and no other
+ * frame does.  A frame's stencil is summed in a fixed order and every row of grad_x is stored once: no atomics, the same bits on every
+ * run, whatever n_frames.  W, b as molann_value_and_vjp_f64 takes them; parameters and the table are data.  Every plan
+ * molann_value_and_restraint_f64 serves with out_dim <= 3: MOLANN_E_UNSUPPORTED otherwise; MOLANN_E_STAGE for a plan without items.
+ * After these checks: a NULL shape, lower or spacing: MOLANN_E_NULL; shape[k] < 4, a spacing that is not finite and > 0, a lower that
+ * is not finite, or 2^31 table points or more: MOLANN_E_DESC.  n_frames < 0: MOLANN_E_DESC; n_frames == 0: nothing is read or
+ * launched.  x, table, out, bias, grad_x 8-byte aligned, contiguous.  The call only enqueues on `stream` (no workspace, no event):
+ * thread-safe and capturable. */
+int molann_value_and_grid_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                              const double* table, const int64_t* shape, const double* lower, const double* spacing, const int32_t* periodic,
+                              double* out, double* bias, double* grad_x, molann_stream_t stream);
+
+/* 1 when molann_value_and_grid_f64 serves the plan (molann_value_and_restraint_f64 serves it and out_dim <= 3), 0 otherwise. */
+int molann_plan_supports_value_and_grid_f64(const molann_plan* plan);
+
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
  * is fused into the lane kernel, and large-frame plans with a head within the fused MLP's limits (the features are written
@@ -433,6 +462,15 @@ double molann_selftest_restraint_f64(double y, double z, double kappa, double pe
  * negative n_hills or a missing pointer: NaN, dy untouched */
 double molann_selftest_hills_f64(const double* y, int d, const double* centers, const double* heights, int64_t n_hills, const double* sigma,
                                  int64_t sigma_stride, const double* period, double* dy);
+/* one axis' step of molann_value_and_grid_f64 on the host, through the function its kernel calls: the four table indices, the four
+ * weights and the four derivative weights (s w' / spacing) for output value y on an axis of n points; any of the three may be NULL */
+void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]);
+/* one frame's interpolation of molann_value_and_grid_f64 on the host, through the functions its kernel calls (table: a HOST pointer
+ * here): returns the bias of y[d] and stores dy[k] = d bias / d y_k (dy may be NULL); stencil points are added in ascending order.  d
+ * outside 1..3, a missing pointer (periodic may be NULL) or a grid molann_value_and_grid_f64 answers with MOLANN_E_DESC: NaN, dy
+ * untouched */
+double molann_selftest_grid_f64(const double* y, int d, const double* table, const int64_t* shape, const double* lower, const double* spacing,
+                                const int32_t* periodic, double* dy);
 /* the unit-cotangent local Jacobian frames_value_jac_f64_kernel combines: jac36[c][j][xyz] = d(output column c of the item) /
  * d(atom j) for the item's 4 atoms (rows past the item's width are 0); returns the width */
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* atoms_xyz, double* jac36);

@@ -111,6 +111,8 @@ def lib():
             "molann_plan_supports_value_and_restraint_f64": (i32, [vp]),
             "molann_value_and_hills_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
             "molann_plan_supports_value_and_hills_f64": (i32, [vp]),
+            "molann_value_and_grid_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "molann_plan_supports_value_and_grid_f64": (i32, [vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -127,6 +129,8 @@ def lib():
             "molann_selftest_act_derivative_f64": (ctypes.c_double, [i32, ctypes.c_double]),
             "molann_selftest_restraint_f64": (ctypes.c_double, [ctypes.c_double] * 5 + [ctypes.POINTER(ctypes.c_double)]),
             "molann_selftest_hills_f64": (ctypes.c_double, [vp, i32, vp, vp, i64, vp, i64, vp, vp]),
+            "molann_selftest_grid_axis_f64": (None, [ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32, vp, vp, vp]),
+            "molann_selftest_grid_f64": (ctypes.c_double, [vp, i32, vp, vp, vp, vp, vp, vp]),
             "molann_selftest_item_jacobian_f64": (i32, [i32, i32, vp, vp]),
             "molann_features_jvp_f32": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
             "molann_features_jvp_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
@@ -439,6 +443,26 @@ class Plan(object):
         self._launch("molann_value_and_hills_f64", x.data_ptr(), x.shape[0], W, B, centers.data_ptr() if centers is not None else None,
                      heights.data_ptr() if heights is not None else None, n_hills, sigma.data_ptr(), sigma_stride,
                      period.data_ptr() if period is not None else None, out.data_ptr(), bias.data_ptr(), grad_x.data_ptr())
+        return out, bias, grad_x
+
+    def supports_value_and_grid_f64(self):
+        """True when `value_and_grid_f64` serves this plan: `value_and_restraint_f64` serves it and it has at most 3 outputs (nothing
+        is built)."""
+        return lib().molann_plan_supports_value_and_grid_f64(self._handle) == 1
+
+    def value_and_grid_f64(self, x, weights, biases, table, lower, spacing, periodic, out, bias, grad_x):
+        """out[N, d_out], bias[N] = the cubic-convolution interpolant of `table` at out and grad_x[N, n_inp, 3] = d bias / d x in float64,
+        one launch of frames_value_grid_f64_kernel.  `weights` / `biases` as `value_and_vjp_f64` takes them; `table` a contiguous
+        float64 tensor on x's device with one axis per output (its shape is the grid's); `lower`, `spacing`: d_out floats; `periodic`:
+        d_out bools or None - host values, read during the call."""
+        W, B = _layer_pointers(weights, biases)
+        d = table.dim()
+        shape = (ctypes.c_int64 * d)(*table.shape)
+        lo = (ctypes.c_double * d)(*[float(v) for v in lower])
+        h = (ctypes.c_double * d)(*[float(v) for v in spacing])
+        per = (ctypes.c_int32 * d)(*[1 if v else 0 for v in periodic]) if periodic is not None else None
+        self._launch("molann_value_and_grid_f64", x.data_ptr(), x.shape[0], W, B, table.data_ptr(), shape, lo, h, per, out.data_ptr(),
+                     bias.data_ptr(), grad_x.data_ptr())
         return out, bias, grad_x
 
     def forward_train(self, x, out, features):

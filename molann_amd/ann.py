@@ -920,9 +920,10 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
 
 
 # ---- The calls that give the values and a derivative in one launch: MolANN.value_and_vjp / value_and_jacobian / value_and_metric /
-# value_and_restraint / value_and_hills and PreprocessingANN.value_and_metric / value_and_restraint / value_and_hills.  What differs
+# value_and_restraint / value_and_hills / value_and_grid and PreprocessingANN.value_and_metric / value_and_restraint / value_and_hills /
+# value_and_grid.  What differs
 # between them, by kind; the checks and the two ways to the kernel are written once below.
-_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS = 0, 1, 2, 3, 4
+_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID = 0, 1, 2, 3, 4, 5
 _HILLS_MAX_D_OUT = 8      # HILLS64_MAX_D_OUT of csrc/molann_value_f64.inc: the kernel's cotangent sums are a register array
 _JACOBIAN_ROUTE = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
 _METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
@@ -930,10 +931,17 @@ _RESTRAINT_ROUTE = "use `model(x)`, form `kappa * d` and the energy with torch, 
 _RESTRAINT_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, form the energy with torch and take torch.autograd.grad"
 _HILLS_ROUTE = "use `model(x)`, form the hill sum and its derivative with torch, then `value_and_vjp`"
 _HILLS_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, form the hill sum with torch and take torch.autograd.grad"
-_ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint", "value_and_hills")
-_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE)     # the route that remains where the call refuses
-_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)")       # what `into` holds
-_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills")            # the dispatcher operator, in MolANN._fast_state
+_GRID_MAX_D_OUT = 3       # GRID64_MAX_D_OUT of csrc/molann_value_f64.inc: the table has one axis per output
+_GRID_ROUTE = "use `model(x)`, interpolate the table and its derivative with torch, then `value_and_vjp`"
+_GRID_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, interpolate the table with torch and take torch.autograd.grad"
+_ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint", "value_and_hills", "value_and_grid")
+# the route that remains where the call refuses
+_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE)
+_ONE_LAUNCH_FEATURES_ROUTE = (None, None, None, _RESTRAINT_FEATURES_ROUTE, _HILLS_FEATURES_ROUTE, _GRID_FEATURES_ROUTE)
+_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)", "(y, bias, dx)")       # what `into` holds
+# the dispatcher operator, in MolANN._fast_state
+_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid")
+_BIAS_KINDS = (_RESTRAINT, _HILLS, _GRID)      # the calls that return (y, a scalar per frame, dx)
 
 
 def _check_into(name, x, into, dtype, out_dim, second_shape, pair):
@@ -953,7 +961,7 @@ def _check_into(name, x, into, dtype, out_dim, second_shape, pair):
 
 
 def _check_into_triple(name, x, into, out_dim, kind=_RESTRAINT):
-    """`into` of value_and_restraint and value_and_hills, before any launch, with `_check_into`'s checks: a triple of contiguous float64 tensors on x's
+    """`into` of value_and_restraint, value_and_hills and value_and_grid, before any launch, with `_check_into`'s checks: a triple of contiguous float64 tensors on x's
     device that hold [N, out_dim], [N] and x's elements.  Returns the triple, (None, None, None) for None."""
     if into is None:
         return None, None, None
@@ -1045,6 +1053,60 @@ def _check_hills_args(name, x, out_dim, centers, heights, sigma, period, into, o
     return tuple(rows) + triple
 
 
+def _grid_floats(name, what, v, out_dim):
+    """`lower` or `spacing` of value_and_grid: a sequence, or a CPU tensor, of out_dim numbers, as a list of floats."""
+    if isinstance(v, torch.Tensor):
+        if v.device.type != "cpu":
+            raise ValueError("%s: `%s` holds host values: a sequence or a CPU tensor of %d floats; got a tensor on %s" % (name, what, out_dim, v.device))
+        v = v.reshape(-1).tolist() if v.dim() <= 1 else v
+    try:
+        vals = [float(t) for t in v]
+    except (TypeError, ValueError, RuntimeError):
+        raise TypeError("%s: `%s` must be a sequence or a CPU tensor of %d floats; got %s" % (name, what, out_dim, type(v).__name__))
+    if len(vals) != out_dim:
+        raise ValueError("%s: `%s` must hold one value per output (%d); got %d" % (name, what, out_dim, len(vals)))
+    return vals
+
+
+def _check_grid_args(name, x, out_dim, table, lower, spacing, periodic, into, owner=None):
+    """The `table`, `lower`, `spacing`, `periodic` and `into` checks of value_and_grid, all before any launch on x's device; returns
+    (table, lower, spacing, periodic, y, bias, dx) as the kernel takes them: the table as it is, three lists of out_dim host values
+    (`periodic` all False for None), y, bias, dx None without `into`.  More than 3 outputs: NotImplementedError.  Nothing is
+    converted: a table that is not float64, contiguous, on x's device, with one dimension of at least 4 points per output is an
+    error, and so is a spacing that is not finite and > 0 or a lower that is not finite."""
+    if out_dim > _GRID_MAX_D_OUT:
+        raise NotImplementedError("%s: the one-launch kernel serves at most %d outputs (got %d); %s" % (name, _GRID_MAX_D_OUT, out_dim, _GRID_ROUTE))
+    if not isinstance(table, torch.Tensor):
+        raise TypeError("%s: `table` must be a float64 tensor with one dimension per output; got %s" % (name, type(table).__name__))
+    if table.dtype != torch.float64:
+        raise TypeError("%s: `table` must be float64; got %s" % (name, table.dtype))
+    if table.device != x.device:
+        raise ValueError("%s: `table` must be on %s; got %s" % (name, x.device, table.device))
+    if table.dim() != out_dim or any(n < 4 for n in table.shape):
+        raise ValueError("%s: `table` must have one dimension of at least 4 points per output (%d); got %s" % (name, out_dim, list(table.shape)))
+    if not table.is_contiguous():
+        raise ValueError("%s: `table` must be contiguous (output 0 is its slowest axis)" % name)
+    if table.numel() >= 2 ** 31:
+        raise ValueError("%s: `table` must hold fewer than 2^31 points; got %d" % (name, table.numel()))
+    lower, spacing = _grid_floats(name, "lower", lower, out_dim), _grid_floats(name, "spacing", spacing, out_dim)
+    if not all(math.isfinite(h) and h > 0.0 for h in spacing):
+        raise ValueError("%s: `spacing` holds the grid's steps and must be finite and > 0; got %s" % (name, spacing))
+    if not all(math.isfinite(v) for v in lower):
+        raise ValueError("%s: `lower` holds the position of the grid's first point and must be finite; got %s" % (name, lower))
+    if periodic is None:
+        periodic = [False] * out_dim
+    else:
+        if isinstance(periodic, torch.Tensor):
+            periodic = periodic.reshape(-1).tolist()
+        try:
+            periodic = [bool(p) for p in periodic]
+        except TypeError:
+            raise TypeError("%s: `periodic` must be None or a sequence of %d bools; got %s" % (name, out_dim, type(periodic).__name__))
+        if len(periodic) != out_dim:
+            raise ValueError("%s: `periodic` must hold one bool per output (%d); got %d" % (name, out_dim, len(periodic)))
+    return (table.detach(), lower, spacing, periodic) + _check_into_triple(name, x, into, out_dim, _GRID)
+
+
 def _check_grad_out(name, x, out_dim, grad_out):
     if not isinstance(grad_out, torch.Tensor) or grad_out.numel() != x.shape[0] * out_dim or grad_out.device != x.device:
         raise ValueError("%s: grad_out must hold [%d, %d] values on %s" % (name, x.shape[0], out_dim, x.device))
@@ -1074,8 +1136,8 @@ def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=
     """The float64 one-launch calls after the caller's gate (a HIP tensor, modules one plan serves), in this order: x's shape, float64
     x, float64 head (the alignment's ref_x where there is no head) on x's device, x detached and contiguous, the extra argument
     (`grad_out`, the metric's atom weights, the restraint's (center, kappa, period, flat), the hills' (centers, heights, sigma,
-    period)), `into`.  Returns (x, extra, y, second, second's shape), y and second None without `into`; the restraint's second is the
-    pair (energy, dx), the hills' (bias, dx)."""
+    period), the grid's (table, lower, spacing, periodic)), `into`.  Returns (x, extra, y, second, second's shape), y and second None without `into`; the restraint's second is the
+    pair (energy, dx), the hills' and the grid's (bias, dx)."""
     name = _ONE_LAUNCH_NAME[kind]
     _check_input(x, n_inp)
     if x.dtype != torch.float64:
@@ -1099,8 +1161,8 @@ def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=
             raise TypeError("%s: grad_out must be a floating-point tensor; got %s" % (name, extra.dtype))
     elif kind == _JACOBIAN:
         shape = (n, out_dim, n_inp, 3)
-    elif kind in (_RESTRAINT, _HILLS):
-        checked = (_check_restraint_args if kind == _RESTRAINT else _check_hills_args)(name, x, out_dim, *extra, into, owner=owner)
+    elif kind in _BIAS_KINDS:
+        checked = (_check_restraint_args, _check_hills_args, _check_grid_args)[kind - _RESTRAINT](name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:4], checked[4], (checked[5], checked[6]) if checked[4] is not None else None, (n, n_inp, 3)
     else:
         shape = (n, out_dim, out_dim)
@@ -1115,8 +1177,8 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
     """The ctypes way to the kernel of a float64 one-launch call whose arguments `_one_launch_arguments` has checked."""
     plan = entry.plan
     with torch.cuda.device(x.device):
-        if kind in (_RESTRAINT, _HILLS):
-            if not (plan.supports_value_and_restraint_f64() if kind == _RESTRAINT else plan.supports_value_and_hills_f64()):
+        if kind in _BIAS_KINDS:
+            if not (plan.supports_value_and_restraint_f64, plan.supports_value_and_hills_f64, plan.supports_value_and_grid_f64)[kind - _RESTRAINT]():
                 raise NotImplementedError("%s: one frame's rows exceed the LDS of a compute unit for this model; %s"
                                           % (_ONE_LAUNCH_NAME[kind], _ONE_LAUNCH_ROUTE[kind]))
         elif kind != _VJP and not (plan.supports_value_and_jacobian_f64() if kind == _JACOBIAN else plan.supports_value_and_metric_f64()):
@@ -1131,7 +1193,7 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
         if y is None:
             y = torch.empty((x.shape[0], out_dim), dtype=torch.float64, device=x.device)
             second = torch.empty(shape, dtype=torch.float64, device=x.device)
-            if kind in (_RESTRAINT, _HILLS):
+            if kind in _BIAS_KINDS:
                 second = (torch.empty((x.shape[0],), dtype=torch.float64, device=x.device), second)
         if kind == _RESTRAINT:
             if x.shape[0] > 0:
@@ -1142,6 +1204,11 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
             if x.shape[0] > 0:
                 plan.value_and_hills_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
                                          *extra, y, *second)
+            return (y,) + tuple(second)
+        if kind == _GRID:
+            if x.shape[0] > 0:
+                plan.value_and_grid_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
+                                        *extra, y, *second)
             return (y,) + tuple(second)
         if x.shape[0] > 0:
             W = [lin.weight.detach().contiguous() for lin in lins]
@@ -1228,11 +1295,20 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
         caller's buffers.  The same bits on every call."""
         return self._bias_on_features(_HILLS, x, (centers, heights, sigma, period), into)
 
+    def value_and_grid(self, x, table, lower, spacing, periodic=None, into=None):
+        """``(feat, bias, dx)``: `MolANN.value_and_grid` on the features themselves, float64, in ONE kernel launch
+        (`molann_value_and_grid_f64`, frames_value_grid_f64_kernel, on this module's float64 feature plan; no head): the bias
+        interpolated from ``table`` (cubic convolution on a regular grid, one axis per feature) and ``dx = d bias / d x``; forces are
+        ``-dx``.  A phi / psi surface on raw dihedral angles: ``use_angle_value=True``, ``lower = -pi``, ``spacing = 2 pi / n`` and
+        ``periodic = True``.  ``table``, ``lower``, ``spacing``, ``periodic`` as `MolANN.value_and_grid` takes them; at most 3 features.
+        No autograd graph is recorded; ``into=(feat, bias, dx)`` reuses the caller's buffers.  The same bits on every call."""
+        return self._bias_on_features(_GRID, x, (table, lower, spacing, periodic), into)
+
     def _bias_on_features(self, kind, x, extra, into):
-        """value_and_restraint / value_and_hills of this module: the gate, the checks and the ctypes plan of the features."""
+        """value_and_restraint / value_and_hills / value_and_grid of this module: the gate, the checks and the ctypes plan of the features."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and self._fusable()):
             raise NotImplementedError("%s needs a FeatureLayer behind an AlignmentLayer or none, float64, on a HIP tensor; "
-                                      "otherwise %s" % (_ONE_LAUNCH_NAME[kind], _RESTRAINT_FEATURES_ROUTE if kind == _RESTRAINT else _HILLS_FEATURES_ROUTE))
+                                      "otherwise %s" % (_ONE_LAUNCH_NAME[kind], _ONE_LAUNCH_FEATURES_ROUTE[kind]))
         fl = self.feature_layer
         al = self.align_layer if isinstance(self.align_layer, AlignmentLayer) else None
         d = fl.output_dimension()
@@ -1370,7 +1446,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
             return _one_launch_ctypes(kind, st["entry"](), x, extra, y, second, shape, out_dim, lins, al)
         op, ref = st[_ONE_LAUNCH_OP[kind]], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"]
         W, B, into = [lin.weight for lin in lins], [lin.bias for lin in lins], list(into) if into is not None else []
-        if kind in (_RESTRAINT, _HILLS):
+        if kind in _BIAS_KINDS:
             return tuple(op(x, st["handle"], ref, W, B, *extra, into))
         y, second = op(x, st["handle"], ref, W, B, into) if kind == _JACOBIAN else op(x, st["handle"], ref, W, B, extra, into)
         return y, second
@@ -1438,9 +1514,34 @@ class MolANN(_PlanOwner, torch.nn.Module):
         ``into=(y, bias, dx)`` reuses the caller's buffers.  Every sum has a fixed order and every row of dx is stored once: the same
         bits on every call, whatever N.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at
         most 8 outputs (NotImplementedError beyond).  Out of scope: float32, a `GraphedForces` replay of this launch, depositing hills
-        (append rows to your own tensors; well-tempered scaling uses the returned bias), bias grids and cutoffs, gradients with
+        (append rows to your own tensors; well-tempered scaling uses the returned bias), cutoffs (a bias on a grid: `value_and_grid`), gradients with
         respect to parameters or hills."""
         return self._one_launch_f64(_HILLS, self._one_launch_state(x, _HILLS, "float64"), x, (centers, heights, sigma, period), into)
+
+    def value_and_grid(self, x, table, lower, spacing, periodic=None, into=None):
+        """``(y, bias, dx)`` with ``y = self(x)`` [N, d_out], a bias interpolated from a table over it, ``bias[f] = V(y[f])`` [N], and
+        ``dx = d bias / d x = J^T (d bias / d y)`` [N, n_inp, 3] (the gradient, like `value_and_vjp`'s dx: forces are ``-dx``), float64,
+        in ONE kernel launch (`molann_value_and_grid_f64`, frames_value_grid_f64_kernel).  The table is what MD engines interpolate
+        instead of walking 10^4 - 10^5 hills at every step - accumulated metadynamics hills (`molann_amd.bias.add_hills_to_grid`), a
+        converged free-energy surface, an ABF or OPES estimate, a bias read from another program, walls - so a call costs the same
+        whatever the table was made from: 4^d_out loads per frame.  ``table``: a float64 contiguous tensor on x's device with
+        ``d_out <= 3`` dimensions of at least 4 points each, output 0 its slowest axis; it is read at launch as it is (nothing is
+        converted or cached: update it in place between steps).  ``lower``, ``spacing``: sequences or CPU tensors of d_out floats,
+        grid point i of axis k sits at ``lower[k] + i spacing[k]``, the spacing finite and > 0; ``periodic``: None or d_out bools, a
+        periodic axis has period ``n_k spacing[k]`` (an angle: ``lower = -pi``, ``spacing = 2 pi / n_k``), any other spans
+        ``[lower, lower + (n_k - 1) spacing]``.  They are host values and travel in the launch's arguments.  V is the
+        cubic-convolution (Catmull-Rom) interpolant: four neighbours per axis, wrapped on a periodic axis, the edge's value repeated on
+        any other; it takes the table's value at a grid point, is C1 inside the range and across the periodic seam, and ``dx`` is the
+        exact gradient of V, so energy is conserved.  Its error against the function the table samples falls as h^3 (the derivative's
+        as h^2).  Outside a non-periodic range the bias is the edge's value and that axis' derivative exactly 0: the derivative JUMPS
+        at the range's ends, so keep walls and everything a trajectory visits inside the range.  ``y`` is `value_and_vjp`'s, bit for
+        bit.  A NaN or an infinite output poisons its own frame only, and no table index leaves the table whatever y holds.  No autograd
+        graph is recorded (parameters and the table are data); ``into=(y, bias, dx)`` reuses the caller's buffers.  Every sum has a
+        fixed order and every row of dx is stored once: the same bits on every call, whatever N.  `model.double()` and a float64 x on a
+        HIP device; a model served by one fused plan with at most 3 outputs (NotImplementedError beyond).  Out of scope: float32, more
+        than 3 outputs, a bias on a subset of the outputs, tables with stored derivatives, depositing into the table inside the launch,
+        a `GraphedForces` replay of this launch, gradients with respect to the table or the parameters."""
+        return self._one_launch_f64(_GRID, self._one_launch_state(x, _GRID, "float64"), x, (table, lower, spacing, periodic), into)
 
     def _tangent_present(self, x):
         if _has_tangent(x):
@@ -1497,6 +1598,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
                 st["op_vjp"], st["op_jacobian"], st["op_metric"] = (torch.ops.molann.value_and_vjp_h, torch.ops.molann.value_and_jacobian_h,
                                                                     torch.ops.molann.value_and_metric_h)
                 st["op_restraint"], st["op_hills"] = torch.ops.molann.value_and_restraint_h, torch.ops.molann.value_and_hills_h
+                st["op_grid"] = torch.ops.molann.value_and_grid_h
                 from . import script
                 st["desc"] = script.make_desc(script.KIND_FORWARD, fl.input_atom_num,
                                               align_idx=al._local_align_atom_indices if al is not None else None,

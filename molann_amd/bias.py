@@ -1,0 +1,58 @@
+"""Tables for `MolANN.value_and_grid`: a bias on a regular grid over the collective variables.  Plain torch - building or updating a
+table is plumbing between steps, not a hot path.
+
+A table has one axis per output, output 0 the slowest; grid point i of axis k sits at ``lower[k] + i * spacing[k]``.  A periodic axis
+has period ``n_k * spacing[k]`` (so the point after the last is the first again); any other spans
+``[lower[k], lower[k] + (n_k - 1) * spacing[k]]``.  A metadynamics run that starts with `MolANN.value_and_hills` moves to the table
+with `add_hills_to_grid`: deposit each new hill onto the table and call `value_and_grid`, whose cost does not grow with the run."""
+
+import torch
+
+__all__ = ["grid_points", "add_hills_to_grid"]
+
+
+def grid_points(shape, lower, spacing, device=None):
+    """The grid's coordinates: a tuple of one float64 tensor per axis, ``lower[k] + arange(shape[k]) * spacing[k]``.
+    ``torch.meshgrid(*grid_points(...), indexing="ij")`` gives the coordinates of every table entry."""
+    shape, lower, spacing = [int(n) for n in shape], [float(v) for v in lower], [float(v) for v in spacing]
+    if not (len(shape) == len(lower) == len(spacing)):
+        raise ValueError("grid_points: `shape`, `lower` and `spacing` must have one entry per axis; got %d, %d, %d" % (len(shape), len(lower), len(spacing)))
+    return tuple(lo + torch.arange(n, dtype=torch.float64, device=device) * h for n, lo, h in zip(shape, lower, spacing))
+
+
+def add_hills_to_grid(table, lower, spacing, periodic, centers, heights, sigma, chunk=1024):
+    """Adds ``sum_h heights_h exp(-1/2 sum_k (d_hk / sigma_hk)^2)`` - `MolANN.value_and_hills`' bias - onto ``table`` in place, at
+    every grid point g: ``d_hk = g_k - centers[h, k]``, wrapped to ``d - P rint(d / P)`` with ``P = n_k spacing[k]`` on a periodic
+    axis.  ``table``: float64 with 1 to 3 dimensions; ``lower``, ``spacing``: one float per axis; ``periodic``: one bool per axis or
+    None; ``centers``: [H, d]; ``heights``: [H] or a float; ``sigma``: a float, [d] or [H, d], > 0.  The Gaussian is a product over
+    the axes, so the hills are taken ``chunk`` at a time and the temporaries are ``chunk * n_k`` values per axis, whatever the
+    table's size.  Returns ``table``."""
+    if not (isinstance(table, torch.Tensor) and table.dtype == torch.float64 and 1 <= table.dim() <= 3):
+        raise TypeError("add_hills_to_grid: `table` must be a float64 tensor with 1 to 3 dimensions")
+    d = table.dim()
+    periodic = [False] * d if periodic is None else [bool(p) for p in periodic]
+    points = grid_points(table.shape, lower, spacing, device=table.device)
+    if len(periodic) != d or len(points) != d:
+        raise ValueError("add_hills_to_grid: `lower`, `spacing` and `periodic` must have one entry per axis of `table` (%d)" % d)
+    f64 = dict(dtype=torch.float64, device=table.device)
+    centers = torch.as_tensor(centers, **f64).reshape(-1, d)
+    n_hills = centers.shape[0]
+    heights = torch.as_tensor(heights, **f64).expand(n_hills)
+    sigma = torch.as_tensor(sigma, **f64)
+    sigma = sigma.expand(n_hills, d) if sigma.dim() < 2 else sigma
+    if sigma.shape != (n_hills, d) or not bool((sigma > 0).all()):
+        raise ValueError("add_hills_to_grid: `sigma` must be a float, [d] or [H, d] and > 0 everywhere")
+    letters = "ijl"[:d]
+    equation = "h," + ",".join("h" + c for c in letters) + "->" + letters
+    for start in range(0, n_hills, int(chunk)):
+        rows = slice(start, start + int(chunk))
+        factors = []
+        for k in range(d):
+            dk = points[k][None, :] - centers[rows, k, None]
+            if periodic[k]:
+                P = table.shape[k] * float(spacing[k])
+                dk = dk - P * torch.round(dk / P)
+            s = dk / sigma[rows, k, None]
+            factors.append(torch.exp(-0.5 * s * s))
+        table += torch.einsum(equation, heights[rows], *factors)
+    return table

@@ -599,6 +599,84 @@ MOLANN_HD double hill_term_f64(const double* y, const double* c, const double* s
     return g;
 }
 
+// A bias tabulated on a regular grid over d <= GRID_MAX_D outputs, interpolated by cubic convolution (Catmull-Rom): V(y) = sum over the
+// 4^d stencil points of T[idx_0 j0, ...] prod_k a_k jk, dV/dy_k the same sum with b_k jk in place of a_k jk.  grid_axis_f64 is one
+// axis' step: u = (y - lower) / h; periodic: u <- u - n floor(u / n), i = floor(u) held in [0, n - 1], idx_j = (i - 1 + j) mod n;
+// not periodic: s = 1 inside [0, n - 1], else s = 0 and u is clamped to it, i = floor(u) held in [0, n - 2], idx_j = i - 1 + j clamped
+// to [0, n - 1] (the edge's value repeats); t = u - i, a_j = w_j(t), b_j = s w'_j(t) / h.  Outside a non-periodic range V is the edge's
+// value and that axis' derivative exactly 0: the derivative jumps at the range's ends.  Every idx lies in [0, n - 1] for every bit
+// pattern of y: the cell index is formed in double, held to its range by comparisons that a NaN fails towards 0, and only then
+// converted; a u that is not finite takes cell 0 and a NaN t, so the frame's bias and derivatives are NaN.  Nothing is contracted.
+constexpr int GRID_MAX_D = 3;
+MOLANN_HD void grid_axis_f64(double y, long n, double lower, double h, bool periodic, long (&idx)[4], double (&a)[4], double (&b)[4]) {
+#pragma clang fp contract(off)
+    const double nd = (double)n;
+    double u = (y - lower) / h;
+    double s = 1.0, fi = 0.0, t;
+    if (!(fabs(u) <= 1.7976931348623157e308)) {    // NaN, +-inf
+        t = u - u;                                 // NaN
+    } else if (periodic) {
+        u = u - nd * floor(u / nd);
+        fi = floor(u);
+        fi = fi >= 0.0 ? fi : 0.0;
+        fi = fi <= nd - 1.0 ? fi : nd - 1.0;
+        t = u - fi;
+    } else {
+        if (!(u >= 0.0)) { s = 0.0; u = 0.0; }
+        if (!(u <= nd - 1.0)) { s = 0.0; u = nd - 1.0; }
+        fi = floor(u);
+        fi = fi <= nd - 2.0 ? fi : nd - 2.0;
+        t = u - fi;
+    }
+    const long i = (long)fi;    // an integer in [0, n - 1]
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        long q = i - 1 + j;
+        if (periodic) q = q < 0 ? q + n : q >= n ? q - n : q;
+        else q = q < 0 ? 0 : q > n - 1 ? n - 1 : q;
+        idx[j] = q;
+    }
+    const double t2 = t * t;
+    a[0] = ((-t + 2.0) * t - 1.0) * t / 2.0;
+    a[1] = ((3.0 * t - 5.0) * t2 + 2.0) / 2.0;
+    a[2] = ((-3.0 * t + 4.0) * t + 1.0) * t / 2.0;
+    a[3] = (t - 1.0) * t2 / 2.0;
+    const double sh = s / h;
+    b[0] = sh * ((-3.0 * t2 + 4.0 * t - 1.0) / 2.0);
+    b[1] = sh * ((9.0 * t2 - 10.0 * t) / 2.0);
+    b[2] = sh * ((-9.0 * t2 + 8.0 * t + 1.0) / 2.0);
+    b[3] = sh * ((3.0 * t2 - 2.0 * t) / 2.0);
+}
+
+// entry j of a 4-array by comparisons, so that an array indexed by a value known only at run time stays in registers
+template <typename T>
+MOLANN_HD T grid_pick(const T (&v)[4], int j) { return j == 0 ? v[0] : j == 1 ? v[1] : j == 2 ? v[2] : v[3]; }
+
+// Stencil point p of 4^d (j_k = (p >> 2k) & 3) of the bias above: returns T[...] prod_k a_k jk and stores T[...] b_k jk prod_{m != k} a_m jm
+// in term[k] (0 for k >= d).  The table is row-major with output 0 slowest; the offset is formed in long.  The one load is
+// unconditional, so a caller that unrolls over its points gets every load issued before the first is waited for.
+MOLANN_HD double grid_stencil_term_f64(int p, int d, const double* table, const long (&n)[GRID_MAX_D], const long (&idx)[GRID_MAX_D][4],
+                                       const double (&a)[GRID_MAX_D][4], const double (&b)[GRID_MAX_D][4], double (&term)[GRID_MAX_D]) {
+#pragma clang fp contract(off)
+    long off = 0;
+    double wa[GRID_MAX_D], wb[GRID_MAX_D];
+#pragma unroll
+    for (int k = 0; k < GRID_MAX_D; ++k) {
+        wa[k] = 1.0; wb[k] = 0.0;
+        if (k < d) {
+            const int j = (p >> (2 * k)) & 3;
+            off = off * n[k] + grid_pick(idx[k], j);
+            wa[k] = grid_pick(a[k], j);
+            wb[k] = grid_pick(b[k], j);
+        }
+    }
+    const double T = table[off];
+    term[0] = T * (wb[0] * wa[1] * wa[2]);
+    term[1] = d > 1 ? T * (wa[0] * wb[1] * wa[2]) : 0.0;
+    term[2] = d > 2 ? T * (wa[0] * wa[1] * wb[2]) : 0.0;
+    return T * (wa[0] * wa[1] * wa[2]);
+}
+
 // Backward of kabsch_rotation: given H, the rotation R it produced and G_R = dL/dR, returns G_H = dL/dH.
 // With S = R^T H (symmetric at the optimum) a perturbation dH turns R by dR = R [w]x where
 // (tr(S) I - S) w = vee(R^T dH - dH^T R); hence G_H = R [n]x, n = (tr(S) I - S)^-1 vee(M - M^T), M = R^T G_R.

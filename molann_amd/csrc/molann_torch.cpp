@@ -679,6 +679,79 @@ std::vector<at::Tensor> value_and_hills_h_hip(const at::Tensor& x_in, int64_t ha
     return value_and_hills_impl(x_in, *desc_of(handle, "molann::value_and_hills_h"), ref_x, weights, biases, centers, heights, sigma, period, into);
 }
 
+// {out, bias, grad_x}: the float64 forward's outputs, a bias interpolated from `table` over them (cubic convolution on a regular grid: one
+// axis of the table per output, point i of axis k at lower[k] + i spacing[k], periodic[k] wraps with period n_k spacing[k]) and its gradient
+// grad_x[N, n_inp, 3] in ONE launch (molann_value_and_grid_f64 on the float64 Linear tensors).  Parameters and the table are data.  table:
+// float64, contiguous, on x's device, out_dim <= 3 dimensions of at least 4 points; lower, spacing, periodic: out_dim host values (periodic
+// may be empty: no axis is periodic).  `into`: none or {out, bias, grad_x}.
+std::vector<at::Tensor> value_and_grid_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                            const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases, const at::Tensor& table,
+                                            const std::vector<double>& lower, const std::vector<double>& spacing, const c10::List<bool>& periodic_in,
+                                            const std::vector<at::Tensor>& into) {
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_grid is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_grid: a forward or a features description");
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    TORCH_CHECK_NOT_IMPLEMENTED(cols <= 3, "molann::value_and_grid: the one-launch kernel serves at most 3 outputs (got ", cols,
+                                "); use run, interpolate the table and its derivative with torch, then value_and_vjp");
+    TORCH_CHECK_TYPE(table.scalar_type() == at::kDouble, "molann::value_and_grid: `table` must be float64 (got ", table.scalar_type(), ")");
+    TORCH_CHECK_VALUE(table.dim() == cols && table.is_contiguous() && table.device() == x.device(),
+                      "molann::value_and_grid: `table` must be contiguous with one dimension per output (", cols, ") on ", x.device());
+    TORCH_CHECK_VALUE((int64_t)lower.size() == cols && (int64_t)spacing.size() == cols && (periodic_in.size() == 0 || (int64_t)periodic_in.size() == cols),
+                      "molann::value_and_grid: `lower`, `spacing` and `periodic` must hold one value per output (", cols, ")");
+    int64_t shape[3] = {4, 4, 4};
+    int32_t periodic[3] = {0, 0, 0};
+    for (int64_t k = 0; k < cols; ++k) {
+        shape[k] = table.size(k);
+        TORCH_CHECK_VALUE(shape[k] >= 4, "molann::value_and_grid: every dimension of `table` must have at least 4 points (got ", shape[k], ")");
+        TORCH_CHECK_VALUE(std::isfinite(spacing[k]) && spacing[k] > 0.0 && std::isfinite(lower[k]),
+                          "molann::value_and_grid: `spacing` must be finite and > 0 and `lower` finite");
+        periodic[k] = periodic_in.size() > 0 && periodic_in.get(k) ? 1 : 0;
+    }
+    TORCH_CHECK_VALUE(table.numel() < (int64_t(1) << 31), "molann::value_and_grid: `table` must hold fewer than 2^31 points");
+    TORCH_CHECK(into.empty() || into.size() == 3, "molann::value_and_grid: `into` must be a triple of tensors (out, bias, grad_x)");
+    at::Tensor out, bias, gx;
+    if (into.empty()) {
+        out = at::empty({n, cols}, x.options()); bias = at::empty({n}, x.options()); gx = at::empty_like(x);
+    } else {
+        out = into[0]; bias = into[1]; gx = into[2];
+        const int64_t counts[3] = {n * cols, n, x.numel()};
+        for (int i = 0; i < 3; ++i) {
+            TORCH_CHECK_TYPE(into[i].scalar_type() == at::kDouble, "molann::value_and_grid: `into` must be float64 like x");
+            TORCH_CHECK_VALUE(into[i].is_contiguous() && into[i].numel() == counts[i] && into[i].device() == x.device(),
+                              "molann::value_and_grid: `into` must be contiguous {[N, out_dim], [N], [N, n_inp, 3]} on x's device");
+        }
+    }
+    F64Linears lin;
+    f64_linears("molann::value_and_grid", *e, x, weights, biases, lin, ": call .double()");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_grid_f64(e->plan) == 1,
+                                "molann::value_and_grid: one frame's rows exceed the LDS of a compute unit for this model; use run, interpolate "
+                                "the table and its derivative with torch, then value_and_vjp");
+    if (n == 0) return {out, bias, gx};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_grid_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), table.data_ptr<double>(), shape, lower.data(),
+                                    spacing.data(), periodic, out.data_ptr<double>(), bias.data_ptr<double>(), gx.data_ptr<double>(), stream),
+          "molann_value_and_grid_f64");
+    return {out, bias, gx};
+}
+std::vector<at::Tensor> value_and_grid_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                           std::vector<at::Tensor> biases, const at::Tensor& table, std::vector<double> lower,
+                                           std::vector<double> spacing, c10::List<bool> periodic, std::vector<at::Tensor> into) {
+    return value_and_grid_impl(x_in, desc, ref_x, weights, biases, table, lower, spacing, periodic, into);
+}
+std::vector<at::Tensor> value_and_grid_h_hip(const at::Tensor& x_in, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                             std::vector<at::Tensor> biases, const at::Tensor& table, std::vector<double> lower,
+                                             std::vector<double> spacing, c10::List<bool> periodic, std::vector<at::Tensor> into) {
+    return value_and_grid_impl(x_in, *desc_of(handle, "molann::value_and_grid_h"), ref_x, weights, biases, table, lower, spacing, periodic, into);
+}
+
 // The fused forward that also keeps the features: {out, features} - or {out, empty} where the plan has no such twin of its
 // kernel (molann_plan_backward_kind != 1 ... != 2 plans recompute in molann_backward_f32).  float32 fused plans.
 std::vector<at::Tensor> run_train_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -1310,6 +1383,10 @@ TORCH_LIBRARY(molann, m) {
           "Tensor? period, Tensor[] into) -> Tensor[]");
     m.def("value_and_hills(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor centers, Tensor heights, Tensor sigma, "
           "Tensor? period, Tensor[] into) -> Tensor[]");
+    m.def("value_and_grid_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor table, float[] lower, float[] spacing, "
+          "bool[] periodic, Tensor[] into) -> Tensor[]");
+    m.def("value_and_grid(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor table, float[] lower, float[] spacing, "
+          "bool[] periodic, Tensor[] into) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
     m.def("run_head(Tensor feat, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases) -> Tensor", run_head);
@@ -1338,6 +1415,8 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_restraint_h", value_and_restraint_h_hip);
     m.impl("value_and_hills", value_and_hills_hip);
     m.impl("value_and_hills_h", value_and_hills_h_hip);
+    m.impl("value_and_grid", value_and_grid_hip);
+    m.impl("value_and_grid_h", value_and_grid_h_hip);
 }
 
 TORCH_LIBRARY_IMPL(molann, Autograd, m) { m.impl("run", run_autograd); }

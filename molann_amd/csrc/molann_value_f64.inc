@@ -2,9 +2,9 @@
 // values and a derivative in one launch (see include/molann_hip.h): molann_value_and_vjp_f64 (forces, frames_value_vjp_f64_kernel of
 // molann_dev_vjp_f64.inc), molann_value_and_jacobian_f64 (frames_value_jac_f64_kernel, molann_dev_jac_f64.inc),
 // molann_value_and_metric_f64 (frames_value_metric_f64_kernel, molann_dev_metric_f64.inc), molann_value_and_restraint_f64
-// (frames_value_restraint_f64_kernel, molann_dev_restraint_f64.inc) and molann_value_and_hills_f64 (frames_value_hills_f64_kernel,
-// molann_dev_hills_f64.inc).  One argument front end, one launch and one dispatch over the lane group serve the five; an entry names
-// its kernel, its pointers and its rows.
+// (frames_value_restraint_f64_kernel, molann_dev_restraint_f64.inc), molann_value_and_hills_f64 (frames_value_hills_f64_kernel,
+// molann_dev_hills_f64.inc) and molann_value_and_grid_f64 (frames_value_grid_f64_kernel, molann_dev_grid_f64.inc).  One argument front
+// end, one launch and one dispatch over the lane group serve the six; an entry names its kernel, its pointers and its rows.
 namespace {
 
 constexpr size_t VJP64_LDS_DEFAULT = 65536;    // dynamic LDS a launch may ask for as it is
@@ -13,8 +13,10 @@ constexpr size_t VJP64_LDS_CU = 163840;        // the LDS of a gfx950 compute un
 constexpr int METRIC64_MAX_D_OUT = 64;
 // the widest output the hills kernel serves: its cotangent sums are a register array of this size (hill_term_f64 of molann_math.h)
 constexpr int HILLS64_MAX_D_OUT = HILLS_MAX_D;
+// the widest output the grid kernel serves: the table has one axis per output (grid_axis_f64 of molann_math.h)
+constexpr int GRID64_MAX_D_OUT = GRID_MAX_D;
 
-enum F64Entry { F64_VJP, F64_JACOBIAN, F64_METRIC, F64_RESTRAINT, F64_HILLS };
+enum F64Entry { F64_VJP, F64_JACOBIAN, F64_METRIC, F64_RESTRAINT, F64_HILLS, F64_GRID };
 
 struct Vjp64Geom {
     int G, block;       // lanes per frame, threads per block
@@ -80,17 +82,20 @@ inline void f64_entry_rows(const molann_plan* p, VjpF64Args& a) { vjp64_rows(p, 
 inline void f64_entry_rows(const molann_plan* p, JacF64Args& a) { jac64_rows(p, a.max_w, a.z_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, RestraintF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, HillsF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
+inline void f64_entry_rows(const molann_plan* p, GridF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
 
-// geometry for this entry: the forces' rows, the restraint's (the hills' too) or the Jacobian's, and the metric's and the hills' caps
-// on the outputs
+// geometry for this entry: the forces' rows, the restraint's (the hills' and the grid's too) or the Jacobian's, and the metric's, the
+// hills' and the grid's caps on the outputs
 inline Vjp64Geom f64_entry_geometry(const molann_plan* p, F64Entry entry) {
     int max_w, z_w, per_frame;
     if (entry == F64_VJP) vjp64_rows(p, max_w, per_frame);
-    else if (entry == F64_RESTRAINT || entry == F64_HILLS) restraint64_rows(p, max_w, per_frame);
+    else if (entry == F64_RESTRAINT || entry == F64_HILLS || entry == F64_GRID) restraint64_rows(p, max_w, per_frame);
     else jac64_rows(p, max_w, z_w, per_frame);
     Vjp64Geom g = vjp64_geometry_rows(p, max_w, per_frame);
     const int d_out = p->n_layers > 0 ? p->dims[p->n_layers] : p->d_feat;
-    if ((entry == F64_METRIC && d_out > METRIC64_MAX_D_OUT) || (entry == F64_HILLS && d_out > HILLS64_MAX_D_OUT)) g.ok = false;
+    if ((entry == F64_METRIC && d_out > METRIC64_MAX_D_OUT) || (entry == F64_HILLS && d_out > HILLS64_MAX_D_OUT) ||
+        (entry == F64_GRID && d_out > GRID64_MAX_D_OUT))
+        g.ok = false;
     return g;
 }
 
@@ -101,7 +106,7 @@ struct F64Call {    // what a launch takes besides the caller's pointers
     F64Mlp m;
 };
 
-// The argument front end of the five entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
+// The argument front end of the six entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
 // must be there (`required`), their and the `optional` ones' 8-byte alignment (a null optional pointer passes), items, the head's
 // tensors layer by layer, geometry.  Nothing is dereferenced but W and b.
 template <class Args>
@@ -161,6 +166,22 @@ int f64_entry_launch(Kernel* kernel, const char* name, const char* what, molann_
     snprintf(p->last_info, sizeof(p->last_info), "%s (values + %s in one launch; %d lanes per frame) grid=%d block=%d lds=%d", name, what, g.G, grid,
              g.block, (int)g.lds);
     return rc;
+}
+
+// the grid of molann_value_and_grid_f64 from the caller's host arrays into the kernel's: false where an axis has fewer than 4 points, a
+// spacing that is not finite and > 0 or a lower that is not finite, or where the table has 2^31 points or more
+inline bool grid_geometry_f64(int d, const int64_t* shape, const double* lower, const double* spacing, const int32_t* periodic,
+                              long (&n)[GRID_MAX_D], double (&lo)[GRID_MAX_D], double (&h)[GRID_MAX_D], int (&per)[GRID_MAX_D]) {
+    int64_t points = 1;
+    for (int k = 0; k < GRID_MAX_D; ++k) {
+        n[k] = 4; lo[k] = 0.0; h[k] = 1.0; per[k] = 0;
+        if (k >= d) continue;
+        if (shape[k] < 4 || shape[k] >= (int64_t(1) << 31) || !(spacing[k] > 0.0) || !std::isfinite(spacing[k]) || !std::isfinite(lower[k])) return false;
+        points *= shape[k];
+        if (points >= (int64_t(1) << 31)) return false;
+        n[k] = (long)shape[k]; lo[k] = lower[k]; h[k] = spacing[k]; per[k] = periodic && periodic[k] ? 1 : 0;
+    }
+    return true;
 }
 
 } // namespace
@@ -247,6 +268,24 @@ int molann_value_and_hills_f64(molann_plan* p, const double* x, int64_t n, const
                             heights, sigma, period, out, bias, grad_x);
 }
 
+int molann_plan_supports_value_and_grid_f64(const molann_plan* p) {
+    if (!p) return MOLANN_E_NULL;
+    return f64_entry_geometry(p, F64_GRID).ok ? 1 : 0;
+}
+
+int molann_value_and_grid_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b, const double* table,
+                              const int64_t* shape, const double* lower, const double* spacing, const int32_t* periodic, double* out, double* bias,
+                              double* grad_x, molann_stream_t stream) {
+    F64Call<GridF64Args> c;
+    const int e = f64_entry_arguments(p, F64_GRID, n, {x, table, out, bias, grad_x}, {}, W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    // the grid's geometry: host arrays of d_out entries, read now and carried by value
+    if (!shape || !lower || !spacing) return MOLANN_E_NULL;
+    if (!grid_geometry_f64(c.a.d_out, shape, lower, spacing, periodic, c.a.n, c.a.lower, c.a.h, c.a.periodic)) return MOLANN_E_DESC;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_grid_f64_kernel, c.g.G), "frames_value_grid_f64_kernel", "grid", p, c, stream, x, table, out,
+                            bias, grad_x);
+}
+
 double molann_selftest_act_derivative_f64(int act, double z) { return act_derivative_f64(act, z); }
 
 double molann_selftest_restraint_f64(double y, double z, double kappa, double period, double flat, double* dy) {
@@ -267,6 +306,37 @@ double molann_selftest_hills_f64(const double* y, int d, const double* centers, 
         v += hill_term_f64(y, centers + h * d, sigma + h * sigma_stride, inv, shared, period, heights[h], d, acc);
     if (dy)
         for (int k = 0; k < d; ++k) dy[k] = -acc[k];
+    return v;
+}
+
+void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]) {
+    long i4[4];
+    double a4[4], b4[4];
+    grid_axis_f64(y, (long)n, lower, spacing, periodic != 0, i4, a4, b4);
+    for (int j = 0; j < 4; ++j) {
+        if (idx) idx[j] = i4[j];
+        if (w) w[j] = a4[j];
+        if (dw) dw[j] = b4[j];
+    }
+}
+
+double molann_selftest_grid_f64(const double* y, int d, const double* table, const int64_t* shape, const double* lower, const double* spacing,
+                                const int32_t* periodic, double* dy) {
+    if (!y || !table || !shape || !lower || !spacing || d < 1 || d > GRID64_MAX_D_OUT) return (double)NAN;
+    long n[GRID_MAX_D], idx[GRID_MAX_D][4] = {};
+    double lo[GRID_MAX_D], h[GRID_MAX_D], a[GRID_MAX_D][4] = {}, b[GRID_MAX_D][4] = {};
+    int per[GRID_MAX_D];
+    if (!grid_geometry_f64(d, shape, lower, spacing, periodic, n, lo, h, per)) return (double)NAN;
+    for (int k = 0; k < d; ++k) grid_axis_f64(y[k], n[k], lo[k], h[k], per[k] != 0, idx[k], a[k], b[k]);
+    double v = 0.;
+    double acc[GRID_MAX_D] = {0., 0., 0.};
+    for (int p = 0; p < (1 << (2 * d)); ++p) {
+        double term[GRID_MAX_D];
+        v += grid_stencil_term_f64(p, d, table, n, idx, a, b, term);
+        for (int k = 0; k < GRID_MAX_D; ++k) acc[k] += term[k];
+    }
+    if (dy)
+        for (int k = 0; k < d; ++k) dy[k] = acc[k];
     return v;
 }
 
