@@ -394,6 +394,49 @@ int molann_value_and_grid_f64(molann_plan* plan, const double* x, int64_t n_fram
 /* 1 when molann_value_and_grid_f64 serves the plan (molann_value_and_restraint_f64 serves it and out_dim <= 3), 0 otherwise. */
 int molann_plan_supports_value_and_grid_f64(const molann_plan* plan);
 
+/* Values, UP TO THREE BIAS TERMS ON CHOSEN OUTPUTS and the gradient of their sum in ONE launch of frames_value_bias_f64_kernel (ahead of
+ * time: no hipRTC): what a production step of enhanced sampling carries - a tabulated metadynamics bias plus walls, hills on top - at
+ * the cost of one pass over the frame.  out[N, out_dim] = molann_value_and_vjp_f64's out, bit for bit; energies[N, 3] = (E_r, V_h, V_g),
+ * kept apart because well-tempered heights and reweighting need V_h / V_g without the walls, an absent term's column exactly 0.0;
+ * grad_x[N, n_inp, 3] = d(E_r + V_h + V_g) / dx - the gradient: forces are its negative.  Everything in double.
+ *   E_r: molann_value_and_restraint_f64's energy on ALL out_dim outputs (kappa_k = 0 leaves output k free); absent when kappa == NULL.
+ *        center (center_stride 0 or out_dim), kappa, restraint_period, flat: DEVICE pointers as that call takes them.
+ *   V_h: molann_value_and_hills_f64's bias on the n_hills_columns <= 8 outputs hills_columns[0..n) - a HOST array of distinct indices in
+ *        any order, NULL for 0..n-1; absent when n_hills_columns == 0.  centers[n_hills, n], heights[n_hills], sigma ([n], sigma_stride 0,
+ *        or [n_hills, n], sigma_stride n), hills_period [n] or NULL: DEVICE pointers, laid out over the chosen columns in the order of
+ *        the list.  n_hills may be 0: centers, heights and sigma are not read then.
+ *   V_g: molann_value_and_grid_f64's interpolant on the n_grid_columns <= 3 outputs grid_columns[0..n) (HOST, NULL for 0..n-1), axis 0
+ *        of the table being the first listed output; absent when n_grid_columns == 0.  table: a DEVICE pointer; shape, lower, spacing,
+ *        periodic (may be NULL): HOST arrays of n entries, read during the call.
+ * The two lists may overlap each other and the restrained outputs.  An absent term's pointers are not looked at.  The cotangent of an
+ * output is the restraint's kappa d (0 without one), then the hills' derivative is added, then the table's: a fixed order, and with it,
+ * the fixed order of every sum and one store per row of grad_x, the same bits on every run, whatever n_frames.  With one term alone
+ * (identity lists) the term's energy and grad_x are the single call's, bit for bit.  Every table index is in range for every bit
+ * pattern of out; a frame that is not finite gets NaN and no other frame does.
+ * Every plan molann_value_and_restraint_f64 serves whose rows and one more of 11 doubles fit the LDS, whatever out_dim.  Refusals, in
+ * this order, nothing being written: a NULL plan, terms, x, out, energies, grad_x or pointer a present term requires (shape, lower and
+ * spacing of a present table among them): MOLANN_E_NULL; a pointer that is not 8-byte aligned: MOLANN_E_ALIGNMENT; MOLANN_E_STAGE /
+ * MOLANN_E_UNSUPPORTED as molann_value_and_restraint_f64; no term present, a negative count, a stride other than 0 or the term's
+ * width, a grid molann_value_and_grid_f64 refuses: MOLANN_E_DESC; a column outside [0, out_dim) or repeated within its list:
+ * MOLANN_E_INDEX; more than 8 hills columns or 3 grid columns: MOLANN_E_UNSUPPORTED; a NULL list longer than out_dim: MOLANN_E_INDEX.
+ * n_frames < 0: MOLANN_E_DESC; n_frames == 0: nothing is read or launched.  The call only enqueues on `stream` (no workspace, no
+ * atomics, no event): thread-safe and capturable. */
+typedef struct molann_bias_terms_f64 {
+    /* restraint on all outputs; absent when kappa == NULL */
+    const double* center; int64_t center_stride; const double *kappa, *restraint_period, *flat;
+    /* hills on n_hills_columns <= 8 outputs; absent when n_hills_columns == 0 */
+    int32_t n_hills_columns; const int32_t* hills_columns;
+    const double *centers, *heights; int64_t n_hills; const double* sigma; int64_t sigma_stride; const double* hills_period;
+    /* table on n_grid_columns <= 3 outputs; absent when n_grid_columns == 0 */
+    int32_t n_grid_columns; const int32_t* grid_columns;
+    const double* table; const int64_t* shape; const double *lower, *spacing; const int32_t* periodic;
+} molann_bias_terms_f64;
+int molann_value_and_bias_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                              const molann_bias_terms_f64* terms, double* out, double* energies, double* grad_x, molann_stream_t stream);
+
+/* 1 when molann_value_and_bias_f64 serves the plan (its rows fit the LDS of a compute unit; no cap on out_dim), 0 otherwise. */
+int molann_plan_supports_value_and_bias_f64(const molann_plan* plan);
+
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
  * is fused into the lane kernel, and large-frame plans with a head within the fused MLP's limits (the features are written
@@ -471,6 +514,10 @@ void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spa
  * untouched */
 double molann_selftest_grid_f64(const double* y, int d, const double* table, const int64_t* shape, const double* lower, const double* spacing,
                                 const int32_t* periodic, double* dy);
+/* one frame of molann_value_and_bias_f64 on the host, through the functions its kernel calls, with its column mapping and its order of
+ * additions (every pointer of `terms` a HOST pointer here; center is one row): energies3 = (E_r, V_h, V_g), dy[d_out] = the cotangent.
+ * Returns MOLANN_OK, or the code molann_value_and_bias_f64 gives the same terms (nothing written then) */
+int molann_selftest_bias_f64(const double* y, int d_out, const molann_bias_terms_f64* terms, double* energies3, double* dy);
 /* the unit-cotangent local Jacobian frames_value_jac_f64_kernel combines: jac36[c][j][xyz] = d(output column c of the item) /
  * d(atom j) for the item's 4 atoms (rows past the item's width are 0); returns the width */
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* atoms_xyz, double* jac36);

@@ -57,6 +57,67 @@ def build_library(force=False):
     return LIB_PATH
 
 
+class BiasTermsF64(ctypes.Structure):
+    """molann_bias_terms_f64 of include/molann_hip.h: the terms of `molann_value_and_bias_f64`."""
+    _fields_ = [("center", ctypes.c_void_p), ("center_stride", ctypes.c_int64), ("kappa", ctypes.c_void_p),
+                ("restraint_period", ctypes.c_void_p), ("flat", ctypes.c_void_p),
+                ("n_hills_columns", ctypes.c_int32), ("hills_columns", ctypes.POINTER(ctypes.c_int32)),
+                ("centers", ctypes.c_void_p), ("heights", ctypes.c_void_p), ("n_hills", ctypes.c_int64), ("sigma", ctypes.c_void_p),
+                ("sigma_stride", ctypes.c_int64), ("hills_period", ctypes.c_void_p),
+                ("n_grid_columns", ctypes.c_int32), ("grid_columns", ctypes.POINTER(ctypes.c_int32)),
+                ("table", ctypes.c_void_p), ("shape", ctypes.POINTER(ctypes.c_int64)), ("lower", ctypes.POINTER(ctypes.c_double)),
+                ("spacing", ctypes.POINTER(ctypes.c_double)), ("periodic", ctypes.POINTER(ctypes.c_int32))]
+
+
+def bias_terms_f64(restraint=None, hills=None, grid=None, ptr=lambda t: t.data_ptr()):
+    """A `BiasTermsF64` and the host arrays it points into (keep both alive for the call).  restraint: (center, kappa, period, flat,
+    center_stride); hills: (columns, centers, heights, sigma, period, n_hills, sigma_stride); grid: (columns, table, shape, lower,
+    spacing, periodic); None: the term is absent.  Tensors give their addresses through `ptr`; columns None is the identity list and
+    needs the count in its place: (None, n)."""
+    t, keep = BiasTermsF64(), []
+
+    def address(v):
+        return None if v is None else ptr(v)
+
+    def host(ctype, values):
+        if values is None:
+            return None
+        arr = (ctype * max(len(values), 1))(*values)
+        keep.append(arr)
+        return arr
+
+    def columns(cols):
+        if isinstance(cols, tuple) and len(cols) == 2 and cols[0] is None:
+            return int(cols[1]), None
+        cols = [int(c) for c in cols]
+        return len(cols), host(ctypes.c_int32, cols)
+
+    if restraint is not None:
+        center, kappa, period, flat, stride = restraint
+        t.center, t.center_stride, t.kappa, t.restraint_period, t.flat = address(center), stride, address(kappa), address(period), address(flat)
+    if hills is not None:
+        cols, centers, heights, sigma, period, n_hills, stride = hills
+        t.n_hills_columns, arr = columns(cols)
+        if arr is not None:
+            t.hills_columns = arr
+        t.centers, t.heights, t.n_hills, t.sigma, t.sigma_stride, t.hills_period = \
+            address(centers), address(heights), n_hills, address(sigma), stride, address(period)
+    if grid is not None:
+        cols, table, shape, lower, spacing, periodic = grid
+        t.n_grid_columns, arr = columns(cols)
+        if arr is not None:
+            t.grid_columns = arr
+        t.table = address(table)
+        for name, ctype, values in (("shape", ctypes.c_int64, None if shape is None else [int(v) for v in shape]),
+                                    ("lower", ctypes.c_double, None if lower is None else [float(v) for v in lower]),
+                                    ("spacing", ctypes.c_double, None if spacing is None else [float(v) for v in spacing]),
+                                    ("periodic", ctypes.c_int32, None if periodic is None else [1 if v else 0 for v in periodic])):
+            arr = host(ctype, values)
+            if arr is not None:
+                setattr(t, name, arr)
+    return t, keep
+
+
 _lib = None
 
 
@@ -113,6 +174,8 @@ def lib():
             "molann_plan_supports_value_and_hills_f64": (i32, [vp]),
             "molann_value_and_grid_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
             "molann_plan_supports_value_and_grid_f64": (i32, [vp]),
+            "molann_value_and_bias_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(BiasTermsF64), vp, vp, vp, vp]),
+            "molann_plan_supports_value_and_bias_f64": (i32, [vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -131,6 +194,7 @@ def lib():
             "molann_selftest_hills_f64": (ctypes.c_double, [vp, i32, vp, vp, i64, vp, i64, vp, vp]),
             "molann_selftest_grid_axis_f64": (None, [ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32, vp, vp, vp]),
             "molann_selftest_grid_f64": (ctypes.c_double, [vp, i32, vp, vp, vp, vp, vp, vp]),
+            "molann_selftest_bias_f64": (i32, [vp, i32, ctypes.POINTER(BiasTermsF64), vp, vp]),
             "molann_selftest_item_jacobian_f64": (i32, [i32, i32, vp, vp]),
             "molann_features_jvp_f32": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
             "molann_features_jvp_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
@@ -464,6 +528,39 @@ class Plan(object):
         self._launch("molann_value_and_grid_f64", x.data_ptr(), x.shape[0], W, B, table.data_ptr(), shape, lo, h, per, out.data_ptr(),
                      bias.data_ptr(), grad_x.data_ptr())
         return out, bias, grad_x
+
+    def supports_value_and_bias_f64(self):
+        """True when `value_and_bias_f64` serves this plan: a frame's rows (the restraint's and the selection row of 11) fit the LDS,
+        whatever the number of outputs (nothing is built)."""
+        return lib().molann_plan_supports_value_and_bias_f64(self._handle) == 1
+
+    def value_and_bias_f64(self, x, weights, biases, out, energies, grad_x, restraint=None, hills=None, grid=None):
+        """out[N, d_out], energies[N, 3] = (restraint, hills, table) and grad_x[N, n_inp, 3] = d(their sum) / d x in float64, one launch
+        of frames_value_bias_f64_kernel.  `weights` / `biases` as `value_and_vjp_f64` takes them.  restraint: None or (center, kappa,
+        period, flat) as `value_and_restraint_f64`, on all outputs; hills: None or (columns, centers, heights, sigma, period) on the
+        listed outputs (at most 8; None: the first centers.shape[1]); grid: None or (columns, table, lower, spacing, periodic) on the
+        listed outputs (at most 3; None: the first table.dim()).  Device tensors on x's device; columns, lower, spacing, periodic
+        are host values, read during the call."""
+        W, B = _layer_pointers(weights, biases)
+        d_out = out.numel() // max(x.shape[0], 1)
+        r = h = g = None
+        if restraint is not None:
+            center, kappa, period, flat = restraint
+            r = (center, kappa, period, flat, 0 if center.numel() == d_out and center.dim() < 2 else d_out)
+        if hills is not None:
+            cols, centers, heights, sigma, period = hills
+            n_hills = centers.shape[0]
+            width = centers.shape[1] if cols is None else len(cols)
+            h = ((None, width) if cols is None else cols, centers if n_hills else None, heights if n_hills else None,
+                 sigma if n_hills else None, period, n_hills, width if sigma.dim() == 2 else 0)
+        if grid is not None:
+            cols, table, lower, spacing, periodic = grid
+            g = ((None, table.dim()) if cols is None else cols, table, table.shape, lower, spacing, periodic)
+        terms, keep = bias_terms_f64(r, h, g)
+        self._launch("molann_value_and_bias_f64", x.data_ptr(), x.shape[0], W, B, ctypes.byref(terms), out.data_ptr(), energies.data_ptr(),
+                     grad_x.data_ptr())
+        del keep
+        return out, energies, grad_x
 
     def forward_train(self, x, out, features):
         """`forward_packed` that also keeps the features (for `mlp_backward` + `features_backward`)."""

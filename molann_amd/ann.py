@@ -29,6 +29,7 @@ import pandas as pd
 from torch.autograd import forward_ad as _fwAD
 
 from . import _capi
+from . import bias as _bias
 
 _ACT_CODES = (
     (torch.nn.Tanh, _capi.ACT_TANH, lambda m: True),
@@ -920,10 +921,10 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
 
 
 # ---- The calls that give the values and a derivative in one launch: MolANN.value_and_vjp / value_and_jacobian / value_and_metric /
-# value_and_restraint / value_and_hills / value_and_grid and PreprocessingANN.value_and_metric / value_and_restraint / value_and_hills /
-# value_and_grid.  What differs
+# value_and_restraint / value_and_hills / value_and_grid / value_and_bias and PreprocessingANN.value_and_metric / value_and_restraint /
+# value_and_hills / value_and_grid / value_and_bias.  What differs
 # between them, by kind; the checks and the two ways to the kernel are written once below.
-_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID = 0, 1, 2, 3, 4, 5
+_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID, _BIAS = 0, 1, 2, 3, 4, 5, 6
 _HILLS_MAX_D_OUT = 8      # HILLS64_MAX_D_OUT of csrc/molann_value_f64.inc: the kernel's cotangent sums are a register array
 _JACOBIAN_ROUTE = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
 _METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
@@ -934,13 +935,16 @@ _HILLS_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, form the hi
 _GRID_MAX_D_OUT = 3       # GRID64_MAX_D_OUT of csrc/molann_value_f64.inc: the table has one axis per output
 _GRID_ROUTE = "use `model(x)`, interpolate the table and its derivative with torch, then `value_and_vjp`"
 _GRID_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, interpolate the table with torch and take torch.autograd.grad"
-_ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint", "value_and_hills", "value_and_grid")
+_BIAS_ROUTE = "use `model(x)`, form the terms and their derivatives on the chosen columns with torch, then `value_and_vjp`"
+_BIAS_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, form the terms with torch and take torch.autograd.grad"
+_ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint", "value_and_hills", "value_and_grid",
+                    "value_and_bias")
 # the route that remains where the call refuses
-_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE)
-_ONE_LAUNCH_FEATURES_ROUTE = (None, None, None, _RESTRAINT_FEATURES_ROUTE, _HILLS_FEATURES_ROUTE, _GRID_FEATURES_ROUTE)
-_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)", "(y, bias, dx)")       # what `into` holds
+_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE, _BIAS_ROUTE)
+_ONE_LAUNCH_FEATURES_ROUTE = (None, None, None, _RESTRAINT_FEATURES_ROUTE, _HILLS_FEATURES_ROUTE, _GRID_FEATURES_ROUTE, _BIAS_FEATURES_ROUTE)
+_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)", "(y, bias, dx)", "(y, energies, dx)")   # what `into` holds
 # the dispatcher operator, in MolANN._fast_state
-_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid")
+_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid", "op_bias")
 _BIAS_KINDS = (_RESTRAINT, _HILLS, _GRID)      # the calls that return (y, a scalar per frame, dx)
 
 
@@ -962,7 +966,7 @@ def _check_into(name, x, into, dtype, out_dim, second_shape, pair):
 
 def _check_into_triple(name, x, into, out_dim, kind=_RESTRAINT):
     """`into` of value_and_restraint, value_and_hills and value_and_grid, before any launch, with `_check_into`'s checks: a triple of contiguous float64 tensors on x's
-    device that hold [N, out_dim], [N] and x's elements.  Returns the triple, (None, None, None) for None."""
+    device that hold [N, out_dim], [N] ([N, 3] for value_and_bias) and x's elements.  Returns the triple, (None, None, None) for None."""
     if into is None:
         return None, None, None
     if len(into) != 3 or not all(isinstance(t, torch.Tensor) for t in into):
@@ -970,9 +974,11 @@ def _check_into_triple(name, x, into, out_dim, kind=_RESTRAINT):
     if any(t.dtype != torch.float64 for t in into):
         raise TypeError("%s: `into` must be float64 like x; got %s" % (name, ", ".join(str(t.dtype) for t in into)))
     n = x.shape[0]
-    counts = (n * out_dim, n, x.numel())
+    per = 3 if kind == _BIAS else 1
+    counts = (n * out_dim, n * per, x.numel())
     if not all(t.is_contiguous() and t.numel() == c and t.device == x.device for t, c in zip(into, counts)):
-        raise ValueError("%s: `into` must be contiguous {[%d, %d], [%d], %s} on %s" % (name, n, out_dim, n, list(x.shape), x.device))
+        raise ValueError("%s: `into` must be contiguous {[%d, %d], %s, %s} on %s"
+                         % (name, n, out_dim, [n, 3] if kind == _BIAS else [n], list(x.shape), x.device))
     return tuple(into)
 
 
@@ -1020,7 +1026,7 @@ def _check_restraint_args(name, x, out_dim, center, kappa, period, flat, into, o
     return tuple(rows) + triple
 
 
-def _check_hills_args(name, x, out_dim, centers, heights, sigma, period, into, owner=None):
+def _check_hills_args(name, x, out_dim, centers, heights, sigma, period, into, owner=None, unit="output"):
     """The `centers`, `heights`, `sigma`, `period` and `into` checks of value_and_hills, all before any launch on x's device, with
     `_restraint_row`'s rules for what passes as it is and what is converted; returns (centers, heights, sigma, period, y, bias, dx) as
     the kernel takes them (None where they are).  More than 8 outputs: NotImplementedError.  The number of hills H is centers' first
@@ -1028,13 +1034,13 @@ def _check_hills_args(name, x, out_dim, centers, heights, sigma, period, into, o
     device tensor is read back once and remembered on `owner` until it - or, for a view like ``table[:h]``, the table it is a view
     of - is written to (`_PrefixKey`)."""
     if out_dim > _HILLS_MAX_D_OUT:
-        raise NotImplementedError("%s: the one-launch kernel serves at most %d outputs (got %d); %s" % (name, _HILLS_MAX_D_OUT, out_dim, _HILLS_ROUTE))
+        raise NotImplementedError("%s: the one-launch kernel serves at most %d %ss (got %d); %s" % (name, _HILLS_MAX_D_OUT, unit, out_dim, _HILLS_ROUTE))
     if isinstance(centers, torch.Tensor):
         n_hills = centers.shape[0] if centers.dim() == 2 else 0
     elif hasattr(centers, "__len__"):
         n_hills = len(centers)
     else:
-        raise TypeError("%s: `centers` must be a tensor or a sequence of rows [H, %d]; got %s" % (name, out_dim, type(centers).__name__))
+        raise TypeError("%s: `centers` must be a tensor or a sequence of rows [H, %d] (one column per %s); got %s" % (name, out_dim, unit, type(centers).__name__))
     if not isinstance(centers, torch.Tensor) and n_hills == 0:
         centers = torch.empty((0, out_dim), dtype=torch.float64)
     rows = [_restraint_row(name, "centers", centers, x, ((n_hills, out_dim),)),
@@ -1053,7 +1059,7 @@ def _check_hills_args(name, x, out_dim, centers, heights, sigma, period, into, o
     return tuple(rows) + triple
 
 
-def _grid_floats(name, what, v, out_dim):
+def _grid_floats(name, what, v, out_dim, unit="output"):
     """`lower` or `spacing` of value_and_grid: a sequence, or a CPU tensor, of out_dim numbers, as a list of floats."""
     if isinstance(v, torch.Tensor):
         if v.device.type != "cpu":
@@ -1064,31 +1070,31 @@ def _grid_floats(name, what, v, out_dim):
     except (TypeError, ValueError, RuntimeError):
         raise TypeError("%s: `%s` must be a sequence or a CPU tensor of %d floats; got %s" % (name, what, out_dim, type(v).__name__))
     if len(vals) != out_dim:
-        raise ValueError("%s: `%s` must hold one value per output (%d); got %d" % (name, what, out_dim, len(vals)))
+        raise ValueError("%s: `%s` must hold one value per %s (%d); got %d" % (name, what, unit, out_dim, len(vals)))
     return vals
 
 
-def _check_grid_args(name, x, out_dim, table, lower, spacing, periodic, into, owner=None):
+def _check_grid_args(name, x, out_dim, table, lower, spacing, periodic, into, owner=None, unit="output"):
     """The `table`, `lower`, `spacing`, `periodic` and `into` checks of value_and_grid, all before any launch on x's device; returns
     (table, lower, spacing, periodic, y, bias, dx) as the kernel takes them: the table as it is, three lists of out_dim host values
     (`periodic` all False for None), y, bias, dx None without `into`.  More than 3 outputs: NotImplementedError.  Nothing is
     converted: a table that is not float64, contiguous, on x's device, with one dimension of at least 4 points per output is an
     error, and so is a spacing that is not finite and > 0 or a lower that is not finite."""
     if out_dim > _GRID_MAX_D_OUT:
-        raise NotImplementedError("%s: the one-launch kernel serves at most %d outputs (got %d); %s" % (name, _GRID_MAX_D_OUT, out_dim, _GRID_ROUTE))
+        raise NotImplementedError("%s: the one-launch kernel serves at most %d %ss (got %d); %s" % (name, _GRID_MAX_D_OUT, unit, out_dim, _GRID_ROUTE))
     if not isinstance(table, torch.Tensor):
-        raise TypeError("%s: `table` must be a float64 tensor with one dimension per output; got %s" % (name, type(table).__name__))
+        raise TypeError("%s: `table` must be a float64 tensor with one dimension per %s; got %s" % (name, unit, type(table).__name__))
     if table.dtype != torch.float64:
         raise TypeError("%s: `table` must be float64; got %s" % (name, table.dtype))
     if table.device != x.device:
         raise ValueError("%s: `table` must be on %s; got %s" % (name, x.device, table.device))
     if table.dim() != out_dim or any(n < 4 for n in table.shape):
-        raise ValueError("%s: `table` must have one dimension of at least 4 points per output (%d); got %s" % (name, out_dim, list(table.shape)))
+        raise ValueError("%s: `table` must have one dimension of at least 4 points per %s (%d); got %s" % (name, unit, out_dim, list(table.shape)))
     if not table.is_contiguous():
-        raise ValueError("%s: `table` must be contiguous (output 0 is its slowest axis)" % name)
+        raise ValueError("%s: `table` must be contiguous (%s 0 is its slowest axis)" % (name, unit))
     if table.numel() >= 2 ** 31:
         raise ValueError("%s: `table` must hold fewer than 2^31 points; got %d" % (name, table.numel()))
-    lower, spacing = _grid_floats(name, "lower", lower, out_dim), _grid_floats(name, "spacing", spacing, out_dim)
+    lower, spacing = _grid_floats(name, "lower", lower, out_dim, unit), _grid_floats(name, "spacing", spacing, out_dim, unit)
     if not all(math.isfinite(h) and h > 0.0 for h in spacing):
         raise ValueError("%s: `spacing` holds the grid's steps and must be finite and > 0; got %s" % (name, spacing))
     if not all(math.isfinite(v) for v in lower):
@@ -1103,8 +1109,66 @@ def _check_grid_args(name, x, out_dim, table, lower, spacing, periodic, into, ow
         except TypeError:
             raise TypeError("%s: `periodic` must be None or a sequence of %d bools; got %s" % (name, out_dim, type(periodic).__name__))
         if len(periodic) != out_dim:
-            raise ValueError("%s: `periodic` must hold one bool per output (%d); got %d" % (name, out_dim, len(periodic)))
+            raise ValueError("%s: `periodic` must hold one bool per %s (%d); got %d" % (name, unit, out_dim, len(periodic)))
     return (table.detach(), lower, spacing, periodic) + _check_into_triple(name, x, into, out_dim, _GRID)
+
+
+def _check_bias_terms(name, restraint, hills, grid):
+    """The terms of value_and_bias as they come, before anything needs a device: each None or its record of `molann_amd.bias` (whose
+    construction has checked its `columns`), and at least one of them."""
+    for what, term, cls in (("restraint", restraint, _bias.Restraint), ("hills", hills, _bias.Hills), ("grid", grid, _bias.Grid)):
+        if term is not None and not isinstance(term, cls):
+            raise TypeError("%s: `%s` must be None or a molann_amd.bias.%s; got %s" % (name, what, cls.__name__, type(term).__name__))
+    if restraint is None and hills is None and grid is None:
+        raise ValueError("%s: at least one of `restraint`, `hills` and `grid` must be given" % name)
+
+
+def _bias_columns(name, what, columns, width, cap, out_dim):
+    """The column list of a term of value_and_bias against the model: None is the first `width` outputs.  An index >= out_dim or an
+    identity list longer than out_dim: IndexError; more than `cap` columns: NotImplementedError."""
+    if columns is None:      # the cap, then the model: the order of the C entry
+        if width > cap:
+            raise NotImplementedError("%s: the one-launch kernel serves at most %d %s columns (got %d); %s" % (name, cap, what, width, _BIAS_ROUTE))
+        if width > out_dim:
+            raise IndexError("%s: `%s` has %d columns but the model has %d outputs" % (name, what, width, out_dim))
+        return tuple(range(width))
+    if any(c >= out_dim for c in columns):
+        raise IndexError("%s: `%s.columns` must lie in [0, %d); got %s" % (name, what, out_dim, list(columns)))
+    return columns
+
+
+def _hills_width(name, centers):
+    """The number of columns of a `Hills` without `columns`: centers' second dimension, or the length of its first row.  An empty
+    sequence has neither: ValueError (a ``[0, d]`` tensor, or `columns`, says what is meant)."""
+    if isinstance(centers, torch.Tensor) and centers.dim() == 2:
+        return centers.shape[1]
+    rows = len(centers) if hasattr(centers, "__len__") else 0
+    if rows and hasattr(centers[0], "__len__"):
+        return len(centers[0])
+    raise ValueError("%s: `hills.centers` must be [H, columns] to tell the columns the hills act on; for no hills yet pass `columns` or a "
+                     "[0, columns] tensor (got %s)" % (name, list(centers.shape) if isinstance(centers, torch.Tensor) else type(centers).__name__))
+
+
+def _check_bias_args(name, x, out_dim, restraint, hills, grid, into, owner=None):
+    """The checks of value_and_bias after the gate, all before any launch on x's device: the column lists against the model, then every
+    term by the check of its single call with the term's width in place of the number of outputs (the same conversions and remembered
+    read-backs), then `into`.  Returns ((center, kappa, period, flat) or None, (columns, centers, heights, sigma, period) or None,
+    (columns, table, lower, spacing, periodic) or None, y, energies, dx)."""
+    hc = gc = None
+    if hills is not None:
+        width = len(hills.columns) if hills.columns is not None else _hills_width(name, hills.centers)
+        hc = _bias_columns(name, "hills", hills.columns, width, _bias.HILLS_MAX_COLUMNS, out_dim)
+    if grid is not None:
+        width = grid.table.dim() if isinstance(grid.table, torch.Tensor) and grid.columns is None else 1
+        gc = _bias_columns(name, "grid", grid.columns, width, _bias.GRID_MAX_COLUMNS, out_dim)
+    r = h = g = None
+    if restraint is not None:
+        r = _check_restraint_args(name, x, out_dim, restraint.center, restraint.kappa, restraint.period, restraint.flat, None, owner=owner)[:4]
+    if hills is not None:
+        h = (hc,) + _check_hills_args(name, x, len(hc), hills.centers, hills.heights, hills.sigma, hills.period, None, owner=owner, unit="hills column")[:4]
+    if grid is not None:
+        g = (gc,) + _check_grid_args(name, x, len(gc), grid.table, grid.lower, grid.spacing, grid.periodic, None, owner=owner, unit="grid column")[:4]
+    return (r, h, g) + _check_into_triple(name, x, into, out_dim, _BIAS)
 
 
 def _check_grad_out(name, x, out_dim, grad_out):
@@ -1161,6 +1225,9 @@ def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=
             raise TypeError("%s: grad_out must be a floating-point tensor; got %s" % (name, extra.dtype))
     elif kind == _JACOBIAN:
         shape = (n, out_dim, n_inp, 3)
+    elif kind == _BIAS:
+        checked = _check_bias_args(name, x, out_dim, *extra, into, owner=owner)
+        return x, checked[:3], checked[3], (checked[4], checked[5]) if checked[3] is not None else None, (n, n_inp, 3)
     elif kind in _BIAS_KINDS:
         checked = (_check_restraint_args, _check_hills_args, _check_grid_args)[kind - _RESTRAINT](name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:4], checked[4], (checked[5], checked[6]) if checked[4] is not None else None, (n, n_inp, 3)
@@ -1177,8 +1244,9 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
     """The ctypes way to the kernel of a float64 one-launch call whose arguments `_one_launch_arguments` has checked."""
     plan = entry.plan
     with torch.cuda.device(x.device):
-        if kind in _BIAS_KINDS:
-            if not (plan.supports_value_and_restraint_f64, plan.supports_value_and_hills_f64, plan.supports_value_and_grid_f64)[kind - _RESTRAINT]():
+        if kind in _BIAS_KINDS or kind == _BIAS:
+            if not (plan.supports_value_and_restraint_f64, plan.supports_value_and_hills_f64, plan.supports_value_and_grid_f64,
+                    plan.supports_value_and_bias_f64)[kind - _RESTRAINT]():
                 raise NotImplementedError("%s: one frame's rows exceed the LDS of a compute unit for this model; %s"
                                           % (_ONE_LAUNCH_NAME[kind], _ONE_LAUNCH_ROUTE[kind]))
         elif kind != _VJP and not (plan.supports_value_and_jacobian_f64() if kind == _JACOBIAN else plan.supports_value_and_metric_f64()):
@@ -1195,6 +1263,13 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
             second = torch.empty(shape, dtype=torch.float64, device=x.device)
             if kind in _BIAS_KINDS:
                 second = (torch.empty((x.shape[0],), dtype=torch.float64, device=x.device), second)
+            if kind == _BIAS:
+                second = (torch.empty((x.shape[0], 3), dtype=torch.float64, device=x.device), second)
+        if kind == _BIAS:
+            if x.shape[0] > 0:
+                plan.value_and_bias_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
+                                        y, *second, restraint=extra[0], hills=extra[1], grid=extra[2])
+            return (y,) + tuple(second)
         if kind == _RESTRAINT:
             if x.shape[0] > 0:
                 plan.value_and_restraint_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
@@ -1304,8 +1379,19 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
         No autograd graph is recorded; ``into=(feat, bias, dx)`` reuses the caller's buffers.  The same bits on every call."""
         return self._bias_on_features(_GRID, x, (table, lower, spacing, periodic), into)
 
+    def value_and_bias(self, x, restraint=None, hills=None, grid=None, into=None):
+        """``(feat, energies, dx)``: `MolANN.value_and_bias` on the features themselves, float64, in ONE kernel launch
+        (`molann_value_and_bias_f64`, frames_value_bias_f64_kernel, on this module's float64 feature plan; no head): a restraint on
+        all features, hills on up to 8 chosen features and a table on up to 3, ``energies[f] = (E_r, V_h, V_g)`` and ``dx`` the gradient
+        of their sum; forces are ``-dx``.  Position columns under walls and two raw dihedral angles under metadynamics:
+        ``use_angle_value=True``, the angles' indices as ``columns`` and ``period = 2 pi``.  The terms are `molann_amd.bias.Restraint`,
+        `Hills` and `Grid`, as `MolANN.value_and_bias` takes them.  No autograd graph is recorded; ``into=(feat, energies, dx)``
+        reuses the caller's buffers.  The same bits on every call."""
+        _check_bias_terms("value_and_bias", restraint, hills, grid)
+        return self._bias_on_features(_BIAS, x, (restraint, hills, grid), into)
+
     def _bias_on_features(self, kind, x, extra, into):
-        """value_and_restraint / value_and_hills / value_and_grid of this module: the gate, the checks and the ctypes plan of the features."""
+        """value_and_restraint / value_and_hills / value_and_grid / value_and_bias of this module: the gate, the checks and the ctypes plan of the features."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and self._fusable()):
             raise NotImplementedError("%s needs a FeatureLayer behind an AlignmentLayer or none, float64, on a HIP tensor; "
                                       "otherwise %s" % (_ONE_LAUNCH_NAME[kind], _ONE_LAUNCH_FEATURES_ROUTE[kind]))
@@ -1448,6 +1534,10 @@ class MolANN(_PlanOwner, torch.nn.Module):
         W, B, into = [lin.weight for lin in lins], [lin.bias for lin in lins], list(into) if into is not None else []
         if kind in _BIAS_KINDS:
             return tuple(op(x, st["handle"], ref, W, B, *extra, into))
+        if kind == _BIAS:
+            r, h, g = extra
+            return tuple(op(x, st["handle"], ref, W, B, *(r or (None,) * 4), *((list(h[0]),) + h[1:] if h else ([], None, None, None, None)),
+                            *((list(g[0]),) + g[1:] if g else ([], None, [], [], [])), into))
         y, second = op(x, st["handle"], ref, W, B, into) if kind == _JACOBIAN else op(x, st["handle"], ref, W, B, extra, into)
         return y, second
 
@@ -1513,7 +1603,8 @@ class MolANN(_PlanOwner, torch.nn.Module):
         bit.  A NaN poisons its own frame only.  No autograd graph is recorded (parameters and hills are data);
         ``into=(y, bias, dx)`` reuses the caller's buffers.  Every sum has a fixed order and every row of dx is stored once: the same
         bits on every call, whatever N.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at
-        most 8 outputs (NotImplementedError beyond).  Out of scope: float32, a `GraphedForces` replay of this launch, depositing hills
+        most 8 outputs (NotImplementedError beyond; hills on some of a wider model's outputs, or together with walls or a table:
+        `value_and_bias`).  Out of scope: float32, a `GraphedForces` replay of this launch, depositing hills
         (append rows to your own tensors; well-tempered scaling uses the returned bias), cutoffs (a bias on a grid: `value_and_grid`), gradients with
         respect to parameters or hills."""
         return self._one_launch_f64(_HILLS, self._one_launch_state(x, _HILLS, "float64"), x, (centers, heights, sigma, period), into)
@@ -1539,9 +1630,36 @@ class MolANN(_PlanOwner, torch.nn.Module):
         graph is recorded (parameters and the table are data); ``into=(y, bias, dx)`` reuses the caller's buffers.  Every sum has a
         fixed order and every row of dx is stored once: the same bits on every call, whatever N.  `model.double()` and a float64 x on a
         HIP device; a model served by one fused plan with at most 3 outputs (NotImplementedError beyond).  Out of scope: float32, more
-        than 3 outputs, a bias on a subset of the outputs, tables with stored derivatives, depositing into the table inside the launch,
+        than 3 table axes (a table on some of a wider model's outputs, or together with walls or hills: `value_and_bias`), tables with stored derivatives, depositing into the table inside the launch,
         a `GraphedForces` replay of this launch, gradients with respect to the table or the parameters."""
         return self._one_launch_f64(_GRID, self._one_launch_state(x, _GRID, "float64"), x, (table, lower, spacing, periodic), into)
+
+    def value_and_bias(self, x, restraint=None, hills=None, grid=None, into=None):
+        """``(y, energies, dx)`` with ``y = self(x)`` [N, d_out], up to three bias terms on chosen outputs, ``energies[f] = (E_r, V_h,
+        V_g)`` [N, 3], and ``dx = d(E_r + V_h + V_g) / d x`` [N, n_inp, 3] (the gradient: forces are ``-dx``), float64, in ONE kernel
+        launch (`molann_value_and_bias_f64`, frames_value_bias_f64_kernel): what a production step of enhanced sampling carries -
+        metadynamics on a table plus walls, hills on top - for the cost of one pass over the frame, where `value_and_restraint`,
+        `value_and_hills` and `value_and_grid` back to back compute the rotation, the features, the head and its backward three times.
+        ``restraint``: a `molann_amd.bias.Restraint` ``(center, kappa, period=None, flat=None)`` on ALL outputs, as
+        `value_and_restraint` takes them (``kappa[k] = 0`` leaves output k free).  ``hills``: a `molann_amd.bias.Hills` ``(centers,
+        heights, sigma, period=None, columns=None)`` as `value_and_hills` takes them, on the outputs ``columns`` - distinct indices in
+        any order, at most 8; ``centers`` [H, len(columns)], ``sigma`` and ``period`` are laid out in the order of the list; None
+        means the first ``centers.shape[1]`` outputs.  ``grid``: a `molann_amd.bias.Grid` ``(table, lower, spacing, periodic=None,
+        columns=None)`` as `value_and_grid` takes them, on at most 3 outputs, axis 0 of the table being the first listed.  The lists
+        may overlap each other and the restrained outputs, so a model with any number of outputs takes a table on two of them.  Any
+        term may be None, not all three (ValueError); an absent term's energy is exactly 0.  The three energies are kept apart:
+        well-tempered heights and reweighting need ``V_h`` / ``V_g`` without the walls.  Periods, flat bottoms, per-frame centres,
+        ``H = 0``, shared or per-hill widths, periodic or clamped axes, conversions and the remembered ``sigma`` / ``flat`` read-backs
+        are the single calls'.  ``y`` is `value_and_vjp`'s, bit for bit; with one term alone on identity columns its energy and
+        ``dx`` are the single call's, bit for bit.  An output's cotangent is the restraint's, then the hills' is added, then the
+        table's: a fixed order, the same bits on every call, whatever N.  A frame that is not finite gets NaN and no other frame
+        does.  Columns that are not integers, or a term that is not its record: TypeError; an index outside the outputs or repeated:
+        IndexError; more than 8 / 3 columns: NotImplementedError.  No autograd graph is recorded; ``into=(y, energies, dx)`` reuses
+        the caller's buffers.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan.  Out of scope:
+        float32, more than one term of a kind, a restraint on a list of columns (use ``kappa = 0``), a `GraphedForces` replay of this
+        launch, gradients with respect to parameters or bias tables."""
+        _check_bias_terms("value_and_bias", restraint, hills, grid)
+        return self._one_launch_f64(_BIAS, self._one_launch_state(x, _BIAS, "float64"), x, (restraint, hills, grid), into)
 
     def _tangent_present(self, x):
         if _has_tangent(x):
@@ -1598,7 +1716,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
                 st["op_vjp"], st["op_jacobian"], st["op_metric"] = (torch.ops.molann.value_and_vjp_h, torch.ops.molann.value_and_jacobian_h,
                                                                     torch.ops.molann.value_and_metric_h)
                 st["op_restraint"], st["op_hills"] = torch.ops.molann.value_and_restraint_h, torch.ops.molann.value_and_hills_h
-                st["op_grid"] = torch.ops.molann.value_and_grid_h
+                st["op_grid"], st["op_bias"] = torch.ops.molann.value_and_grid_h, torch.ops.molann.value_and_bias_h
                 from . import script
                 st["desc"] = script.make_desc(script.KIND_FORWARD, fl.input_atom_num,
                                               align_idx=al._local_align_atom_indices if al is not None else None,

@@ -6,9 +6,75 @@ has period ``n_k * spacing[k]`` (so the point after the last is the first again)
 ``[lower[k], lower[k] + (n_k - 1) * spacing[k]]``.  A metadynamics run that starts with `MolANN.value_and_hills` moves to the table
 with `add_hills_to_grid`: deposit each new hill onto the table and call `value_and_grid`, whose cost does not grow with the run."""
 
+import collections
+import operator
+
 import torch
 
-__all__ = ["grid_points", "add_hills_to_grid"]
+__all__ = ["grid_points", "add_hills_to_grid", "Restraint", "Hills", "Grid"]
+
+HILLS_MAX_COLUMNS = 8     # HILLS_MAX_D of csrc/molann_math.h
+GRID_MAX_COLUMNS = 3      # GRID_MAX_D of csrc/molann_math.h
+
+
+def _columns(name, columns, cap, route):
+    """A record's `columns`: None (the first outputs, as many as the term is wide) or a list / tuple / range of distinct output
+    indices >= 0 in any order, returned as a tuple of ints.  Anything else: TypeError; a negative or repeated index: IndexError; more
+    than `cap`: NotImplementedError naming the route that remains.  The upper end is checked against the model, in `value_and_bias`."""
+    if columns is None:
+        return None
+    if not isinstance(columns, (list, tuple, range)):
+        raise TypeError("%s: `columns` must be None or a list, tuple or range of output indices; got %s" % (name, type(columns).__name__))
+    cols = []
+    for c in columns:
+        if isinstance(c, bool):
+            raise TypeError("%s: `columns` must hold integers; got a bool" % name)
+        try:
+            cols.append(operator.index(c))
+        except TypeError:
+            raise TypeError("%s: `columns` must hold integers; got %s" % (name, type(c).__name__))
+    if any(c < 0 for c in cols):
+        raise IndexError("%s: `columns` holds output indices >= 0; got %s" % (name, cols))
+    if len(set(cols)) != len(cols):
+        raise IndexError("%s: `columns` must be distinct; got %s" % (name, cols))
+    if not cols:
+        raise ValueError("%s: `columns` must name at least one output (leave the term out for none)" % name)
+    if len(cols) > cap:
+        raise NotImplementedError("%s: the one-launch kernel serves at most %d columns (got %d); %s" % (name, cap, len(cols), route))
+    return tuple(cols)
+
+
+class Restraint(collections.namedtuple("Restraint", "center kappa period flat")):
+    """The harmonic restraint of `MolANN.value_and_bias`, on all outputs: `MolANN.value_and_restraint`'s arguments (``kappa[k] = 0``
+    leaves output k free).  Immutable; the tensors are held, not copied."""
+    __slots__ = ()
+
+    def __new__(cls, center, kappa, period=None, flat=None):
+        return super().__new__(cls, center, kappa, period, flat)
+
+
+class Hills(collections.namedtuple("Hills", "centers heights sigma period columns")):
+    """The metadynamics hills of `MolANN.value_and_bias` on the outputs ``columns`` (distinct indices in any order, at most 8; None:
+    the first ``centers.shape[1]``): `MolANN.value_and_hills`' arguments, ``centers`` [H, len(columns)], ``sigma`` and ``period``
+    laid out over the chosen outputs in the order of the list.  Immutable; the tensors are held, not copied."""
+    __slots__ = ()
+
+    def __new__(cls, centers, heights, sigma, period=None, columns=None):
+        columns = _columns("Hills", columns, HILLS_MAX_COLUMNS, "form the hill sum and its derivative on `model(x)[:, columns]` with "
+                           "torch, scatter it into a cotangent, then `value_and_vjp`")
+        return super().__new__(cls, centers, heights, sigma, period, columns)
+
+
+class Grid(collections.namedtuple("Grid", "table lower spacing periodic columns")):
+    """The tabulated bias of `MolANN.value_and_bias` on the outputs ``columns`` (distinct indices in any order, at most 3; None: the
+    first ``table.dim()``): `MolANN.value_and_grid`'s arguments, axis 0 of ``table`` (the slowest) being the first listed output.
+    Immutable; the table is held, not copied, and read at launch as it is."""
+    __slots__ = ()
+
+    def __new__(cls, table, lower, spacing, periodic=None, columns=None):
+        columns = _columns("Grid", columns, GRID_MAX_COLUMNS, "interpolate the table and its derivative on `model(x)[:, columns]` with "
+                           "torch, scatter it into a cotangent, then `value_and_vjp`")
+        return super().__new__(cls, table, lower, spacing, periodic, columns)
 
 
 def grid_points(shape, lower, spacing, device=None):

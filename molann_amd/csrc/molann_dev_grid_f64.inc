@@ -27,6 +27,45 @@ struct GridF64Args : VjpF64Args {
     int periodic[GRID_MAX_D];     // != 0: the axis has period n h
 };
 
+// Step 3g's axis steps and stencil loop, one text for this kernel and frames_value_bias_f64_kernel (molann_dev_bias_f64.inc): y is the
+// frame's row of d values in LDS (a broadcast read), lane gl takes the stencil points gl, gl + G, ... < 4^d ascending.  Returns the
+// group's V; acc[k < d] leaves as the group's dV/dy_k.
+template <int G>
+__device__ __forceinline__ double frame_grid_stencil_f64(const double* y, const double* __restrict__ table, const long (&n)[GRID_MAX_D],
+                                                         const double (&lower)[GRID_MAX_D], const double (&spacing)[GRID_MAX_D],
+                                                         const int (&periodic)[GRID_MAX_D], int d, int gl, double (&acc)[GRID_MAX_D]) {
+    const int points = 1 << (2 * d);
+    long idx[GRID_MAX_D][4];
+    double wa[GRID_MAX_D][4], wb[GRID_MAX_D][4];
+#pragma unroll
+    for (int k = 0; k < GRID_MAX_D; ++k) {
+        if (k < d) {
+            grid_axis_f64(y[k], n[k], lower[k], spacing[k], periodic[k] != 0, idx[k], wa[k], wb[k]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { idx[k][j] = 0; wa[k][j] = 0.; wb[k][j] = 0.; }
+        }
+    }
+    double v = 0.;
+    // 64 / G rounds whatever d: a round past the last point loads a point again (p wraps, the address is a stencil point's)
+    // and adds nothing, so no load sits behind a branch and all of a lane's loads are in flight together
+#pragma unroll
+    for (int r = 0; r < 64 / G; ++r) {
+        const int p = gl + r * G;
+        double term[GRID_MAX_D];
+        const double t = grid_stencil_term_f64(p & (points - 1), d, table, n, idx, wa, wb, term);
+        const bool mine = p < points;
+        v += mine ? t : 0.;
+#pragma unroll
+        for (int k = 0; k < GRID_MAX_D; ++k) acc[k] += mine ? term[k] : 0.;
+    }
+    v = group_sum<G>(v);
+#pragma unroll
+    for (int k = 0; k < GRID_MAX_D; ++k)
+        if (k < d) acc[k] = group_sum<G>(acc[k]);
+    return v;
+}
+
 template <int G>
 __global__ __launch_bounds__(256) void frames_value_grid_f64_kernel(const double* __restrict__ x, const double* __restrict__ table,
                                                                     double* __restrict__ out, double* __restrict__ bias,
@@ -43,7 +82,6 @@ __global__ __launch_bounds__(256) void frames_value_grid_f64_kernel(const double
     const long frame_dw = 3l * a.n_inp;
     const bool has_align = a.n_align > 0;
     const bool has_head = m.n_layers > 0;
-    const int points = 1 << (2 * a.d_out);
     // cot first, then the rows of frames_value_vjp_f64_kernel where there is a head (lds_per_frame = d_out without one)
     double* cot = (double*)smem + (size_t)slot * a.lds_per_frame;
     double* feat = cot + a.d_out;
@@ -67,35 +105,8 @@ __global__ __launch_bounds__(256) void frames_value_grid_f64_kernel(const double
         if (has_head) zl = frame_head_forward_f64<G>(m, gl, feat, zrows, row0, row1, cot);
         // ---- 3g. the table on the outputs
         for (int k = gl; k < a.d_out; k += G) of[k] = cot[k];
-        long idx[GRID_MAX_D][4];
-        double wa[GRID_MAX_D][4], wb[GRID_MAX_D][4];
-#pragma unroll
-        for (int k = 0; k < GRID_MAX_D; ++k) {
-            if (k < a.d_out) {
-                grid_axis_f64(cot[k], a.n[k], a.lower[k], a.h[k], a.periodic[k] != 0, idx[k], wa[k], wb[k]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { idx[k][j] = 0; wa[k][j] = 0.; wb[k][j] = 0.; }
-            }
-        }
-        double v = 0.;
         double acc[GRID_MAX_D] = {0., 0., 0.};
-        // 64 / G rounds whatever d_out: a round past the last point loads a point again (p wraps, the address is a stencil point's)
-        // and adds nothing, so no load sits behind a branch and all of a lane's loads are in flight together
-#pragma unroll
-        for (int r = 0; r < 64 / G; ++r) {
-            const int p = gl + r * G;
-            double term[GRID_MAX_D];
-            const double t = grid_stencil_term_f64(p & (points - 1), a.d_out, table, a.n, idx, wa, wb, term);
-            const bool mine = p < points;
-            v += mine ? t : 0.;
-#pragma unroll
-            for (int k = 0; k < GRID_MAX_D; ++k) acc[k] += mine ? term[k] : 0.;
-        }
-        v = group_sum<G>(v);
-#pragma unroll
-        for (int k = 0; k < GRID_MAX_D; ++k)
-            if (k < a.d_out) acc[k] = group_sum<G>(acc[k]);
+        const double v = frame_grid_stencil_f64<G>(cot, table, a.n, a.lower, a.h, a.periodic, a.d_out, gl, acc);
         lds_wave_sync();   // every lane has read y from cot
 #pragma unroll
         for (int k = 0; k < GRID_MAX_D; ++k)

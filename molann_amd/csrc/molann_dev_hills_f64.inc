@@ -23,6 +23,28 @@ struct HillsF64Args : VjpF64Args {
     long sigma_stride;   // doubles between the hills' rows of sigma: 0 or d_out
 };
 
+// Step 3h's walk, one text for this kernel and frames_value_bias_f64_kernel (molann_dev_bias_f64.inc): y is the frame's row of d values in
+// LDS (a broadcast read), lane gl takes hills gl, gl + G, ... ascending.  Returns the group's V; acc[k < d] leaves as the group's sum of
+// the hills' g s_k / sigma_k, so dV/dy_k is -acc[k].  n_hills == 0 is a uniform skip: 0, acc as it came (zeros), no pointer read.
+template <int G>
+__device__ __forceinline__ double frame_hill_walk_f64(const double* y, const double* __restrict__ centers, const double* __restrict__ heights,
+                                                      const double* __restrict__ sigma, const double* __restrict__ period, long n_hills,
+                                                      long sigma_stride, int d, int gl, double (&acc)[HILLS_MAX_D]) {
+    double v = 0.;
+    if (n_hills > 0) {    // the first step of a run has no table: no walk, no sums
+        const bool shared = sigma_stride == 0;
+        double inv[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
+        if (shared) hill_inverse_widths_f64(sigma, d, inv);
+        for (long hh = gl; hh < n_hills; hh += G)
+            v += hill_term_f64(y, centers + hh * d, sigma + hh * sigma_stride, inv, shared, period, heights[hh], d, acc);
+        v = group_sum<G>(v);
+#pragma unroll
+        for (int k = 0; k < HILLS_MAX_D; ++k)
+            if (k < d) acc[k] = group_sum<G>(acc[k]);
+    }
+    return v;
+}
+
 template <int G>
 __global__ __launch_bounds__(256) void frames_value_hills_f64_kernel(const double* __restrict__ x, const double* __restrict__ centers,
                                                                      const double* __restrict__ heights, const double* __restrict__ sigma,
@@ -63,19 +85,8 @@ __global__ __launch_bounds__(256) void frames_value_hills_f64_kernel(const doubl
         if (has_head) zl = frame_head_forward_f64<G>(m, gl, feat, zrows, row0, row1, cot);
         // ---- 3h. the hills on the outputs
         for (int k = gl; k < a.d_out; k += G) of[k] = cot[k];
-        double v = 0.;
         double acc[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
-        if (a.n_hills > 0) {    // the first step of a run has no table: no walk, no sums
-            const bool shared = a.sigma_stride == 0;
-            double inv[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
-            if (shared) hill_inverse_widths_f64(sigma, a.d_out, inv);
-            for (long hh = gl; hh < a.n_hills; hh += G)
-                v += hill_term_f64(cot, centers + hh * a.d_out, sigma + hh * a.sigma_stride, inv, shared, period, heights[hh], a.d_out, acc);
-            v = group_sum<G>(v);
-#pragma unroll
-            for (int k = 0; k < HILLS_MAX_D; ++k)
-                if (k < a.d_out) acc[k] = group_sum<G>(acc[k]);
-        }
+        const double v = frame_hill_walk_f64<G>(cot, centers, heights, sigma, period, a.n_hills, a.sigma_stride, a.d_out, gl, acc);
         lds_wave_sync();   // every lane has read y from cot
 #pragma unroll
         for (int k = 0; k < HILLS_MAX_D; ++k)

@@ -63,6 +63,7 @@ using namespace molann;
 #include "molann_dev_restraint_f64.inc"
 #include "molann_dev_hills_f64.inc"
 #include "molann_dev_grid_f64.inc"
+#include "molann_dev_bias_f64.inc"
 #include "molann_dev_jac_f64.inc"
 #include "molann_dev_metric_f64.inc"
 // Host code (what `make san` instruments: -fno-gpu-sanitize leaves the device code alone):

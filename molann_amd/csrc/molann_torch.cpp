@@ -752,6 +752,145 @@ std::vector<at::Tensor> value_and_grid_h_hip(const at::Tensor& x_in, int64_t han
     return value_and_grid_impl(x_in, *desc_of(handle, "molann::value_and_grid_h"), ref_x, weights, biases, table, lower, spacing, periodic, into);
 }
 
+// {out, energies, grad_x}: the float64 forward's outputs, up to three bias terms on chosen outputs - the restraint of value_and_restraint on all
+// of them, the hills of value_and_hills on `hills_columns`, the table of value_and_grid on `grid_columns` - energies[N, 3] = (E_r, V_h, V_g)
+// and the gradient of their sum grad_x[N, n_inp, 3] in ONE launch (molann_value_and_bias_f64 on the float64 Linear tensors).  A term is
+// absent where `kappa` is none / a column list is empty; not all three.  The lists hold distinct output indices in any order; the hill
+// table and the grid are laid out over them in the order of the list.  Tensors float64 on x's device (the Python methods convert what is
+// not, and check sigma > 0); lower, spacing, periodic host values (periodic may be empty).  `into`: none or {out, energies, grad_x}.
+at::Tensor bias_tensor(const char* what, const c10::optional<at::Tensor>& t, const at::Tensor& x, bool required) {
+    if (!t.has_value() || !t->defined()) {
+        TORCH_CHECK_VALUE(!required, "molann::value_and_bias: `", what, "` is required by a term that is present");
+        return at::Tensor();
+    }
+    TORCH_CHECK_TYPE(t->scalar_type() == at::kDouble, "molann::value_and_bias: `", what, "` must be float64 (got ", t->scalar_type(), ")");
+    TORCH_CHECK_VALUE(t->device() == x.device(), "molann::value_and_bias: `", what, "` must be on ", x.device());
+    return t->detach().contiguous();
+}
+std::vector<int32_t> bias_columns(const char* what, const std::vector<int64_t>& columns, int64_t cap, int64_t cols) {
+    std::vector<int32_t> list;
+    for (size_t j = 0; j < columns.size(); ++j) {
+        TORCH_CHECK_INDEX(columns[j] >= 0 && columns[j] < cols, "molann::value_and_bias: `", what, "` must lie in [0, ", cols, "); got ", columns[j]);
+        for (size_t i = 0; i < j; ++i) TORCH_CHECK_INDEX(columns[i] != columns[j], "molann::value_and_bias: `", what, "` must be distinct");
+        list.push_back((int32_t)columns[j]);
+    }
+    TORCH_CHECK_NOT_IMPLEMENTED((int64_t)columns.size() <= cap, "molann::value_and_bias: the one-launch kernel serves at most ", cap, " `", what,
+                                "` (got ", columns.size(), "); use run, form the terms on the chosen columns with torch, then value_and_vjp");
+    return list;
+}
+std::vector<at::Tensor> value_and_bias_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                            const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                                            const c10::optional<at::Tensor>& center_in, const c10::optional<at::Tensor>& kappa_in,
+                                            const c10::optional<at::Tensor>& rperiod_in, const c10::optional<at::Tensor>& flat_in,
+                                            const std::vector<int64_t>& hills_columns, const c10::optional<at::Tensor>& centers_in,
+                                            const c10::optional<at::Tensor>& heights_in, const c10::optional<at::Tensor>& sigma_in,
+                                            const c10::optional<at::Tensor>& hperiod_in, const std::vector<int64_t>& grid_columns,
+                                            const c10::optional<at::Tensor>& table_in, const std::vector<double>& lower,
+                                            const std::vector<double>& spacing, const c10::List<bool>& periodic_in, const std::vector<at::Tensor>& into) {
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_bias is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_bias: a forward or a features description");
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    const bool has_r = kappa_in.has_value() && kappa_in->defined(), has_h = !hills_columns.empty(), has_g = !grid_columns.empty();
+    TORCH_CHECK_VALUE(has_r || has_h || has_g, "molann::value_and_bias: at least one of the restraint, the hills and the table must be given");
+    const std::vector<int32_t> hc = bias_columns("hills_columns", hills_columns, 8, cols), gc = bias_columns("grid_columns", grid_columns, 3, cols);
+    const int64_t dh = (int64_t)hc.size(), dg = (int64_t)gc.size();
+    molann_bias_terms_f64 t;
+    memset(&t, 0, sizeof(t));
+    at::Tensor center, kappa, rperiod, flat, centers, heights, sigma, hperiod, table;
+    if (has_r) {
+        center = bias_tensor("center", center_in, x, true); kappa = bias_tensor("kappa", kappa_in, x, true);
+        rperiod = bias_tensor("restraint_period", rperiod_in, x, false); flat = bias_tensor("flat", flat_in, x, false);
+        const bool per_frame = center.dim() == 2 && center.size(0) == n && center.size(1) == cols;
+        TORCH_CHECK_VALUE(per_frame || (center.dim() == 1 && center.size(0) == cols), "molann::value_and_bias: `center` must be [", cols, "] or [N, out_dim]");
+        TORCH_CHECK_VALUE(kappa.dim() == 1 && kappa.size(0) == cols && (!rperiod.defined() || (rperiod.dim() == 1 && rperiod.size(0) == cols)) &&
+                              (!flat.defined() || (flat.dim() == 1 && flat.size(0) == cols)),
+                          "molann::value_and_bias: `kappa`, `restraint_period` and `flat` must be [", cols, "]");
+        t.center = center.data_ptr<double>(); t.center_stride = per_frame ? cols : 0; t.kappa = kappa.data_ptr<double>();
+        t.restraint_period = rperiod.defined() ? rperiod.data_ptr<double>() : nullptr;
+        t.flat = flat.defined() ? flat.data_ptr<double>() : nullptr;
+    }
+    if (has_h) {
+        centers = bias_tensor("centers", centers_in, x, true); heights = bias_tensor("heights", heights_in, x, true);
+        sigma = bias_tensor("sigma", sigma_in, x, true); hperiod = bias_tensor("hills_period", hperiod_in, x, false);
+        TORCH_CHECK_VALUE(centers.dim() == 2 && centers.size(1) == dh, "molann::value_and_bias: `centers` must be [H, ", dh, "]");
+        const int64_t n_hills = centers.size(0);
+        const bool per_hill = sigma.dim() == 2 && sigma.size(0) == n_hills && sigma.size(1) == dh;
+        TORCH_CHECK_VALUE(heights.dim() == 1 && heights.size(0) == n_hills && (per_hill || (sigma.dim() == 1 && sigma.size(0) == dh)) &&
+                              (!hperiod.defined() || (hperiod.dim() == 1 && hperiod.size(0) == dh)),
+                          "molann::value_and_bias: `heights` must be [H], `sigma` [", dh, "] or [H, ", dh, "], `hills_period` [", dh, "]");
+        t.n_hills_columns = (int32_t)dh; t.hills_columns = hc.data(); t.n_hills = n_hills;
+        t.centers = n_hills > 0 ? centers.data_ptr<double>() : nullptr; t.heights = n_hills > 0 ? heights.data_ptr<double>() : nullptr;
+        t.sigma = n_hills > 0 ? sigma.data_ptr<double>() : nullptr; t.sigma_stride = per_hill ? dh : 0;
+        t.hills_period = hperiod.defined() ? hperiod.data_ptr<double>() : nullptr;
+    }
+    int64_t shape[3] = {4, 4, 4};
+    int32_t periodic[3] = {0, 0, 0};
+    if (has_g) {
+        table = bias_tensor("table", table_in, x, true);
+        TORCH_CHECK_VALUE(table.dim() == dg && table_in->is_contiguous(), "molann::value_and_bias: `table` must be contiguous with one dimension per "
+                          "grid column (", dg, ")");
+        TORCH_CHECK_VALUE((int64_t)lower.size() == dg && (int64_t)spacing.size() == dg && (periodic_in.size() == 0 || (int64_t)periodic_in.size() == dg),
+                          "molann::value_and_bias: `lower`, `spacing` and `periodic` must hold one value per grid column (", dg, ")");
+        for (int64_t k = 0; k < dg; ++k) {
+            shape[k] = table.size(k);
+            TORCH_CHECK_VALUE(shape[k] >= 4, "molann::value_and_bias: every dimension of `table` must have at least 4 points (got ", shape[k], ")");
+            TORCH_CHECK_VALUE(std::isfinite(spacing[k]) && spacing[k] > 0.0 && std::isfinite(lower[k]),
+                              "molann::value_and_bias: `spacing` must be finite and > 0 and `lower` finite");
+            periodic[k] = periodic_in.size() > 0 && periodic_in.get(k) ? 1 : 0;
+        }
+        TORCH_CHECK_VALUE(table.numel() < (int64_t(1) << 31), "molann::value_and_bias: `table` must hold fewer than 2^31 points");
+        t.n_grid_columns = (int32_t)dg; t.grid_columns = gc.data(); t.table = table.data_ptr<double>();
+        t.shape = shape; t.lower = lower.data(); t.spacing = spacing.data(); t.periodic = periodic;
+    }
+    TORCH_CHECK(into.empty() || into.size() == 3, "molann::value_and_bias: `into` must be a triple of tensors (out, energies, grad_x)");
+    at::Tensor out, energies, gx;
+    if (into.empty()) {
+        out = at::empty({n, cols}, x.options()); energies = at::empty({n, 3}, x.options()); gx = at::empty_like(x);
+    } else {
+        out = into[0]; energies = into[1]; gx = into[2];
+        const int64_t counts[3] = {n * cols, 3 * n, x.numel()};
+        for (int i = 0; i < 3; ++i) {
+            TORCH_CHECK_TYPE(into[i].scalar_type() == at::kDouble, "molann::value_and_bias: `into` must be float64 like x");
+            TORCH_CHECK_VALUE(into[i].is_contiguous() && into[i].numel() == counts[i] && into[i].device() == x.device(),
+                              "molann::value_and_bias: `into` must be contiguous {[N, out_dim], [N, 3], [N, n_inp, 3]} on x's device");
+        }
+    }
+    F64Linears lin;
+    f64_linears("molann::value_and_bias", *e, x, weights, biases, lin, ": call .double()");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_bias_f64(e->plan) == 1,
+                                "molann::value_and_bias: one frame's rows exceed the LDS of a compute unit for this model; use run, form the terms "
+                                "on the chosen columns with torch, then value_and_vjp");
+    if (n == 0) return {out, energies, gx};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_bias_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), &t, out.data_ptr<double>(),
+                                    energies.data_ptr<double>(), gx.data_ptr<double>(), stream),
+          "molann_value_and_bias_f64");
+    return {out, energies, gx};
+}
+#define MOLANN_BIAS_OP_PARAMS                                                                                                                        \
+    const at::Tensor &ref_x, std::vector<at::Tensor> weights, std::vector<at::Tensor> biases, const c10::optional<at::Tensor>&center,                \
+        const c10::optional<at::Tensor>&kappa, const c10::optional<at::Tensor>&rperiod, const c10::optional<at::Tensor>&flat,                        \
+        std::vector<int64_t> hills_columns, const c10::optional<at::Tensor>&centers, const c10::optional<at::Tensor>&heights,                        \
+        const c10::optional<at::Tensor>&sigma, const c10::optional<at::Tensor>&hperiod, std::vector<int64_t> grid_columns,                           \
+        const c10::optional<at::Tensor>&table, std::vector<double> lower, std::vector<double> spacing, c10::List<bool> periodic,                     \
+        std::vector<at::Tensor> into
+#define MOLANN_BIAS_OP_ARGS                                                                                                                          \
+    ref_x, weights, biases, center, kappa, rperiod, flat, hills_columns, centers, heights, sigma, hperiod, grid_columns, table, lower, spacing, periodic, into
+std::vector<at::Tensor> value_and_bias_hip(const at::Tensor& x_in, std::vector<int64_t> desc, MOLANN_BIAS_OP_PARAMS) {
+    return value_and_bias_impl(x_in, desc, MOLANN_BIAS_OP_ARGS);
+}
+std::vector<at::Tensor> value_and_bias_h_hip(const at::Tensor& x_in, int64_t handle, MOLANN_BIAS_OP_PARAMS) {
+    return value_and_bias_impl(x_in, *desc_of(handle, "molann::value_and_bias_h"), MOLANN_BIAS_OP_ARGS);
+}
+
 // The fused forward that also keeps the features: {out, features} - or {out, empty} where the plan has no such twin of its
 // kernel (molann_plan_backward_kind != 1 ... != 2 plans recompute in molann_backward_f32).  float32 fused plans.
 std::vector<at::Tensor> run_train_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -1387,6 +1526,12 @@ TORCH_LIBRARY(molann, m) {
           "bool[] periodic, Tensor[] into) -> Tensor[]");
     m.def("value_and_grid(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor table, float[] lower, float[] spacing, "
           "bool[] periodic, Tensor[] into) -> Tensor[]");
+    m.def("value_and_bias_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, Tensor? restraint_period, "
+          "Tensor? flat, int[] hills_columns, Tensor? centers, Tensor? heights, Tensor? sigma, Tensor? hills_period, int[] grid_columns, Tensor? table, "
+          "float[] lower, float[] spacing, bool[] periodic, Tensor[] into) -> Tensor[]");
+    m.def("value_and_bias(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, Tensor? restraint_period, "
+          "Tensor? flat, int[] hills_columns, Tensor? centers, Tensor? heights, Tensor? sigma, Tensor? hills_period, int[] grid_columns, Tensor? table, "
+          "float[] lower, float[] spacing, bool[] periodic, Tensor[] into) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
     m.def("run_head(Tensor feat, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases) -> Tensor", run_head);
@@ -1417,6 +1562,8 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_hills_h", value_and_hills_h_hip);
     m.impl("value_and_grid", value_and_grid_hip);
     m.impl("value_and_grid_h", value_and_grid_h_hip);
+    m.impl("value_and_bias", value_and_bias_hip);
+    m.impl("value_and_bias_h", value_and_bias_h_hip);
 }
 
 TORCH_LIBRARY_IMPL(molann, Autograd, m) { m.impl("run", run_autograd); }

@@ -3,8 +3,9 @@
 // molann_dev_vjp_f64.inc), molann_value_and_jacobian_f64 (frames_value_jac_f64_kernel, molann_dev_jac_f64.inc),
 // molann_value_and_metric_f64 (frames_value_metric_f64_kernel, molann_dev_metric_f64.inc), molann_value_and_restraint_f64
 // (frames_value_restraint_f64_kernel, molann_dev_restraint_f64.inc), molann_value_and_hills_f64 (frames_value_hills_f64_kernel,
-// molann_dev_hills_f64.inc) and molann_value_and_grid_f64 (frames_value_grid_f64_kernel, molann_dev_grid_f64.inc).  One argument front
-// end, one launch and one dispatch over the lane group serve the six; an entry names its kernel, its pointers and its rows.
+// molann_dev_hills_f64.inc), molann_value_and_grid_f64 (frames_value_grid_f64_kernel, molann_dev_grid_f64.inc) and
+// molann_value_and_bias_f64 (frames_value_bias_f64_kernel, molann_dev_bias_f64.inc).  One argument front end, one launch and one dispatch
+// over the lane group serve the seven; an entry names its kernel, its pointers and its rows.
 namespace {
 
 constexpr size_t VJP64_LDS_DEFAULT = 65536;    // dynamic LDS a launch may ask for as it is
@@ -16,7 +17,7 @@ constexpr int HILLS64_MAX_D_OUT = HILLS_MAX_D;
 // the widest output the grid kernel serves: the table has one axis per output (grid_axis_f64 of molann_math.h)
 constexpr int GRID64_MAX_D_OUT = GRID_MAX_D;
 
-enum F64Entry { F64_VJP, F64_JACOBIAN, F64_METRIC, F64_RESTRAINT, F64_HILLS, F64_GRID };
+enum F64Entry { F64_VJP, F64_JACOBIAN, F64_METRIC, F64_RESTRAINT, F64_HILLS, F64_GRID, F64_BIAS };
 
 struct Vjp64Geom {
     int G, block;       // lanes per frame, threads per block
@@ -41,6 +42,13 @@ inline void vjp64_rows(const molann_plan* p, int& max_w, int& per_frame) {
 inline void restraint64_rows(const molann_plan* p, int& max_w, int& per_frame) {
     vjp64_rows(p, max_w, per_frame);
     const long total = (long)per_frame + (p->n_layers > 0 ? p->dims[p->n_layers] : p->d_feat);
+    per_frame = total > (1l << 28) ? (1 << 28) : (int)total;
+}
+
+// doubles of LDS per frame of the bias on chosen outputs: the restraint's rows and the selection row of BIAS_SEL, whatever terms a call has
+inline void bias64_rows(const molann_plan* p, int& max_w, int& per_frame) {
+    restraint64_rows(p, max_w, per_frame);
+    const long total = (long)per_frame + BIAS_SEL;
     per_frame = total > (1l << 28) ? (1 << 28) : (int)total;
 }
 
@@ -83,13 +91,15 @@ inline void f64_entry_rows(const molann_plan* p, JacF64Args& a) { jac64_rows(p, 
 inline void f64_entry_rows(const molann_plan* p, RestraintF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, HillsF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, GridF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
+inline void f64_entry_rows(const molann_plan* p, BiasF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }
 
-// geometry for this entry: the forces' rows, the restraint's (the hills' and the grid's too) or the Jacobian's, and the metric's, the
-// hills' and the grid's caps on the outputs
+// geometry for this entry: the forces' rows, the restraint's (the hills' and the grid's too), the bias' or the Jacobian's, and the
+// metric's, the hills' and the grid's caps on the outputs
 inline Vjp64Geom f64_entry_geometry(const molann_plan* p, F64Entry entry) {
     int max_w, z_w, per_frame;
     if (entry == F64_VJP) vjp64_rows(p, max_w, per_frame);
     else if (entry == F64_RESTRAINT || entry == F64_HILLS || entry == F64_GRID) restraint64_rows(p, max_w, per_frame);
+    else if (entry == F64_BIAS) bias64_rows(p, max_w, per_frame);
     else jac64_rows(p, max_w, z_w, per_frame);
     Vjp64Geom g = vjp64_geometry_rows(p, max_w, per_frame);
     const int d_out = p->n_layers > 0 ? p->dims[p->n_layers] : p->d_feat;
@@ -106,7 +116,7 @@ struct F64Call {    // what a launch takes besides the caller's pointers
     F64Mlp m;
 };
 
-// The argument front end of the six entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
+// The argument front end of the seven entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
 // must be there (`required`), their and the `optional` ones' 8-byte alignment (a null optional pointer passes), items, the head's
 // tensors layer by layer, geometry.  Nothing is dereferenced but W and b.
 template <class Args>
@@ -182,6 +192,56 @@ inline bool grid_geometry_f64(int d, const int64_t* shape, const double* lower, 
         n[k] = (long)shape[k]; lo[k] = lower[k]; h[k] = spacing[k]; per[k] = periodic && periodic[k] ? 1 : 0;
     }
     return true;
+}
+
+// one frame's hills on the host, through the functions the kernels call and in the order of one lane: returns V, dy[k < d] = dV/dy_k
+inline double host_hills_f64(const double* y, int d, const double* centers, const double* heights, int64_t n_hills, const double* sigma,
+                             int64_t sigma_stride, const double* period, double* dy) {
+    double v = 0.;
+    double acc[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.}, inv[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
+    const bool shared = sigma_stride == 0;
+    if (shared && n_hills > 0) hill_inverse_widths_f64(sigma, d, inv);
+    for (int64_t h = 0; h < n_hills; ++h)
+        v += hill_term_f64(y, centers + h * d, sigma + h * sigma_stride, inv, shared, period, heights[h], d, acc);
+    if (dy)
+        for (int k = 0; k < d; ++k) dy[k] = -acc[k];
+    return v;
+}
+
+// one frame's interpolation on the host, the same way: returns V, dy[k < d] = dV/dy_k; NaN for a grid grid_geometry_f64 refuses
+inline double host_grid_f64(const double* y, int d, const double* table, const int64_t* shape, const double* lower, const double* spacing,
+                            const int32_t* periodic, double* dy) {
+    long n[GRID_MAX_D], idx[GRID_MAX_D][4] = {};
+    double lo[GRID_MAX_D], h[GRID_MAX_D], a[GRID_MAX_D][4] = {}, b[GRID_MAX_D][4] = {};
+    int per[GRID_MAX_D];
+    if (!grid_geometry_f64(d, shape, lower, spacing, periodic, n, lo, h, per)) return (double)NAN;
+    for (int k = 0; k < d; ++k) grid_axis_f64(y[k], n[k], lo[k], h[k], per[k] != 0, idx[k], a[k], b[k]);
+    double v = 0.;
+    double acc[GRID_MAX_D] = {0., 0., 0.};
+    for (int p = 0; p < (1 << (2 * d)); ++p) {
+        double term[GRID_MAX_D];
+        v += grid_stencil_term_f64(p, d, table, n, idx, a, b, term);
+        for (int k = 0; k < GRID_MAX_D; ++k) acc[k] += term[k];
+    }
+    if (dy)
+        for (int k = 0; k < d; ++k) dy[k] = acc[k];
+    return v;
+}
+
+// a column list of molann_value_and_bias_f64 against d_out, in the order of the refusals: an entry outside [0, d_out) or repeated
+// (MOLANN_E_INDEX), more than `cap` entries (MOLANN_E_UNSUPPORTED), an identity list longer than d_out (MOLANN_E_INDEX); then the list is
+// in `cols`
+inline int bias_columns_f64(int32_t count, const int32_t* list, int cap, int d_out, int* cols) {
+    if (list)
+        for (int32_t j = 0; j < count; ++j) {
+            if (list[j] < 0 || list[j] >= d_out) return MOLANN_E_INDEX;
+            for (int32_t i = 0; i < j; ++i)
+                if (list[i] == list[j]) return MOLANN_E_INDEX;
+        }
+    if (count > cap) return MOLANN_E_UNSUPPORTED;
+    if (!list && count > d_out) return MOLANN_E_INDEX;
+    for (int j = 0; j < cap; ++j) cols[j] = j < count ? (list ? list[j] : j) : 0;
+    return MOLANN_OK;
 }
 
 } // namespace
@@ -286,6 +346,51 @@ int molann_value_and_grid_f64(molann_plan* p, const double* x, int64_t n, const 
                             bias, grad_x);
 }
 
+int molann_plan_supports_value_and_bias_f64(const molann_plan* p) {
+    if (!p) return MOLANN_E_NULL;
+    return f64_entry_geometry(p, F64_BIAS).ok ? 1 : 0;
+}
+
+int molann_value_and_bias_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b,
+                              const molann_bias_terms_f64* t, double* out, double* energies, double* grad_x, molann_stream_t stream) {
+    if (p && !t) return MOLANN_E_NULL;
+    // the host arrays of a present table are required pointers like the others: refused with them, before alignment (and, like them, not
+    // looked at where n <= 0)
+    if (p && n > 0 && t->n_grid_columns > 0 && (!t->shape || !t->lower || !t->spacing)) return MOLANN_E_NULL;
+    F64Call<BiasF64Args> c;
+    // A term that is absent has none of its pointers looked at (x stands in for them below); the hill table is required where it has rows,
+    // as molann_value_and_hills_f64 has it.
+    const bool has_r = t && t->kappa, has_h = t && t->n_hills_columns > 0, has_g = t && t->n_grid_columns > 0, rows = has_h && t->n_hills > 0;
+    const int e = f64_entry_arguments(p, F64_BIAS, n,
+                                      {x, out, energies, grad_x, has_r ? t->center : x, rows ? t->centers : x, rows ? t->heights : x,
+                                       rows ? t->sigma : x, has_g ? t->table : x},
+                                      {has_r ? t->restraint_period : nullptr, has_r ? t->flat : nullptr, has_h ? t->hills_period : nullptr,
+                                       has_h && !rows ? t->centers : nullptr, has_h && !rows ? t->heights : nullptr,
+                                       has_h && !rows ? t->sigma : nullptr},
+                                      W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    if (!has_r && t->n_hills_columns == 0 && t->n_grid_columns == 0) return MOLANN_E_DESC;
+    if (t->n_hills_columns < 0 || t->n_grid_columns < 0 || (has_h && t->n_hills < 0)) return MOLANN_E_DESC;
+    BiasF64Args& a = c.a;
+    if (has_r && t->center_stride != 0 && t->center_stride != a.d_out) return MOLANN_E_DESC;
+    if (has_h && t->sigma_stride != 0 && t->sigma_stride != t->n_hills_columns) return MOLANN_E_DESC;
+    if (!grid_geometry_f64(has_g ? t->n_grid_columns : 0, t->shape, t->lower, t->spacing, t->periodic, a.n, a.lower, a.h, a.periodic))
+        return MOLANN_E_DESC;
+    int rc = bias_columns_f64(t->n_hills_columns, t->hills_columns, HILLS_MAX_D, a.d_out, a.hc);
+    if (rc == MOLANN_OK) rc = bias_columns_f64(t->n_grid_columns, t->grid_columns, GRID_MAX_D, a.d_out, a.gc);
+    if (rc != MOLANN_OK) return rc;
+    a.has_restraint = has_r ? 1 : 0;
+    a.n_hc = t->n_hills_columns; a.n_gc = t->n_grid_columns;
+    a.center_stride = has_r ? (long)t->center_stride : 0;
+    a.n_hills = has_h ? (long)t->n_hills : 0;
+    a.sigma_stride = has_h ? (long)t->sigma_stride : 0;
+    const double* none = nullptr;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_bias_f64_kernel, c.g.G), "frames_value_bias_f64_kernel", "bias", p, c, stream, x,
+                            has_r ? t->center : none, has_r ? t->kappa : none, has_r ? t->restraint_period : none, has_r ? t->flat : none,
+                            rows ? t->centers : none, rows ? t->heights : none, rows ? t->sigma : none, has_h ? t->hills_period : none,
+                            has_g ? t->table : none, out, energies, grad_x);
+}
+
 double molann_selftest_act_derivative_f64(int act, double z) { return act_derivative_f64(act, z); }
 
 double molann_selftest_restraint_f64(double y, double z, double kappa, double period, double flat, double* dy) {
@@ -298,15 +403,7 @@ double molann_selftest_restraint_f64(double y, double z, double kappa, double pe
 double molann_selftest_hills_f64(const double* y, int d, const double* centers, const double* heights, int64_t n_hills, const double* sigma,
                                  int64_t sigma_stride, const double* period, double* dy) {
     if (!y || d < 1 || d > HILLS64_MAX_D_OUT || n_hills < 0 || (n_hills > 0 && (!centers || !heights || !sigma))) return (double)NAN;
-    double v = 0.;
-    double acc[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.}, inv[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
-    const bool shared = sigma_stride == 0;
-    if (shared && n_hills > 0) hill_inverse_widths_f64(sigma, d, inv);
-    for (int64_t h = 0; h < n_hills; ++h)
-        v += hill_term_f64(y, centers + h * d, sigma + h * sigma_stride, inv, shared, period, heights[h], d, acc);
-    if (dy)
-        for (int k = 0; k < d; ++k) dy[k] = -acc[k];
-    return v;
+    return host_hills_f64(y, d, centers, heights, n_hills, sigma, sigma_stride, period, dy);
 }
 
 void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]) {
@@ -323,21 +420,41 @@ void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spa
 double molann_selftest_grid_f64(const double* y, int d, const double* table, const int64_t* shape, const double* lower, const double* spacing,
                                 const int32_t* periodic, double* dy) {
     if (!y || !table || !shape || !lower || !spacing || d < 1 || d > GRID64_MAX_D_OUT) return (double)NAN;
-    long n[GRID_MAX_D], idx[GRID_MAX_D][4] = {};
-    double lo[GRID_MAX_D], h[GRID_MAX_D], a[GRID_MAX_D][4] = {}, b[GRID_MAX_D][4] = {};
-    int per[GRID_MAX_D];
-    if (!grid_geometry_f64(d, shape, lower, spacing, periodic, n, lo, h, per)) return (double)NAN;
-    for (int k = 0; k < d; ++k) grid_axis_f64(y[k], n[k], lo[k], h[k], per[k] != 0, idx[k], a[k], b[k]);
-    double v = 0.;
-    double acc[GRID_MAX_D] = {0., 0., 0.};
-    for (int p = 0; p < (1 << (2 * d)); ++p) {
-        double term[GRID_MAX_D];
-        v += grid_stencil_term_f64(p, d, table, n, idx, a, b, term);
-        for (int k = 0; k < GRID_MAX_D; ++k) acc[k] += term[k];
+    return host_grid_f64(y, d, table, shape, lower, spacing, periodic, dy);
+}
+
+int molann_selftest_bias_f64(const double* y, int d_out, const molann_bias_terms_f64* t, double* energies, double* dy) {
+    if (!y || !t || !energies || !dy) return MOLANN_E_NULL;
+    const bool has_r = t->kappa, has_h = t->n_hills_columns > 0, has_g = t->n_grid_columns > 0;
+    if (d_out < 1 || t->n_hills_columns < 0 || t->n_grid_columns < 0 || (!has_r && !has_h && !has_g) || (has_h && t->n_hills < 0)) return MOLANN_E_DESC;
+    if ((has_r && !t->center) || (has_h && t->n_hills > 0 && (!t->centers || !t->heights || !t->sigma)) ||
+        (has_g && (!t->table || !t->shape || !t->lower || !t->spacing)))
+        return MOLANN_E_NULL;
+    int hc[HILLS_MAX_D], gc[GRID_MAX_D], per[GRID_MAX_D];
+    long gn[GRID_MAX_D];
+    double lo[GRID_MAX_D], gh[GRID_MAX_D];
+    if (has_h && t->sigma_stride != 0 && t->sigma_stride != t->n_hills_columns) return MOLANN_E_DESC;
+    if (!grid_geometry_f64(has_g ? t->n_grid_columns : 0, t->shape, t->lower, t->spacing, t->periodic, gn, lo, gh, per)) return MOLANN_E_DESC;
+    int rc = bias_columns_f64(t->n_hills_columns, t->hills_columns, HILLS_MAX_D, d_out, hc);
+    if (rc == MOLANN_OK) rc = bias_columns_f64(t->n_grid_columns, t->grid_columns, GRID_MAX_D, d_out, gc);
+    if (rc != MOLANN_OK) return rc;
+    double ysel[BIAS_SEL] = {}, dh[HILLS_MAX_D] = {}, dg[GRID_MAX_D] = {};
+    for (int j = 0; j < t->n_hills_columns; ++j) ysel[j] = y[hc[j]];
+    for (int j = 0; j < t->n_grid_columns; ++j) ysel[HILLS_MAX_D + j] = y[gc[j]];
+    double e = 0., vh = 0., vg = 0.;
+    for (int k = 0; k < d_out; ++k) {
+        dy[k] = 0.;
+        if (has_r)
+            e += restraint_term_f64(y[k], t->center[k], t->kappa[k], t->restraint_period ? t->restraint_period[k] : 0.0, t->flat ? t->flat[k] : 0.0,
+                                    dy[k]);
     }
-    if (dy)
-        for (int k = 0; k < d; ++k) dy[k] = acc[k];
-    return v;
+    if (has_h)
+        vh = host_hills_f64(ysel, t->n_hills_columns, t->centers, t->heights, t->n_hills, t->sigma, t->sigma_stride, t->hills_period, dh);
+    if (has_g) vg = host_grid_f64(ysel + HILLS_MAX_D, t->n_grid_columns, t->table, t->shape, t->lower, t->spacing, t->periodic, dg);
+    for (int j = 0; j < t->n_hills_columns; ++j) dy[hc[j]] += dh[j];
+    for (int j = 0; j < t->n_grid_columns; ++j) dy[gc[j]] += dg[j];
+    energies[0] = e; energies[1] = vh; energies[2] = vg;
+    return MOLANN_OK;
 }
 
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* a, double* jac36) {
