@@ -9,7 +9,10 @@ from molann_amd import _capi
 
 pytestmark = pytest.mark.gpu
 
-ACTS = {_capi.ACT_TANH: torch.tanh, _capi.ACT_RELU: torch.relu, _capi.ACT_SIGMOID: torch.sigmoid}
+F = torch.nn.functional
+ACTS = {_capi.ACT_TANH: torch.tanh, _capi.ACT_RELU: torch.relu, _capi.ACT_SIGMOID: torch.sigmoid, _capi.ACT_IDENTITY: lambda t: t,
+        _capi.ACT_ELU: F.elu, _capi.ACT_SILU: F.silu, _capi.ACT_SOFTPLUS: F.softplus, _capi.ACT_LEAKY_RELU: F.leaky_relu,
+        _capi.ACT_GELU: F.gelu}
 
 
 def _plan(dims, act, n_inp=128, precision=_capi.MLP_BF16):
