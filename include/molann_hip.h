@@ -34,6 +34,15 @@
  *     ones, each buffer by its own address, with the same bits either way.  A call reads nothing outside its inputs and writes
  *     exactly its outputs' elements - never a byte before, between or behind them, whatever n_frames, the frame size and the
  *     output width are (tests/test_gpu_buffer_placement.py holds every entry to this inside guard bands).
+ *   - Frames are independent.  A value that is not finite (NaN, +-Inf) in one frame's rows of x, of a cotangent, of a tangent or
+ *     of a feature row makes that frame's results that depend on it non-finite and changes no bit of any other frame's results,
+ *     whatever n_frames is and wherever in the batch the frame sits.  "Depend": the feature columns whose item names the atom (a
+ *     position item's through the centroid, when the atom is aligned on), every head output, the energies and biases, and the
+ *     gradient, Jacobian and tangent rows of atoms that share a bond, angle or dihedral with it; the rotation of a frame whose
+ *     covariance is not finite is the identity, so rows that see the atom through the rotation alone may stay finite; +-Inf
+ *     behind a saturating activation is a finite number, and a bond of length Inf has gradient 0 in the coordinates that stayed
+ *     finite.  The sums over frames (grad_params) are the exception, as in torch: one such frame makes the elements it reaches NaN.
+ *     tests/test_gpu_frame_isolation.py holds every entry to this.
  *   - n_frames == 0 is legal and does nothing (the reference returns an empty tensor).
  *   - code object: gfx950 only.
  */

@@ -256,11 +256,13 @@ static int check_io_f64(const void* x, const void* out, int64_t n) {
     return MOLANN_OK;
 }
 
-static int launch_f64(const molann_plan* p, const double* x, int64_t n, double* out, int mode, hipStream_t stream) {
+static int launch_f64(const molann_plan* p, const double* x, int64_t n, double* out, int mode, hipStream_t stream, const char* what) {
     F64Args a;
     a.n_frames = n; a.n_inp = p->n_inp; a.n_align = p->n_align; a.n_items = p->n_items; a.out_cols = p->d_feat; a.mode = mode;
     const int grid = grid_for(p, n, 4, 8);
     hipLaunchKernelGGL(frames_f64_kernel, dim3(grid), dim3(256), 0, stream, x, out, p->d_align_idx, p->d_ref64, p->d_items, a);
+    // the geometry as the plan's bound, not this call's grid: the text does not change with n_frames (a block takes four frames a round)
+    snprintf(const_cast<molann_plan*>(p)->last_info, sizeof(p->last_info), "frames_f64_kernel (%s) grid<=%d block=256", what, grid_for(p, 1L << 40, 4, 8));
     return (int)hipGetLastError();
 }
 
@@ -269,8 +271,7 @@ int molann_align_f64(const molann_plan* p, const double* x, int64_t n, double* o
     if (p->n_align <= 0) return MOLANN_E_STAGE;
     const int c = check_io_f64(x, out_xyz, n);
     if (c != MOLANN_OK || n == 0) return c;
-    snprintf(const_cast<molann_plan*>(p)->last_info, sizeof(p->last_info), "frames_f64_kernel (aligned coordinates)");
-    return launch_f64(p, x, n, out_xyz, 1, (hipStream_t)stream);
+    return launch_f64(p, x, n, out_xyz, 1, (hipStream_t)stream, "aligned coordinates");
 }
 
 int molann_features_f64(const molann_plan* p, const double* x, int64_t n, double* out, molann_stream_t stream) {
@@ -278,8 +279,7 @@ int molann_features_f64(const molann_plan* p, const double* x, int64_t n, double
     if (p->n_items <= 0) return MOLANN_E_STAGE;
     const int c = check_io_f64(x, out, n);
     if (c != MOLANN_OK || n == 0) return c;
-    snprintf(const_cast<molann_plan*>(p)->last_info, sizeof(p->last_info), "frames_f64_kernel (features)");
-    return launch_f64(p, x, n, out, 0, (hipStream_t)stream);
+    return launch_f64(p, x, n, out, 0, (hipStream_t)stream, "features");
 }
 
 // dL/dx of molann_features_f64 for the same x: grad_f[N, feature_dim] -> grad_x[N, n_inp, 3], everything in double
@@ -294,7 +294,7 @@ int molann_features_backward_f64(const molann_plan* p, const double* x, const do
     a.n_frames = n; a.n_inp = p->n_inp; a.n_align = p->n_align; a.n_items = p->n_items; a.out_cols = p->d_feat; a.mode = 0;
     const int grid = grid_for(p, n, 4, 8);
     hipLaunchKernelGGL(frames_bwd_f64_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, grad_f, grad_x, p->d_align_idx, p->d_ref64, p->d_items, a);
-    snprintf(const_cast<molann_plan*>(p)->last_info, sizeof(p->last_info), "frames_bwd_f64_kernel");
+    snprintf(const_cast<molann_plan*>(p)->last_info, sizeof(p->last_info), "frames_bwd_f64_kernel grid<=%d block=256", grid_for(p, 1L << 40, 4, 8));
     return (int)hipGetLastError();
 }
 
@@ -344,7 +344,8 @@ int molann_forward_f64(const molann_plan* p, const double* x, int64_t n, const d
     }
     if ((e = molann_features_f64(p, x, n, features_work, stream)) != MOLANN_OK) return e;
     if ((e = molann_mlp_f64(p, features_work, n, W, b, out, stream)) != MOLANN_OK) return e;
-    snprintf(const_cast<molann_plan*>(p)->last_info, sizeof(p->last_info), "frames_f64_kernel (features) + mlp_f64_kernel");
+    snprintf(const_cast<molann_plan*>(p)->last_info, sizeof(p->last_info), "frames_f64_kernel (features) + mlp_f64_kernel grid<=%d block=256 each",
+             grid_for(p, 1L << 40, 4, 8));
     return e;
 }
 

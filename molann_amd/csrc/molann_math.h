@@ -431,7 +431,7 @@ MOLANN_HD void eval_item_backward(int type, V3 a0, V3 a1, V3 a2, V3 a3, const fl
     case IT_BOND: {
         const V3 r = a1 - a0;
         const float d2 = dot(r, r);
-        const float inv = d2 > 0.0f ? fast_rsq(d2) : 0.0f; // |r| = 0: subgradient 0
+        const float inv = d2 == 0.0f ? 0.0f : fast_rsq(d2); // |r| = 0: subgradient 0; a |r| that is not finite stays so
         axpy(ga1, g[0] * inv, r);
         axpy(ga0, -g[0] * inv, r);
         return;
@@ -786,7 +786,7 @@ MOLANN_HD void eval_item_backward_f64(int type, V3d a0, V3d a1, V3d a2, V3d a3, 
     case IT_BOND: {
         const V3d r = a1 - a0;
         const double d2 = dot(r, r);
-        const double inv = d2 > 0.0 ? 1.0 / sqrt(d2) : 0.0;
+        const double inv = d2 == 0.0 ? 0.0 : 1.0 / sqrt(d2);   // |r| = 0: subgradient 0; a |r| that is not finite stays so
         axpy(ga1, g[0] * inv, r);
         axpy(ga0, -g[0] * inv, r);
         return;
@@ -883,7 +883,7 @@ MOLANN_HD int eval_item_tangent_t(int type, V a0, V a1, V a2, V a3, V t0, V t1, 
         const V r = a1 - a0, dr = t1 - t0;
         const T d = tsqrt(dot(r, r));
         out[0] = d;
-        dout[0] = d > (T)0 ? dot(r, dr) / d : (T)0;   // |r| = 0: the subgradient 0 the backward takes
+        dout[0] = d == (T)0 ? (T)0 : dot(r, dr) / d;  // |r| = 0: the subgradient 0 the backward takes; a |r| that is not finite stays so
         return 1;
     }
     case IT_ANGLE_COS:
@@ -1039,7 +1039,7 @@ MOLANN_HD void eval_item_backward_gen(int type, V a0, V a1, V a2, V a3, const T 
     case IT_BOND: {
         const V r = a1 - a0;
         const T d2 = dot(r, r);
-        const T inv = value_of(d2) > 0.0 ? (T)(1.0 / tsqrt(d2)) : zero;
+        const T inv = value_of(d2) == 0.0 ? zero : (T)(1.0 / tsqrt(d2));
         axpy(ga1, g[0] * inv, r);
         axpy(ga0, -(g[0] * inv), r);
         return;

@@ -320,7 +320,8 @@ __device__ __forceinline__ void mlp_tile_backward(MlpTileState& st, float* S, co
                                 S[(d_row(l > 0 ? l - 1 : 0) + row) * SSTR + 16 * fb + n16] = d;
                                 sum += d;
                             } else {
-                                S[(GF_ROW + row) * SSTR + 16 * fb + n16] = G[kb][fb][r];
+                                // rows K .. pad4(K) are the next tile's K-padding: G is 0 * delta there, NaN for a frame that is not finite
+                                S[(GF_ROW + row) * SSTR + 16 * fb + n16] = row < K ? G[kb][fb][r] : 0.f;
                             }
                         }
                     }
