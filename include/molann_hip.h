@@ -374,6 +374,35 @@ int molann_value_and_hills_f64(molann_plan* plan, const double* x, int64_t n_fra
 /* 1 when molann_value_and_hills_f64 serves the plan (molann_value_and_restraint_f64 serves it and out_dim <= 8), 0 otherwise. */
 int molann_plan_supports_value_and_hills_f64(const molann_plan* plan);
 
+/* Values, an OPES bias on them - the logarithm of a KERNEL DENSITY (on-the-fly probability enhanced sampling, PLUMED's OPES_METAD) - AND
+ * its gradient in ONE launch of frames_value_opes_f64_kernel (ahead of time: no hipRTC): out[N, out_dim] = molann_value_and_vjp_f64's
+ * out, bit for bit,
+ *   P(y)    = sum_h heights[h] K_h(y),   K_h = exp(-q_h / 2) - exp(-cutoff^2 / 2) where q_h < cutoff^2, else 0,
+ *   q_h     = sum_k (d_hk / sigma_hk)^2,   d_hk = out[f, k] - centers[h * out_dim + k],
+ *   bias[f] = scale log(P(out[f]) / norm + epsilon),
+ * and grad_x[N, n_inp, 3] = d bias / d x = J^T (d bias / d out) - the gradient: forces are its negative - everything in double.
+ * centers, heights, n_kernels, sigma, sigma_stride and period as molann_value_and_hills_f64 takes them (the wrap of a periodic output,
+ * one row of widths or one per kernel, the table required only where n_kernels > 0, read at launch, nothing cached).  scale (the
+ * caller's kT (1 - 1 / biasfactor)), norm (its normalisation Z times the sum of the weights), epsilon and cutoff are host values and
+ * travel in the launch's arguments: changing them at every deposit costs nothing.  cutoff = +inf: no cutoff.  A kernel is dropped when
+ * q_h >= cutoff^2 is true, so the derivative JUMPS there, as it does in every OPES code.  n_kernels == 0 (the first step of a run):
+ * bias = scale log(epsilon), grad_x = 0.  The same for a frame outside every kernel's cutoff.  Negative heights are not checked; a
+ * frame with P / norm + epsilon <= 0 gets what log and the division give (NaN or +-inf) and no other frame does.  A NaN in a
+ * frame's out makes that frame's bias and grad_x NaN and no other's, at a finite cutoff too.  Every sum has a fixed order, every row
+ * of grad_x is stored once: no atomics, the same bits on every run, whatever n_frames.  Plans, argument checks, their order and their
+ * codes are molann_value_and_hills_f64's (out_dim <= 8: MOLANN_E_UNSUPPORTED beyond); after them a scale that is not finite, a norm or
+ * an epsilon that is not finite and > 0, a cutoff that is NaN or not > 0: MOLANN_E_DESC.  The call only enqueues on `stream` (no
+ * workspace, no event): thread-safe and capturable.  Out of scope: depositing, merging or compressing kernels and the update of the
+ * normalisation (between steps, on the caller's own tensors); an OPES term inside molann_value_and_bias_f64; float32; neighbour
+ * lists; gradients with respect to the table or the parameters. */
+int molann_value_and_opes_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                              const double* centers, const double* heights, int64_t n_kernels, const double* sigma, int64_t sigma_stride,
+                              const double* period, double scale, double norm, double epsilon, double cutoff, double* out, double* bias,
+                              double* grad_x, molann_stream_t stream);
+
+/* 1 when molann_value_and_opes_f64 serves the plan (molann_value_and_hills_f64 serves it), 0 otherwise. */
+int molann_plan_supports_value_and_opes_f64(const molann_plan* plan);
+
 /* Values, a bias interpolated from a TABLE over them AND its gradient in ONE launch of frames_value_grid_f64_kernel (ahead of time: no
  * hipRTC): out[N, out_dim] = molann_value_and_vjp_f64's out, bit for bit (out_dim = feature_dim for a plan without an MLP),
  * bias[N] = V(out) and grad_x[N, n_inp, 3] = d bias / d x = J^T (d bias / d out) - the gradient: forces are its negative - everything
@@ -514,6 +543,13 @@ double molann_selftest_restraint_f64(double y, double z, double kappa, double pe
  * negative n_hills or a missing pointer: NaN, dy untouched */
 double molann_selftest_hills_f64(const double* y, int d, const double* centers, const double* heights, int64_t n_hills, const double* sigma,
                                  int64_t sigma_stride, const double* period, double* dy);
+/* one frame's bias of molann_value_and_opes_f64 on the host, through the functions its kernel calls per kernel and per frame: returns
+ * scale log(P / norm + epsilon) for y[d] under the table and stores dy[k] = d bias / d y_k (dy may be NULL); kernels are added in
+ * ascending order; the four scalars are used as they come.  d outside 1..8, a negative n_kernels or a missing pointer: NaN, dy
+ * untouched */
+double molann_selftest_opes_f64(const double* y, int d, const double* centers, const double* heights, int64_t n_kernels, const double* sigma,
+                                int64_t sigma_stride, const double* period, double scale, double norm, double epsilon, double cutoff,
+                                double* dy);
 /* one axis' step of molann_value_and_grid_f64 on the host, through the function its kernel calls: the four table indices, the four
  * weights and the four derivative weights (s w' / spacing) for output value y on an axis of n points; any of the three may be NULL */
 void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]);

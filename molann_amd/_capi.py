@@ -172,6 +172,9 @@ def lib():
             "molann_plan_supports_value_and_restraint_f64": (i32, [vp]),
             "molann_value_and_hills_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
             "molann_plan_supports_value_and_hills_f64": (i32, [vp]),
+            "molann_value_and_opes_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, i64, vp, i64, vp] + [ctypes.c_double] * 4
+                                          + [vp, vp, vp, vp]),
+            "molann_plan_supports_value_and_opes_f64": (i32, [vp]),
             "molann_value_and_grid_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
             "molann_plan_supports_value_and_grid_f64": (i32, [vp]),
             "molann_value_and_bias_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(BiasTermsF64), vp, vp, vp, vp]),
@@ -192,6 +195,7 @@ def lib():
             "molann_selftest_act_derivative_f64": (ctypes.c_double, [i32, ctypes.c_double]),
             "molann_selftest_restraint_f64": (ctypes.c_double, [ctypes.c_double] * 5 + [ctypes.POINTER(ctypes.c_double)]),
             "molann_selftest_hills_f64": (ctypes.c_double, [vp, i32, vp, vp, i64, vp, i64, vp, vp]),
+            "molann_selftest_opes_f64": (ctypes.c_double, [vp, i32, vp, vp, i64, vp, i64, vp] + [ctypes.c_double] * 4 + [vp]),
             "molann_selftest_grid_axis_f64": (None, [ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32, vp, vp, vp]),
             "molann_selftest_grid_f64": (ctypes.c_double, [vp, i32, vp, vp, vp, vp, vp, vp]),
             "molann_selftest_bias_f64": (i32, [vp, i32, ctypes.POINTER(BiasTermsF64), vp, vp]),
@@ -508,6 +512,29 @@ class Plan(object):
                      heights.data_ptr() if heights is not None else None, n_hills, sigma.data_ptr(), sigma_stride,
                      period.data_ptr() if period is not None else None, out.data_ptr(), bias.data_ptr(), grad_x.data_ptr())
         return out, bias, grad_x
+
+    def supports_value_and_opes_f64(self):
+        """True when `value_and_opes_f64` serves this plan: `value_and_hills_f64` serves it (nothing is built)."""
+        return lib().molann_plan_supports_value_and_opes_f64(self._handle) == 1
+
+    def value_and_opes_f64(self, x, weights, biases, centers, heights, sigma, period, scale, norm, epsilon, cutoff, out, bias, grad_x,
+                           n_kernels=None, sigma_stride=None):
+        """out[N, d_out], bias[N] = scale log(P / norm + epsilon) with P = sum_h heights_h (exp(-q_h / 2) - exp(-cutoff^2 / 2)) over the
+        kernels with q_h = sum_k (d_hk / sigma_hk)^2 < cutoff^2 (d_h = out - centers_h, wrapped by `period`) and grad_x[N, n_inp, 3] =
+        d bias / d x in float64, one launch of frames_value_opes_f64_kernel.  The tensors as `value_and_hills_f64` takes them; `scale`,
+        `norm`, `epsilon`, `cutoff` floats (`cutoff` None or +inf: no cutoff)."""
+        W, B = _layer_pointers(weights, biases)
+        if n_kernels is None:
+            n_kernels = heights.numel() if heights is not None else 0
+        if sigma_stride is None:
+            sigma_stride = sigma.shape[-1] if sigma.dim() == 2 else 0
+        self._launch("molann_value_and_opes_f64", x.data_ptr(), x.shape[0], W, B, centers.data_ptr() if centers is not None else None,
+                     heights.data_ptr() if heights is not None else None, n_kernels, sigma.data_ptr() if sigma is not None else None, sigma_stride,
+                     period.data_ptr() if period is not None else None, float(scale), float(norm), float(epsilon),
+                     float("inf") if cutoff is None else float(cutoff), out.data_ptr(), bias.data_ptr(), grad_x.data_ptr())
+        return out, bias, grad_x
+
+    value_and_opes = value_and_opes_f64
 
     def supports_value_and_grid_f64(self):
         """True when `value_and_grid_f64` serves this plan: `value_and_restraint_f64` serves it and it has at most 3 outputs (nothing

@@ -922,9 +922,9 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
 
 # ---- The calls that give the values and a derivative in one launch: MolANN.value_and_vjp / value_and_jacobian / value_and_metric /
 # value_and_restraint / value_and_hills / value_and_grid / value_and_bias and PreprocessingANN.value_and_metric / value_and_restraint /
-# value_and_hills / value_and_grid / value_and_bias.  What differs
+# value_and_hills / value_and_grid / value_and_bias, and value_and_opes of both.  What differs
 # between them, by kind; the checks and the two ways to the kernel are written once below.
-_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID, _BIAS = 0, 1, 2, 3, 4, 5, 6
+_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID, _BIAS, _OPES = 0, 1, 2, 3, 4, 5, 6, 7
 _HILLS_MAX_D_OUT = 8      # HILLS64_MAX_D_OUT of csrc/molann_value_f64.inc: the kernel's cotangent sums are a register array
 _JACOBIAN_ROUTE = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
 _METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
@@ -937,14 +937,18 @@ _GRID_ROUTE = "use `model(x)`, interpolate the table and its derivative with tor
 _GRID_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, interpolate the table with torch and take torch.autograd.grad"
 _BIAS_ROUTE = "use `model(x)`, form the terms and their derivatives on the chosen columns with torch, then `value_and_vjp`"
 _BIAS_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, form the terms with torch and take torch.autograd.grad"
+_OPES_ROUTE = "use `model(x)`, form the kernel sum with `molann_amd.bias.opes_kernel_sum`, its logarithm and its derivative with torch, then `value_and_vjp`"
+_OPES_FEATURES_ROUTE = ("use `module(x)` on an x that requires grad, form the kernel sum with `molann_amd.bias.opes_kernel_sum` and its logarithm with "
+                        "torch and take torch.autograd.grad")
 _ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint", "value_and_hills", "value_and_grid",
-                    "value_and_bias")
+                    "value_and_bias", "value_and_opes")
 # the route that remains where the call refuses
-_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE, _BIAS_ROUTE)
-_ONE_LAUNCH_FEATURES_ROUTE = (None, None, None, _RESTRAINT_FEATURES_ROUTE, _HILLS_FEATURES_ROUTE, _GRID_FEATURES_ROUTE, _BIAS_FEATURES_ROUTE)
-_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)", "(y, bias, dx)", "(y, energies, dx)")   # what `into` holds
+_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE, _BIAS_ROUTE, _OPES_ROUTE)
+_ONE_LAUNCH_FEATURES_ROUTE = (None, None, None, _RESTRAINT_FEATURES_ROUTE, _HILLS_FEATURES_ROUTE, _GRID_FEATURES_ROUTE, _BIAS_FEATURES_ROUTE,
+                              _OPES_FEATURES_ROUTE)
+_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)", "(y, bias, dx)", "(y, energies, dx)", "(y, bias, dx)")   # what `into` holds
 # the dispatcher operator, in MolANN._fast_state
-_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid", "op_bias")
+_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid", "op_bias", "op_opes")
 _BIAS_KINDS = (_RESTRAINT, _HILLS, _GRID)      # the calls that return (y, a scalar per frame, dx)
 
 
@@ -1057,6 +1061,30 @@ def _check_hills_args(name, x, out_dim, centers, heights, sigma, period, into, o
     rows = [t if t is None or (t.dtype == torch.float64 and t.device == x.device and t.is_contiguous())
             else t.to(device=x.device, dtype=torch.float64).contiguous() for t in rows]
     return tuple(rows) + triple
+
+
+def _check_opes_args(name, x, out_dim, centers, heights, sigma, scale, norm, epsilon, cutoff, period, into, owner=None):
+    """The checks of value_and_opes, all before any launch on x's device: the four scalars as Python numbers (`scale` finite, `norm` and
+    `epsilon` finite and > 0, `cutoff` None - no cutoff, passed on as +inf - or > 0 and not NaN: ValueError; anything that is no number:
+    TypeError), more than 8 outputs (NotImplementedError naming the route), then `_check_hills_args` on the table, the widths, the period
+    and `into`.  Returns (centers, heights, sigma, period, scale, norm, epsilon, cutoff, y, bias, dx) as the kernel takes them."""
+    vals = []
+    for what, v in (("scale", scale), ("norm", norm), ("epsilon", epsilon), ("cutoff", math.inf if cutoff is None else cutoff)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError("%s: `%s` must be a Python float%s; got %s" % (name, what, " or None" if what == "cutoff" else "", type(v).__name__))
+        vals.append(float(v))
+    scale, norm, epsilon, cutoff = vals
+    if not math.isfinite(scale):
+        raise ValueError("%s: `scale` must be finite; got %r" % (name, scale))
+    for what, v in (("norm", norm), ("epsilon", epsilon)):
+        if not (math.isfinite(v) and v > 0.0):
+            raise ValueError("%s: `%s` must be finite and > 0; got %r" % (name, what, v))
+    if not cutoff > 0.0:
+        raise ValueError("%s: `cutoff` must be None (no cutoff) or > 0; got %r" % (name, cutoff))
+    if out_dim > _HILLS_MAX_D_OUT:
+        raise NotImplementedError("%s: the one-launch kernel serves at most %d outputs (got %d); %s" % (name, _HILLS_MAX_D_OUT, out_dim, _OPES_ROUTE))
+    checked = _check_hills_args(name, x, out_dim, centers, heights, sigma, period, into, owner=owner)
+    return checked[:4] + (scale, norm, epsilon, cutoff) + checked[4:]
 
 
 def _grid_floats(name, what, v, out_dim, unit="output"):
@@ -1228,6 +1256,9 @@ def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=
     elif kind == _BIAS:
         checked = _check_bias_args(name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:3], checked[3], (checked[4], checked[5]) if checked[3] is not None else None, (n, n_inp, 3)
+    elif kind == _OPES:
+        checked = _check_opes_args(name, x, out_dim, *extra, into, owner=owner)
+        return x, checked[:8], checked[8], (checked[9], checked[10]) if checked[8] is not None else None, (n, n_inp, 3)
     elif kind in _BIAS_KINDS:
         checked = (_check_restraint_args, _check_hills_args, _check_grid_args)[kind - _RESTRAINT](name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:4], checked[4], (checked[5], checked[6]) if checked[4] is not None else None, (n, n_inp, 3)
@@ -1244,7 +1275,10 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
     """The ctypes way to the kernel of a float64 one-launch call whose arguments `_one_launch_arguments` has checked."""
     plan = entry.plan
     with torch.cuda.device(x.device):
-        if kind in _BIAS_KINDS or kind == _BIAS:
+        if kind == _OPES:
+            if not plan.supports_value_and_opes_f64():
+                raise NotImplementedError("value_and_opes: one frame's rows exceed the LDS of a compute unit for this model; " + _OPES_ROUTE)
+        elif kind in _BIAS_KINDS or kind == _BIAS:
             if not (plan.supports_value_and_restraint_f64, plan.supports_value_and_hills_f64, plan.supports_value_and_grid_f64,
                     plan.supports_value_and_bias_f64)[kind - _RESTRAINT]():
                 raise NotImplementedError("%s: one frame's rows exceed the LDS of a compute unit for this model; %s"
@@ -1261,7 +1295,7 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
         if y is None:
             y = torch.empty((x.shape[0], out_dim), dtype=torch.float64, device=x.device)
             second = torch.empty(shape, dtype=torch.float64, device=x.device)
-            if kind in _BIAS_KINDS:
+            if kind in _BIAS_KINDS or kind == _OPES:
                 second = (torch.empty((x.shape[0],), dtype=torch.float64, device=x.device), second)
             if kind == _BIAS:
                 second = (torch.empty((x.shape[0], 3), dtype=torch.float64, device=x.device), second)
@@ -1279,6 +1313,11 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
             if x.shape[0] > 0:
                 plan.value_and_hills_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
                                          *extra, y, *second)
+            return (y,) + tuple(second)
+        if kind == _OPES:
+            if x.shape[0] > 0:
+                plan.value_and_opes_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
+                                        *extra, y, *second)
             return (y,) + tuple(second)
         if kind == _GRID:
             if x.shape[0] > 0:
@@ -1390,8 +1429,18 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
         _check_bias_terms("value_and_bias", restraint, hills, grid)
         return self._bias_on_features(_BIAS, x, (restraint, hills, grid), into)
 
+    def value_and_opes(self, x, centers, heights, sigma, scale, norm, epsilon, cutoff=None, period=None, into=None):
+        """``(feat, bias, dx)``: `MolANN.value_and_opes` on the features themselves, float64, in ONE kernel launch
+        (`molann_value_and_opes_f64`, frames_value_opes_f64_kernel, on this module's float64 feature plan; no head): an OPES bias
+        ``bias[f] = scale log(P(feat[f]) / norm + epsilon)`` on the kernel density ``P = sum_h heights_h (exp(-q_h / 2) - exp(-cutoff^2 /
+        2))`` over the kernels with ``q_h = sum_k (d_hk / sigma_hk)^2 < cutoff^2``, and ``dx = d bias / d x``; forces are ``-dx``.  OPES
+        on raw dihedral angles: ``use_angle_value=True`` and ``period = 2 pi``.  The arguments as `MolANN.value_and_opes` takes them; at
+        most 8 features.  No autograd graph is recorded; ``into=(feat, bias, dx)`` reuses the caller's buffers.  The same bits on every
+        call."""
+        return self._bias_on_features(_OPES, x, (centers, heights, sigma, scale, norm, epsilon, cutoff, period), into)
+
     def _bias_on_features(self, kind, x, extra, into):
-        """value_and_restraint / value_and_hills / value_and_grid / value_and_bias of this module: the gate, the checks and the ctypes plan of the features."""
+        """value_and_restraint / value_and_hills / value_and_grid / value_and_bias / value_and_opes of this module: the gate, the checks and the ctypes plan of the features."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and self._fusable()):
             raise NotImplementedError("%s needs a FeatureLayer behind an AlignmentLayer or none, float64, on a HIP tensor; "
                                       "otherwise %s" % (_ONE_LAUNCH_NAME[kind], _ONE_LAUNCH_FEATURES_ROUTE[kind]))
@@ -1532,7 +1581,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
             return _one_launch_ctypes(kind, st["entry"](), x, extra, y, second, shape, out_dim, lins, al)
         op, ref = st[_ONE_LAUNCH_OP[kind]], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"]
         W, B, into = [lin.weight for lin in lins], [lin.bias for lin in lins], list(into) if into is not None else []
-        if kind in _BIAS_KINDS:
+        if kind in _BIAS_KINDS or kind == _OPES:
             return tuple(op(x, st["handle"], ref, W, B, *extra, into))
         if kind == _BIAS:
             r, h, g = extra
@@ -1608,6 +1657,34 @@ class MolANN(_PlanOwner, torch.nn.Module):
         (append rows to your own tensors; well-tempered scaling uses the returned bias), cutoffs (a bias on a grid: `value_and_grid`), gradients with
         respect to parameters or hills."""
         return self._one_launch_f64(_HILLS, self._one_launch_state(x, _HILLS, "float64"), x, (centers, heights, sigma, period), into)
+
+    def value_and_opes(self, x, centers, heights, sigma, scale, norm, epsilon, cutoff=None, period=None, into=None):
+        """``(y, bias, dx)`` with ``y = self(x)`` [N, d_out], an OPES bias on it (on-the-fly probability enhanced sampling, PLUMED's
+        ``OPES_METAD``) - not a sum of hills but the logarithm of a kernel density -
+        ``bias[f] = scale log(P(y[f]) / norm + epsilon)``, ``P(y) = sum_h heights_h K_h(y)``,
+        ``K_h = exp(-q_h / 2) - exp(-cutoff^2 / 2)`` where ``q_h = sum_k (d_hk / sigma_hk)^2 < cutoff^2`` and 0 elsewhere,
+        ``d_hk = y[f, k] - centers[h, k]``, and ``dx = d bias / d x = J^T (d bias / d y)`` [N, n_inp, 3] (the gradient, like
+        `value_and_vjp`'s dx: forces are ``-dx``), float64, in ONE kernel launch (`molann_value_and_opes_f64`,
+        frames_value_opes_f64_kernel): the lanes that hold y walk the kernel table, as `value_and_hills` does, and take the logarithm
+        where the sums are.  Kernel compression keeps an OPES table at 10^2 - 10^3 entries for a whole run, which is where that walk
+        beats every other route.  ``centers`` [H, d_out], ``heights`` [H] or a float (the kernels' weights; negative ones are not
+        checked and may take the logarithm's argument below 0: NaN or -inf for that frame), ``sigma`` a float, [d_out] or [H, d_out],
+        > 0 everywhere or ValueError, ``period`` None or [d_out]: as `value_and_hills` takes them, with its conversions and its
+        remembered ``sigma`` read-back (pass prefixes ``table[:h]`` of preallocated tensors).  ``scale`` (kT (1 - 1 / biasfactor)),
+        ``norm`` (the normalisation Z times the sum of the weights), ``epsilon`` and ``cutoff`` are Python floats that travel in the
+        launch's arguments, so changing Z at every deposit costs nothing: ``scale`` finite, ``norm`` and ``epsilon`` finite and > 0,
+        ``cutoff`` None (no cutoff) or > 0, else ValueError before any launch.  A kernel is dropped where ``q_h >= cutoff^2``: the
+        derivative jumps there, as in every OPES code.  H may be 0 (the first step of a run): the bias is ``scale log(epsilon)`` and dx
+        zeros, and so they are for a frame outside every kernel's cutoff.  ``y`` is `value_and_vjp`'s, bit for bit.  A NaN poisons its
+        own frame only, at a finite cutoff too.  No autograd graph is recorded (parameters and kernels are data);
+        ``into=(y, bias, dx)`` reuses the caller's buffers.  Every sum has a fixed order and every row of dx is stored once: the same
+        bits on every call, whatever N.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at
+        most 8 outputs (NotImplementedError beyond).  Out of scope: depositing, merging or compressing kernels and the update of Z
+        (between steps, on your own tensors: `molann_amd.bias.opes_kernel_sum` gives P at the kernel centres), an OPES term inside
+        `value_and_bias`, float32, a `GraphedForces` replay of this launch, neighbour lists, gradients with respect to the table or the
+        parameters."""
+        return self._one_launch_f64(_OPES, self._one_launch_state(x, _OPES, "float64"), x,
+                                    (centers, heights, sigma, scale, norm, epsilon, cutoff, period), into)
 
     def value_and_grid(self, x, table, lower, spacing, periodic=None, into=None):
         """``(y, bias, dx)`` with ``y = self(x)`` [N, d_out], a bias interpolated from a table over it, ``bias[f] = V(y[f])`` [N], and
@@ -1717,6 +1794,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
                                                                     torch.ops.molann.value_and_metric_h)
                 st["op_restraint"], st["op_hills"] = torch.ops.molann.value_and_restraint_h, torch.ops.molann.value_and_hills_h
                 st["op_grid"], st["op_bias"] = torch.ops.molann.value_and_grid_h, torch.ops.molann.value_and_bias_h
+                st["op_opes"] = torch.ops.molann.value_and_opes_h
                 from . import script
                 st["desc"] = script.make_desc(script.KIND_FORWARD, fl.input_atom_num,
                                               align_idx=al._local_align_atom_indices if al is not None else None,

@@ -4,14 +4,17 @@ table is plumbing between steps, not a hot path.
 A table has one axis per output, output 0 the slowest; grid point i of axis k sits at ``lower[k] + i * spacing[k]``.  A periodic axis
 has period ``n_k * spacing[k]`` (so the point after the last is the first again); any other spans
 ``[lower[k], lower[k] + (n_k - 1) * spacing[k]]``.  A metadynamics run that starts with `MolANN.value_and_hills` moves to the table
-with `add_hills_to_grid`: deposit each new hill onto the table and call `value_and_grid`, whose cost does not grow with the run."""
+with `add_hills_to_grid`: deposit each new hill onto the table and call `value_and_grid`, whose cost does not grow with the run.
+
+An OPES run (`MolANN.value_and_opes`) keeps its own kernel table; `opes_kernel_sum` gives the kernel density at any points - at the
+kernel centres for the normalisation Z, at a new sample for the weight of its deposit."""
 
 import collections
 import operator
 
 import torch
 
-__all__ = ["grid_points", "add_hills_to_grid", "Restraint", "Hills", "Grid"]
+__all__ = ["grid_points", "add_hills_to_grid", "opes_kernel_sum", "Restraint", "Hills", "Grid"]
 
 HILLS_MAX_COLUMNS = 8     # HILLS_MAX_D of csrc/molann_math.h
 GRID_MAX_COLUMNS = 3      # GRID_MAX_D of csrc/molann_math.h
@@ -122,3 +125,44 @@ def add_hills_to_grid(table, lower, spacing, periodic, centers, heights, sigma, 
             factors.append(torch.exp(-0.5 * s * s))
         table += torch.einsum(equation, heights[rows], *factors)
     return table
+
+
+def opes_kernel_sum(points, centers, heights, sigma, period=None, cutoff=None, chunk=1024):
+    """``P[m] = sum_h heights_h K_h(points[m])`` [M], float64, on points' device: `MolANN.value_and_opes`' kernel density before its
+    logarithm, ``K_h = exp(-q_h / 2) - exp(-cutoff^2 / 2)`` where ``q_h = sum_k (d_hk / sigma_hk)^2 < cutoff^2`` and 0 elsewhere,
+    ``d_hk = points[m, k] - centers[h, k]`` wrapped to ``d - P rint(d / P)`` where ``period[k] > 0``.  What a caller needs between
+    steps: the mean of P over the kernel centres updates Z, P at a new sample picks its deposit's weight.  ``points``: [M, d];
+    ``centers``: [H, d]; ``heights``: [H] or a float; ``sigma``: a float, [d] or [H, d], > 0; ``period``: None or [d]; ``cutoff``: None
+    (no cutoff) or > 0.  The kernels are taken ``chunk`` at a time, so the temporaries are ``M * chunk * d`` values.  Differentiable in
+    ``points`` by autograd."""
+    points = points.to(torch.float64) if isinstance(points, torch.Tensor) else torch.as_tensor(points, dtype=torch.float64)
+    f64 = dict(dtype=torch.float64, device=points.device)
+    if points.dim() != 2:
+        raise ValueError("opes_kernel_sum: `points` must be [M, d]; got %s" % list(points.shape))
+    d = points.shape[1]
+    centers = torch.as_tensor(centers, **f64).reshape(-1, d)
+    n_kernels = centers.shape[0]
+    heights = torch.as_tensor(heights, **f64).expand(n_kernels)
+    sigma = torch.as_tensor(sigma, **f64)
+    sigma = sigma.expand(n_kernels, d) if sigma.dim() < 2 else sigma
+    if sigma.shape != (n_kernels, d) or not bool((sigma > 0).all()):
+        raise ValueError("opes_kernel_sum: `sigma` must be a float, [d] or [H, d] and > 0 everywhere")
+    if cutoff is not None and not float(cutoff) > 0.0:
+        raise ValueError("opes_kernel_sum: `cutoff` must be None or > 0; got %r" % (cutoff,))
+    c2 = float("inf") if cutoff is None else float(cutoff) ** 2
+    c0 = torch.exp(torch.tensor(-0.5 * c2, **f64))
+    if period is not None:
+        period = torch.as_tensor(period, **f64).reshape(d)
+        periodic = period > 0
+        p_safe = torch.where(periodic, period, torch.ones_like(period))
+    total = torch.zeros(points.shape[0], **f64)
+    for start in range(0, n_kernels, int(chunk)):
+        rows = slice(start, start + int(chunk))
+        dd = points[:, None, :] - centers[None, rows, :]
+        if period is not None:
+            dd = torch.where(periodic, dd - p_safe * torch.round(dd / p_safe), dd)
+        s = dd / sigma[None, rows, :]
+        q = (s * s).sum(dim=2)
+        kernel = torch.where(q >= c2, torch.zeros_like(q), torch.exp(-0.5 * q) - c0)
+        total = total + (heights[rows] * kernel).sum(dim=1)
+    return total

@@ -599,6 +599,66 @@ MOLANN_HD double hill_term_f64(const double* y, const double* c, const double* s
     return g;
 }
 
+// One kernel of an OPES bias V(y) = scale log(P(y) / norm + epsilon), P(y) = sum_h w_h (exp(-q_h / 2) - exp(-cutoff^2 / 2)) over the
+// kernels with q_h < cutoff^2, q_h = sum_k (d_hk / sigma_hk)^2, on d <= HILLS_MAX_D outputs.  d_k, its wrap by period_k, 1 / sigma_k,
+// s_k = d_k (1 / sigma_k) and the ascending-k sum of s_k^2 are hill_term_f64's, operation for operation (so are `shared` and
+// hill_inverse_widths_f64); here q is that sum, not its half.  c2 = cutoff^2 and c0 = exp(-(0.5 c2)) come from the caller, once per
+// frame (opes_cutoff_f64).  A kernel with q >= c2 is dropped: it returns 0 and adds nothing, so a table with it and without it gives
+// the same bits.  Otherwise e = exp(-(0.5 q)): returns w (e - c0) and adds (w e) s_k / sigma_k to acc[k], so dP/dy_k is the NEGATIVE of
+// acc[k].  The test is q >= c2 and not !(q < c2): a NaN q fails it, reaches exp and makes the return and every acc[k] NaN.  cutoff =
+// +inf: c2 = +inf, c0 = 0, nothing is dropped.  The exp of a dropped kernel is computed and its results not taken (a select; measured
+// against a branch around the exp, which is no faster: the lanes of a wave hold different kernels and seldom all drop theirs, see
+// DESIGN.md); either form gives the same values.  Nothing is contracted, so the host and the device round alike up to exp.
+MOLANN_HD void opes_cutoff_f64(double cutoff, double& c2, double& c0) {
+#pragma clang fp contract(off)
+    c2 = cutoff * cutoff;
+    c0 = exp(-(0.5 * c2));
+}
+MOLANN_HD double opes_term_f64(const double* y, const double* c, const double* sigma, const double (&inv_shared)[HILLS_MAX_D], bool shared,
+                               const double* period, double w, double c2, double c0, int d, double (&acc)[HILLS_MAX_D]) {
+#pragma clang fp contract(off)
+    double t[HILLS_MAX_D];
+    double q = 0.0;
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k) {
+        t[k] = 0.0;
+        if (k < d) {
+            double dk = y[k] - c[k];
+            const double P = period ? period[k] : 0.0;
+            if (P > 0.0) {
+                const double turns = rint(dk / P);
+                const double whole = P * turns;
+                dk = dk - whole;
+            }
+            const double inv = shared ? inv_shared[k] : 1.0 / sigma[k];
+            const double s = dk * inv;
+            q = q + s * s;
+            t[k] = s * inv;
+        }
+    }
+    const bool drop = q >= c2;
+    const double e = exp(-(0.5 * q));
+    const double g = w * e;
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k)
+        if (k < d) acc[k] = drop ? acc[k] : acc[k] + g * t[k];
+    return drop ? 0.0 : w * (e - c0);
+}
+
+// The transform of an OPES bias, once per frame after the sums: u = P / norm + epsilon, V = scale log(u), f = scale / (norm u) and
+// cot[k] = dV/dy_k = -(f acc[k]) for the acc opes_term_f64 summed.  P = 0 and acc = 0 (no kernel yet, or every kernel past the
+// cutoff): V = scale log(epsilon), cot exactly 0 (-(f 0) is -0.0, which compares equal).  u <= 0 needs negative weights, which are
+// the caller's to avoid: log and the division give NaN or +-inf for that frame.  Nothing is contracted.
+MOLANN_HD double opes_transform_f64(double P, const double (&acc)[HILLS_MAX_D], double scale, double norm, double epsilon, int d,
+                                    double (&cot)[HILLS_MAX_D]) {
+#pragma clang fp contract(off)
+    const double u = P / norm + epsilon;
+    const double f = scale / (norm * u);
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k) cot[k] = k < d ? -(f * acc[k]) : 0.0;
+    return scale * log(u);
+}
+
 // A bias tabulated on a regular grid over d <= GRID_MAX_D outputs, interpolated by cubic convolution (Catmull-Rom): V(y) = sum over the
 // 4^d stencil points of T[idx_0 j0, ...] prod_k a_k jk, dV/dy_k the same sum with b_k jk in place of a_k jk.  grid_axis_f64 is one
 // axis' step: u = (y - lower) / h; periodic: u <- u - n floor(u / n), i = floor(u) held in [0, n - 1], idx_j = (i - 1 + j) mod n;

@@ -34,6 +34,7 @@
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <map>
 #include <memory>
@@ -677,6 +678,83 @@ std::vector<at::Tensor> value_and_hills_h_hip(const at::Tensor& x_in, int64_t ha
                                               std::vector<at::Tensor> biases, const at::Tensor& centers, const at::Tensor& heights,
                                               const at::Tensor& sigma, const c10::optional<at::Tensor>& period, std::vector<at::Tensor> into) {
     return value_and_hills_impl(x_in, *desc_of(handle, "molann::value_and_hills_h"), ref_x, weights, biases, centers, heights, sigma, period, into);
+}
+
+// {out, bias, grad_x}: the float64 forward's outputs, an OPES bias on them, bias[N] = scale log(P / norm + epsilon) with P = sum_h heights_h
+// (exp(-q_h / 2) - exp(-cutoff^2 / 2)) over the kernels with q_h = sum_k (d_hk / sigma_hk)^2 < cutoff^2, and its gradient grad_x[N, n_inp, 3]
+// in ONE launch (molann_value_and_opes_f64 on the float64 Linear tensors).  The tensors as value_and_hills takes them; scale, norm, epsilon
+// and cutoff (inf: none) are host values, checked here as the C entry checks them (the Python methods have checked them already).
+at::Tensor opes_table(const char* what, const at::Tensor& t, const at::Tensor& x, bool ok, const char* shape) {
+    TORCH_CHECK_TYPE(t.scalar_type() == at::kDouble, "molann::value_and_opes: `", what, "` must be float64 (got ", t.scalar_type(), ")");
+    TORCH_CHECK_VALUE(ok && t.device() == x.device(), "molann::value_and_opes: `", what, "` must be ", shape, " on ", x.device());
+    return t.detach().contiguous();
+}
+std::vector<at::Tensor> value_and_opes_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                            const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                                            const at::Tensor& centers_in, const at::Tensor& heights_in, const at::Tensor& sigma_in,
+                                            const c10::optional<at::Tensor>& period_in, double scale, double norm, double epsilon, double cutoff,
+                                            const std::vector<at::Tensor>& into) {
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_opes is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_opes: a forward or a features description");
+    TORCH_CHECK_VALUE(std::isfinite(scale) && std::isfinite(norm) && norm > 0.0 && std::isfinite(epsilon) && epsilon > 0.0 && cutoff > 0.0,
+                      "molann::value_and_opes: `scale` must be finite, `norm` and `epsilon` finite and > 0, `cutoff` > 0 (inf: none); got ", scale,
+                      ", ", norm, ", ", epsilon, ", ", cutoff);
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    const at::Tensor centers = opes_table("centers", centers_in, x, centers_in.dim() == 2 && centers_in.size(1) == cols, "[H, out_dim]");
+    const int64_t n_kernels = centers.size(0);
+    const at::Tensor heights = opes_table("heights", heights_in, x, heights_in.dim() == 1 && heights_in.size(0) == n_kernels, "[H]");
+    const bool per_kernel = sigma_in.dim() == 2 && sigma_in.size(0) == n_kernels && sigma_in.size(1) == cols;
+    const at::Tensor sigma = opes_table("sigma", sigma_in, x, per_kernel || (sigma_in.dim() == 1 && sigma_in.size(0) == cols), "[out_dim] or [H, out_dim]");
+    at::Tensor period;
+    if (period_in.has_value() && period_in->defined())
+        period = opes_table("period", *period_in, x, period_in->dim() == 1 && period_in->size(0) == cols, "[out_dim]");
+    TORCH_CHECK(into.empty() || into.size() == 3, "molann::value_and_opes: `into` must be a triple of tensors (out, bias, grad_x)");
+    at::Tensor out, bias, gx;
+    if (into.empty()) {
+        out = at::empty({n, cols}, x.options()); bias = at::empty({n}, x.options()); gx = at::empty_like(x);
+    } else {
+        out = into[0]; bias = into[1]; gx = into[2];
+        const int64_t counts[3] = {n * cols, n, x.numel()};
+        for (int i = 0; i < 3; ++i) {
+            TORCH_CHECK_TYPE(into[i].scalar_type() == at::kDouble, "molann::value_and_opes: `into` must be float64 like x");
+            TORCH_CHECK_VALUE(into[i].is_contiguous() && into[i].numel() == counts[i] && into[i].device() == x.device(),
+                              "molann::value_and_opes: `into` must be contiguous {[N, out_dim], [N], [N, n_inp, 3]} on x's device");
+        }
+    }
+    F64Linears lin;
+    f64_linears("molann::value_and_opes", *e, x, weights, biases, lin, ": call .double()");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_opes_f64(e->plan) == 1,
+                                "molann::value_and_opes: more than 8 outputs, or one frame's rows exceed the LDS of a compute unit for this model; "
+                                "use run, form the kernel sum, its logarithm and its derivative with torch, then value_and_vjp");
+    if (n == 0) return {out, bias, gx};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_opes_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), n_kernels > 0 ? centers.data_ptr<double>() : nullptr,
+                                    n_kernels > 0 ? heights.data_ptr<double>() : nullptr, n_kernels, sigma.data_ptr<double>(), per_kernel ? cols : 0,
+                                    period.defined() ? period.data_ptr<double>() : nullptr, scale, norm, epsilon, cutoff, out.data_ptr<double>(),
+                                    bias.data_ptr<double>(), gx.data_ptr<double>(), stream),
+          "molann_value_and_opes_f64");
+    return {out, bias, gx};
+}
+std::vector<at::Tensor> value_and_opes_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                           std::vector<at::Tensor> biases, const at::Tensor& centers, const at::Tensor& heights, const at::Tensor& sigma,
+                                           const c10::optional<at::Tensor>& period, double scale, double norm, double epsilon, double cutoff,
+                                           std::vector<at::Tensor> into) {
+    return value_and_opes_impl(x_in, desc, ref_x, weights, biases, centers, heights, sigma, period, scale, norm, epsilon, cutoff, into);
+}
+std::vector<at::Tensor> value_and_opes_h_hip(const at::Tensor& x_in, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                             std::vector<at::Tensor> biases, const at::Tensor& centers, const at::Tensor& heights,
+                                             const at::Tensor& sigma, const c10::optional<at::Tensor>& period, double scale, double norm,
+                                             double epsilon, double cutoff, std::vector<at::Tensor> into) {
+    return value_and_opes_impl(x_in, *desc_of(handle, "molann::value_and_opes_h"), ref_x, weights, biases, centers, heights, sigma, period, scale, norm,
+                               epsilon, cutoff, into);
 }
 
 // {out, bias, grad_x}: the float64 forward's outputs, a bias interpolated from `table` over them (cubic convolution on a regular grid: one
@@ -1522,6 +1600,10 @@ TORCH_LIBRARY(molann, m) {
           "Tensor? period, Tensor[] into) -> Tensor[]");
     m.def("value_and_hills(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor centers, Tensor heights, Tensor sigma, "
           "Tensor? period, Tensor[] into) -> Tensor[]");
+    m.def("value_and_opes_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor centers, Tensor heights, Tensor sigma, "
+          "Tensor? period, float scale, float norm, float epsilon, float cutoff, Tensor[] into) -> Tensor[]");
+    m.def("value_and_opes(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor centers, Tensor heights, Tensor sigma, "
+          "Tensor? period, float scale, float norm, float epsilon, float cutoff, Tensor[] into) -> Tensor[]");
     m.def("value_and_grid_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor table, float[] lower, float[] spacing, "
           "bool[] periodic, Tensor[] into) -> Tensor[]");
     m.def("value_and_grid(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor table, float[] lower, float[] spacing, "
@@ -1560,6 +1642,8 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_restraint_h", value_and_restraint_h_hip);
     m.impl("value_and_hills", value_and_hills_hip);
     m.impl("value_and_hills_h", value_and_hills_h_hip);
+    m.impl("value_and_opes", value_and_opes_hip);
+    m.impl("value_and_opes_h", value_and_opes_h_hip);
     m.impl("value_and_grid", value_and_grid_hip);
     m.impl("value_and_grid_h", value_and_grid_h_hip);
     m.impl("value_and_bias", value_and_bias_hip);

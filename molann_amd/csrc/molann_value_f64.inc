@@ -3,9 +3,10 @@
 // molann_dev_vjp_f64.inc), molann_value_and_jacobian_f64 (frames_value_jac_f64_kernel, molann_dev_jac_f64.inc),
 // molann_value_and_metric_f64 (frames_value_metric_f64_kernel, molann_dev_metric_f64.inc), molann_value_and_restraint_f64
 // (frames_value_restraint_f64_kernel, molann_dev_restraint_f64.inc), molann_value_and_hills_f64 (frames_value_hills_f64_kernel,
-// molann_dev_hills_f64.inc), molann_value_and_grid_f64 (frames_value_grid_f64_kernel, molann_dev_grid_f64.inc) and
-// molann_value_and_bias_f64 (frames_value_bias_f64_kernel, molann_dev_bias_f64.inc).  One argument front end, one launch and one dispatch
-// over the lane group serve the seven; an entry names its kernel, its pointers and its rows.
+// molann_dev_hills_f64.inc), molann_value_and_grid_f64 (frames_value_grid_f64_kernel, molann_dev_grid_f64.inc),
+// molann_value_and_bias_f64 (frames_value_bias_f64_kernel, molann_dev_bias_f64.inc) and molann_value_and_opes_f64
+// (frames_value_opes_f64_kernel, molann_dev_opes_f64.inc).  One argument front end, one launch and one dispatch over the lane group serve
+// the eight; an entry names its kernel, its pointers and its rows.
 namespace {
 
 constexpr size_t VJP64_LDS_DEFAULT = 65536;    // dynamic LDS a launch may ask for as it is
@@ -92,6 +93,7 @@ inline void f64_entry_rows(const molann_plan* p, RestraintF64Args& a) { restrain
 inline void f64_entry_rows(const molann_plan* p, HillsF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, GridF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, BiasF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }
+inline void f64_entry_rows(const molann_plan* p, OpesF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }   // the hills' rows, geometry and cap: F64_HILLS
 
 // geometry for this entry: the forces' rows, the restraint's (the hills' and the grid's too), the bias' or the Jacobian's, and the
 // metric's, the hills' and the grid's caps on the outputs
@@ -206,6 +208,30 @@ inline double host_hills_f64(const double* y, int d, const double* centers, cons
     if (dy)
         for (int k = 0; k < d; ++k) dy[k] = -acc[k];
     return v;
+}
+
+// one frame's OPES bias on the host, the same way: returns V, dy[k < d] = dV/dy_k
+inline double host_opes_f64(const double* y, int d, const double* centers, const double* heights, int64_t n_kernels, const double* sigma,
+                            int64_t sigma_stride, const double* period, double scale, double norm, double epsilon, double cutoff, double* dy) {
+    double p = 0.;
+    double acc[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.}, inv[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.}, cot[HILLS_MAX_D];
+    if (n_kernels > 0) {
+        const bool shared = sigma_stride == 0;
+        if (shared) hill_inverse_widths_f64(sigma, d, inv);
+        double c2, c0;
+        opes_cutoff_f64(cutoff, c2, c0);
+        for (int64_t h = 0; h < n_kernels; ++h)
+            p += opes_term_f64(y, centers + h * d, sigma + h * sigma_stride, inv, shared, period, heights[h], c2, c0, d, acc);
+    }
+    const double v = opes_transform_f64(p, acc, scale, norm, epsilon, d, cot);
+    if (dy)
+        for (int k = 0; k < d; ++k) dy[k] = cot[k];
+    return v;
+}
+
+// the four scalars of molann_value_and_opes_f64: scale finite; norm and epsilon finite and > 0; cutoff > 0, +inf for none (a NaN fails)
+inline bool opes_scalars_f64(double scale, double norm, double epsilon, double cutoff) {
+    return std::isfinite(scale) && std::isfinite(norm) && norm > 0.0 && std::isfinite(epsilon) && epsilon > 0.0 && cutoff > 0.0;
 }
 
 // one frame's interpolation on the host, the same way: returns V, dy[k < d] = dV/dy_k; NaN for a grid grid_geometry_f64 refuses
@@ -328,6 +354,29 @@ int molann_value_and_hills_f64(molann_plan* p, const double* x, int64_t n, const
                             heights, sigma, period, out, bias, grad_x);
 }
 
+int molann_plan_supports_value_and_opes_f64(const molann_plan* p) {
+    if (!p) return MOLANN_E_NULL;
+    return f64_entry_geometry(p, F64_HILLS).ok ? 1 : 0;
+}
+
+int molann_value_and_opes_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b, const double* centers,
+                              const double* heights, int64_t n_kernels, const double* sigma, int64_t sigma_stride, const double* period, double scale,
+                              double norm, double epsilon, double cutoff, double* out, double* bias, double* grad_x, molann_stream_t stream) {
+    if (p && n_kernels < 0) return MOLANN_E_DESC;
+    F64Call<OpesF64Args> c;
+    // the table is required where it has rows, as molann_value_and_hills_f64 has it
+    const int e = n_kernels > 0 ? f64_entry_arguments(p, F64_HILLS, n, {x, centers, heights, sigma, out, bias, grad_x}, {period}, W, b, c)
+                                : f64_entry_arguments(p, F64_HILLS, n, {x, out, bias, grad_x}, {centers, heights, sigma, period}, W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    if (sigma_stride != 0 && sigma_stride != c.a.d_out) return MOLANN_E_DESC;
+    if (!opes_scalars_f64(scale, norm, epsilon, cutoff)) return MOLANN_E_DESC;
+    c.a.n_kernels = (long)n_kernels;
+    c.a.sigma_stride = (long)sigma_stride;
+    c.a.scale = scale; c.a.norm = norm; c.a.epsilon = epsilon; c.a.cutoff = cutoff;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_opes_f64_kernel, c.g.G), "frames_value_opes_f64_kernel", "opes", p, c, stream, x, centers,
+                            heights, sigma, period, out, bias, grad_x);
+}
+
 int molann_plan_supports_value_and_grid_f64(const molann_plan* p) {
     if (!p) return MOLANN_E_NULL;
     return f64_entry_geometry(p, F64_GRID).ok ? 1 : 0;
@@ -404,6 +453,12 @@ double molann_selftest_hills_f64(const double* y, int d, const double* centers, 
                                  int64_t sigma_stride, const double* period, double* dy) {
     if (!y || d < 1 || d > HILLS64_MAX_D_OUT || n_hills < 0 || (n_hills > 0 && (!centers || !heights || !sigma))) return (double)NAN;
     return host_hills_f64(y, d, centers, heights, n_hills, sigma, sigma_stride, period, dy);
+}
+
+double molann_selftest_opes_f64(const double* y, int d, const double* centers, const double* heights, int64_t n_kernels, const double* sigma,
+                                int64_t sigma_stride, const double* period, double scale, double norm, double epsilon, double cutoff, double* dy) {
+    if (!y || d < 1 || d > HILLS64_MAX_D_OUT || n_kernels < 0 || (n_kernels > 0 && (!centers || !heights || !sigma))) return (double)NAN;
+    return host_opes_f64(y, d, centers, heights, n_kernels, sigma, sigma_stride, period, scale, norm, epsilon, cutoff, dy);
 }
 
 void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]) {
