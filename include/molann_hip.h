@@ -393,8 +393,8 @@ int molann_plan_supports_value_and_hills_f64(const molann_plan* plan);
  * codes are molann_value_and_hills_f64's (out_dim <= 8: MOLANN_E_UNSUPPORTED beyond); after them a scale that is not finite, a norm or
  * an epsilon that is not finite and > 0, a cutoff that is NaN or not > 0: MOLANN_E_DESC.  The call only enqueues on `stream` (no
  * workspace, no event): thread-safe and capturable.  Out of scope: depositing, merging or compressing kernels and the update of the
- * normalisation (between steps, on the caller's own tensors); an OPES term inside molann_value_and_bias_f64; float32; neighbour
- * lists; gradients with respect to the table or the parameters. */
+ * normalisation (between steps, on the caller's own tensors); float32; neighbour lists; gradients with respect to the table or the
+ * parameters.  An OPES term on some of a wider model's outputs, or together with walls or a table: molann_value_and_bias_opes_f64. */
 int molann_value_and_opes_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
                               const double* centers, const double* heights, int64_t n_kernels, const double* sigma, int64_t sigma_stride,
                               const double* period, double scale, double norm, double epsilon, double cutoff, double* out, double* bias,
@@ -474,6 +474,50 @@ int molann_value_and_bias_f64(molann_plan* plan, const double* x, int64_t n_fram
 
 /* 1 when molann_value_and_bias_f64 serves the plan (its rows fit the LDS of a compute unit; no cap on out_dim), 0 otherwise. */
 int molann_plan_supports_value_and_bias_f64(const molann_plan* plan);
+
+/* Values, an OPES BIAS ON CHOSEN OUTPUTS TOGETHER WITH WALLS AND A TABLE, and the gradient of their sum in ONE launch of
+ * frames_value_bias_opes_f64_kernel (ahead of time: no hipRTC): molann_value_and_bias_f64 with the kernel density of
+ * molann_value_and_opes_f64 in the place of the hills - what an OPES run with walls carries at every step, on a model of any out_dim.
+ * out[N, out_dim] = molann_value_and_vjp_f64's out, bit for bit; energies[N, 4] = (E_r, V_h, V_g, V_o): columns 0..2 mean what they mean
+ * in molann_value_and_bias_f64's energies, V_h is always exactly 0.0 (hills are no term of this call), an absent term's column exactly
+ * 0.0; grad_x[N, n_inp, 3] = d(E_r + V_o + V_g) / dx - the gradient: forces are its negative.  Everything in double.
+ *   E_r, V_g: the restraint and the table of `terms`, as molann_value_and_bias_f64 takes them (a flat-bottom restraint is a pair of
+ *        walls).  terms may be NULL: neither.  terms->n_hills_columns != 0: MOLANN_E_UNSUPPORTED - move the hills onto a table, or make
+ *        two calls.
+ *   V_o: molann_value_and_opes_f64's bias scale log(P / norm + epsilon) on the n_columns <= 8 outputs columns[0..n) - a HOST array of
+ *        distinct indices in any order, NULL for 0..n-1.  centers[n_kernels, n], heights[n_kernels], sigma ([n], sigma_stride 0, or
+ *        [n_kernels, n], sigma_stride n), period [n] or NULL: DEVICE pointers, laid out over the chosen columns in the order of the
+ *        list.  n_kernels may be 0: centers, heights and sigma are not read then, V_o = scale log(epsilon) and its share of grad_x is
+ *        exactly 0.  scale, norm, epsilon, cutoff (+inf: none) are host values and travel in the launch's arguments; a kernel is dropped
+ *        when q_h >= cutoff^2 is true.  `opes` is required.
+ * The lists may overlap each other and the restrained outputs.  An absent term's pointers are not looked at.  The cotangent of an output
+ * is the restraint's kappa d (0 without one), then the OPES derivative is added, then the table's: a fixed order, and with it, the fixed
+ * order of every sum and one store per row of grad_x, the same bits on every run, whatever n_frames.  With the OPES term alone (identity
+ * list) V_o and grad_x are molann_value_and_opes_f64's, bit for bit.  A frame that is not finite gets NaN and no other frame does, at a
+ * finite cutoff too.  Plans: molann_value_and_bias_f64's, whatever out_dim (same rows, same launch geometry).  Refusals, in this order,
+ * nothing being written: a NULL plan, opes, x, out, energies, grad_x or pointer a present term requires (the kernel table where
+ * n_kernels > 0; shape, lower and spacing of a present table): MOLANN_E_NULL; a pointer that is not 8-byte aligned: MOLANN_E_ALIGNMENT;
+ * MOLANN_E_STAGE / MOLANN_E_UNSUPPORTED as molann_value_and_bias_f64; n_columns <= 0, a negative count, a stride other than 0 or the
+ * term's width, scalars molann_value_and_opes_f64 refuses, a grid molann_value_and_grid_f64 refuses: MOLANN_E_DESC; hills columns in
+ * `terms`: MOLANN_E_UNSUPPORTED; a column outside [0, out_dim) or repeated within its list: MOLANN_E_INDEX; more than 8 OPES columns or 3
+ * grid columns: MOLANN_E_UNSUPPORTED; a NULL list longer than out_dim: MOLANN_E_INDEX.  n_frames < 0: MOLANN_E_DESC; n_frames == 0:
+ * nothing is read or launched.  The call only enqueues on `stream` (no workspace, no atomics, no event): thread-safe and capturable.
+ * Out of scope: hills and OPES in one launch; more than one OPES term; float32; depositing or compressing kernels; gradients with
+ * respect to tables or parameters. */
+typedef struct molann_opes_term_f64 {
+    /* the outputs the kernels act on: a HOST list, distinct, any order, <= 8; NULL: 0..n_columns-1 */
+    int32_t n_columns; const int32_t* columns;
+    /* the kernel table over the listed columns: DEVICE pointers */
+    const double *centers, *heights; int64_t n_kernels; const double* sigma; int64_t sigma_stride; const double* period;
+    /* host values; cutoff = +inf: none */
+    double scale, norm, epsilon, cutoff;
+} molann_opes_term_f64;
+int molann_value_and_bias_opes_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                                   const molann_bias_terms_f64* terms, const molann_opes_term_f64* opes, double* out, double* energies,
+                                   double* grad_x, molann_stream_t stream);
+
+/* 1 when molann_value_and_bias_opes_f64 serves the plan (molann_value_and_bias_f64 serves it), 0 otherwise. */
+int molann_plan_supports_value_and_bias_opes_f64(const molann_plan* plan);
 
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
@@ -563,6 +607,11 @@ double molann_selftest_grid_f64(const double* y, int d, const double* table, con
  * additions (every pointer of `terms` a HOST pointer here; center is one row): energies3 = (E_r, V_h, V_g), dy[d_out] = the cotangent.
  * Returns MOLANN_OK, or the code molann_value_and_bias_f64 gives the same terms (nothing written then) */
 int molann_selftest_bias_f64(const double* y, int d_out, const molann_bias_terms_f64* terms, double* energies3, double* dy);
+/* one frame of molann_value_and_bias_opes_f64 on the host, through the functions its kernel calls, with its column mapping and its order
+ * of additions (every pointer of `terms` and `opes` a HOST pointer here; center is one row): energies4 = (E_r, 0, V_g, V_o), dy[d_out] =
+ * the cotangent.  Returns MOLANN_OK, or the code molann_value_and_bias_opes_f64 gives the same terms (nothing written then) */
+int molann_selftest_bias_opes_f64(const double* y, int d_out, const molann_bias_terms_f64* terms, const molann_opes_term_f64* opes,
+                                  double* energies4, double* dy);
 /* the unit-cotangent local Jacobian frames_value_jac_f64_kernel combines: jac36[c][j][xyz] = d(output column c of the item) /
  * d(atom j) for the item's 4 atoms (rows past the item's width are 0); returns the width */
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* atoms_xyz, double* jac36);

@@ -118,6 +118,32 @@ def bias_terms_f64(restraint=None, hills=None, grid=None, ptr=lambda t: t.data_p
     return t, keep
 
 
+class OpesTermF64(ctypes.Structure):
+    """molann_opes_term_f64 of include/molann_hip.h: the OPES term of `molann_value_and_bias_opes_f64`."""
+    _fields_ = [("n_columns", ctypes.c_int32), ("columns", ctypes.POINTER(ctypes.c_int32)),
+                ("centers", ctypes.c_void_p), ("heights", ctypes.c_void_p), ("n_kernels", ctypes.c_int64), ("sigma", ctypes.c_void_p),
+                ("sigma_stride", ctypes.c_int64), ("period", ctypes.c_void_p),
+                ("scale", ctypes.c_double), ("norm", ctypes.c_double), ("epsilon", ctypes.c_double), ("cutoff", ctypes.c_double)]
+
+
+def opes_term_f64(opes, ptr=lambda t: t.data_ptr()):
+    """An `OpesTermF64` and the host array it points into (keep both alive for the call).  opes: (columns, centers, heights, sigma,
+    period, n_kernels, sigma_stride, scale, norm, epsilon, cutoff); tensors give their addresses through `ptr`; columns None is the
+    identity list and needs the count in its place: (None, n); cutoff None is +inf."""
+    cols, centers, heights, sigma, period, n_kernels, stride, scale, norm, epsilon, cutoff = opes
+    o, keep = OpesTermF64(), []
+    if isinstance(cols, tuple) and len(cols) == 2 and cols[0] is None:
+        o.n_columns = int(cols[1])
+    else:
+        arr = _i32_array(cols)
+        keep.append(arr)
+        o.n_columns, o.columns = len(cols), arr
+    o.centers, o.heights, o.sigma, o.period = (None if v is None else ptr(v) for v in (centers, heights, sigma, period))
+    o.n_kernels, o.sigma_stride = n_kernels, stride
+    o.scale, o.norm, o.epsilon, o.cutoff = float(scale), float(norm), float(epsilon), float("inf") if cutoff is None else float(cutoff)
+    return o, keep
+
+
 _lib = None
 
 
@@ -179,6 +205,9 @@ def lib():
             "molann_plan_supports_value_and_grid_f64": (i32, [vp]),
             "molann_value_and_bias_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(BiasTermsF64), vp, vp, vp, vp]),
             "molann_plan_supports_value_and_bias_f64": (i32, [vp]),
+            "molann_value_and_bias_opes_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(BiasTermsF64),
+                                               ctypes.POINTER(OpesTermF64), vp, vp, vp, vp]),
+            "molann_plan_supports_value_and_bias_opes_f64": (i32, [vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -199,6 +228,7 @@ def lib():
             "molann_selftest_grid_axis_f64": (None, [ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32, vp, vp, vp]),
             "molann_selftest_grid_f64": (ctypes.c_double, [vp, i32, vp, vp, vp, vp, vp, vp]),
             "molann_selftest_bias_f64": (i32, [vp, i32, ctypes.POINTER(BiasTermsF64), vp, vp]),
+            "molann_selftest_bias_opes_f64": (i32, [vp, i32, ctypes.POINTER(BiasTermsF64), ctypes.POINTER(OpesTermF64), vp, vp]),
             "molann_selftest_item_jacobian_f64": (i32, [i32, i32, vp, vp]),
             "molann_features_jvp_f32": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
             "molann_features_jvp_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp]),
@@ -588,6 +618,40 @@ class Plan(object):
                      grad_x.data_ptr())
         del keep
         return out, energies, grad_x
+
+    def supports_value_and_bias_opes_f64(self):
+        """True when `value_and_bias_opes_f64` serves this plan: `value_and_bias_f64` serves it (nothing is built)."""
+        return lib().molann_plan_supports_value_and_bias_opes_f64(self._handle) == 1
+
+    def value_and_bias_opes_f64(self, x, weights, biases, out, energies, grad_x, opes, restraint=None, grid=None):
+        """out[N, d_out], energies[N, 4] = (restraint, 0, table, OPES) and grad_x[N, n_inp, 3] = d(their sum) / d x in float64, one launch
+        of frames_value_bias_opes_f64_kernel.  `weights` / `biases` as `value_and_vjp_f64` takes them.  opes: (columns, centers, heights,
+        sigma, period, scale, norm, epsilon, cutoff) on the listed outputs (at most 8; None: the first centers.shape[1]), the tensors as
+        `value_and_opes_f64` takes them over those outputs, `cutoff` None or +inf for none; restraint, grid: None or as
+        `value_and_bias_f64` takes them.  Device tensors on x's device; columns, the four scalars, lower, spacing, periodic are host
+        values, read during the call."""
+        W, B = _layer_pointers(weights, biases)
+        d_out = out.numel() // max(x.shape[0], 1)
+        r = g = None
+        if restraint is not None:
+            center, kappa, period, flat = restraint
+            r = (center, kappa, period, flat, 0 if center.numel() == d_out and center.dim() < 2 else d_out)
+        if grid is not None:
+            cols, table, lower, spacing, periodic = grid
+            g = ((None, table.dim()) if cols is None else cols, table, table.shape, lower, spacing, periodic)
+        cols, centers, heights, sigma, period, scale, norm, epsilon, cutoff = opes
+        n_kernels = centers.shape[0]
+        width = centers.shape[1] if cols is None else len(cols)
+        term, keep_o = opes_term_f64(((None, width) if cols is None else cols, centers if n_kernels else None, heights if n_kernels else None,
+                                      sigma if n_kernels else None, period, n_kernels, width if sigma.dim() == 2 else 0, scale, norm, epsilon,
+                                      cutoff))
+        terms, keep = bias_terms_f64(r, None, g)
+        self._launch("molann_value_and_bias_opes_f64", x.data_ptr(), x.shape[0], W, B, ctypes.byref(terms), ctypes.byref(term), out.data_ptr(),
+                     energies.data_ptr(), grad_x.data_ptr())
+        del keep, keep_o
+        return out, energies, grad_x
+
+    value_and_bias_opes = value_and_bias_opes_f64
 
     def forward_train(self, x, out, features):
         """`forward_packed` that also keeps the features (for `mlp_backward` + `features_backward`)."""

@@ -924,7 +924,7 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
 # value_and_restraint / value_and_hills / value_and_grid / value_and_bias and PreprocessingANN.value_and_metric / value_and_restraint /
 # value_and_hills / value_and_grid / value_and_bias, and value_and_opes of both.  What differs
 # between them, by kind; the checks and the two ways to the kernel are written once below.
-_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID, _BIAS, _OPES = 0, 1, 2, 3, 4, 5, 6, 7
+_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID, _BIAS, _OPES, _BIAS_OPES = 0, 1, 2, 3, 4, 5, 6, 7, 8
 _HILLS_MAX_D_OUT = 8      # HILLS64_MAX_D_OUT of csrc/molann_value_f64.inc: the kernel's cotangent sums are a register array
 _JACOBIAN_ROUTE = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
 _METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
@@ -940,15 +940,24 @@ _BIAS_FEATURES_ROUTE = "use `module(x)` on an x that requires grad, form the ter
 _OPES_ROUTE = "use `model(x)`, form the kernel sum with `molann_amd.bias.opes_kernel_sum`, its logarithm and its derivative with torch, then `value_and_vjp`"
 _OPES_FEATURES_ROUTE = ("use `module(x)` on an x that requires grad, form the kernel sum with `molann_amd.bias.opes_kernel_sum` and its logarithm with "
                         "torch and take torch.autograd.grad")
+# value_and_bias with an OPES term (_BIAS_OPES, a kernel of its own): what remains where it refuses
+_BIAS_OPES_ROUTE = ("use `model(x)`, form the walls and the table on the chosen columns and the kernel sum with `molann_amd.bias.opes_kernel_sum`, "
+                    "their derivatives with torch, then `value_and_vjp`")
+_BIAS_OPES_FEATURES_ROUTE = ("use `module(x)` on an x that requires grad, form the walls, the table and the kernel sum "
+                             "(`molann_amd.bias.opes_kernel_sum`) with torch and take torch.autograd.grad")
+_HILLS_AND_OPES_ROUTE = ("`hills` and `opes` in one launch are not served: move the hills onto a table with `molann_amd.bias.add_hills_to_grid` and "
+                         "pass it as `grid`, or make two calls (`value_and_bias` with the hills, `value_and_opes` or `value_and_bias` with `opes`) "
+                         "and add their dx")
 _ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint", "value_and_hills", "value_and_grid",
-                    "value_and_bias", "value_and_opes")
+                    "value_and_bias", "value_and_opes", "value_and_bias")
 # the route that remains where the call refuses
-_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE, _BIAS_ROUTE, _OPES_ROUTE)
+_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE, _BIAS_ROUTE, _OPES_ROUTE, _BIAS_OPES_ROUTE)
 _ONE_LAUNCH_FEATURES_ROUTE = (None, None, None, _RESTRAINT_FEATURES_ROUTE, _HILLS_FEATURES_ROUTE, _GRID_FEATURES_ROUTE, _BIAS_FEATURES_ROUTE,
-                              _OPES_FEATURES_ROUTE)
-_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)", "(y, bias, dx)", "(y, energies, dx)", "(y, bias, dx)")   # what `into` holds
+                              _OPES_FEATURES_ROUTE, _BIAS_OPES_FEATURES_ROUTE)
+_ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)", "(y, bias, dx)", "(y, energies, dx)", "(y, bias, dx)",
+                    "(y, energies, dx)")   # what `into` holds
 # the dispatcher operator, in MolANN._fast_state
-_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid", "op_bias", "op_opes")
+_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid", "op_bias", "op_opes", "op_bias_opes")
 _BIAS_KINDS = (_RESTRAINT, _HILLS, _GRID)      # the calls that return (y, a scalar per frame, dx)
 
 
@@ -970,7 +979,7 @@ def _check_into(name, x, into, dtype, out_dim, second_shape, pair):
 
 def _check_into_triple(name, x, into, out_dim, kind=_RESTRAINT):
     """`into` of value_and_restraint, value_and_hills and value_and_grid, before any launch, with `_check_into`'s checks: a triple of contiguous float64 tensors on x's
-    device that hold [N, out_dim], [N] ([N, 3] for value_and_bias) and x's elements.  Returns the triple, (None, None, None) for None."""
+    device that hold [N, out_dim], [N] ([N, 3] for value_and_bias, [N, 4] with an OPES term) and x's elements.  Returns the triple, (None, None, None) for None."""
     if into is None:
         return None, None, None
     if len(into) != 3 or not all(isinstance(t, torch.Tensor) for t in into):
@@ -978,11 +987,11 @@ def _check_into_triple(name, x, into, out_dim, kind=_RESTRAINT):
     if any(t.dtype != torch.float64 for t in into):
         raise TypeError("%s: `into` must be float64 like x; got %s" % (name, ", ".join(str(t.dtype) for t in into)))
     n = x.shape[0]
-    per = 3 if kind == _BIAS else 1
+    per = 3 if kind == _BIAS else 4 if kind == _BIAS_OPES else 1
     counts = (n * out_dim, n * per, x.numel())
     if not all(t.is_contiguous() and t.numel() == c and t.device == x.device for t, c in zip(into, counts)):
         raise ValueError("%s: `into` must be contiguous {[%d, %d], %s, %s} on %s"
-                         % (name, n, out_dim, [n, 3] if kind == _BIAS else [n], list(x.shape), x.device))
+                         % (name, n, out_dim, [n, per] if per > 1 else [n], list(x.shape), x.device))
     return tuple(into)
 
 
@@ -1141,14 +1150,18 @@ def _check_grid_args(name, x, out_dim, table, lower, spacing, periodic, into, ow
     return (table.detach(), lower, spacing, periodic) + _check_into_triple(name, x, into, out_dim, _GRID)
 
 
-def _check_bias_terms(name, restraint, hills, grid):
+def _check_bias_terms(name, restraint, hills, grid, opes=None):
     """The terms of value_and_bias as they come, before anything needs a device: each None or its record of `molann_amd.bias` (whose
-    construction has checked its `columns`), and at least one of them."""
-    for what, term, cls in (("restraint", restraint, _bias.Restraint), ("hills", hills, _bias.Hills), ("grid", grid, _bias.Grid)):
+    construction has checked its `columns`), and at least one of them; `hills` and `opes` together: NotImplementedError naming the
+    routes that remain."""
+    for what, term, cls in (("restraint", restraint, _bias.Restraint), ("hills", hills, _bias.Hills), ("grid", grid, _bias.Grid),
+                            ("opes", opes, _bias.Opes)):
         if term is not None and not isinstance(term, cls):
             raise TypeError("%s: `%s` must be None or a molann_amd.bias.%s; got %s" % (name, what, cls.__name__, type(term).__name__))
-    if restraint is None and hills is None and grid is None:
+    if restraint is None and hills is None and grid is None and opes is None:
         raise ValueError("%s: at least one of `restraint`, `hills` and `grid` must be given" % name)
+    if hills is not None and opes is not None:
+        raise NotImplementedError("%s: %s" % (name, _HILLS_AND_OPES_ROUTE))
 
 
 def _bias_columns(name, what, columns, width, cap, out_dim):
@@ -1165,16 +1178,17 @@ def _bias_columns(name, what, columns, width, cap, out_dim):
     return columns
 
 
-def _hills_width(name, centers):
-    """The number of columns of a `Hills` without `columns`: centers' second dimension, or the length of its first row.  An empty
+def _hills_width(name, centers, what="hills"):
+    """The number of columns of a `Hills` (or an `Opes`, by `what`) without `columns`: centers' second dimension, or the length of its first row.  An empty
     sequence has neither: ValueError (a ``[0, d]`` tensor, or `columns`, says what is meant)."""
     if isinstance(centers, torch.Tensor) and centers.dim() == 2:
         return centers.shape[1]
     rows = len(centers) if hasattr(centers, "__len__") else 0
     if rows and hasattr(centers[0], "__len__"):
         return len(centers[0])
-    raise ValueError("%s: `hills.centers` must be [H, columns] to tell the columns the hills act on; for no hills yet pass `columns` or a "
-                     "[0, columns] tensor (got %s)" % (name, list(centers.shape) if isinstance(centers, torch.Tensor) else type(centers).__name__))
+    raise ValueError("%s: `%s.centers` must be [H, columns] to tell the columns the %s act on; for no %s yet pass `columns` or a "
+                     "[0, columns] tensor (got %s)" % (name, what, "kernels" if what == "opes" else what, "kernels" if what == "opes" else what,
+                                                       list(centers.shape) if isinstance(centers, torch.Tensor) else type(centers).__name__))
 
 
 def _check_bias_args(name, x, out_dim, restraint, hills, grid, into, owner=None):
@@ -1197,6 +1211,28 @@ def _check_bias_args(name, x, out_dim, restraint, hills, grid, into, owner=None)
     if grid is not None:
         g = (gc,) + _check_grid_args(name, x, len(gc), grid.table, grid.lower, grid.spacing, grid.periodic, None, owner=owner, unit="grid column")[:4]
     return (r, h, g) + _check_into_triple(name, x, into, out_dim, _BIAS)
+
+
+def _check_bias_opes_args(name, x, out_dim, restraint, grid, opes, into, owner=None):
+    """The checks of value_and_bias with an OPES term after the gate, as `_check_bias_args` makes them: the column lists against the
+    model, then the restraint and the table by the checks of their single calls, the OPES term by `_check_opes_args` with the term's
+    width ``len(columns)`` in place of the number of outputs (the same conversions, the same remembered `sigma` read-back, the same
+    scalar ValueErrors), then `into` with energies [N, 4].  Returns ((center, kappa, period, flat) or None, (columns, table, lower,
+    spacing, periodic) or None, (columns, centers, heights, sigma, period, scale, norm, epsilon, cutoff), y, energies, dx)."""
+    width = len(opes.columns) if opes.columns is not None else _hills_width(name, opes.centers, "opes")
+    oc = _bias_columns(name, "opes", opes.columns, width, _bias.HILLS_MAX_COLUMNS, out_dim)
+    gc = None
+    if grid is not None:
+        width = grid.table.dim() if isinstance(grid.table, torch.Tensor) and grid.columns is None else 1
+        gc = _bias_columns(name, "grid", grid.columns, width, _bias.GRID_MAX_COLUMNS, out_dim)
+    r = g = None
+    if restraint is not None:
+        r = _check_restraint_args(name, x, out_dim, restraint.center, restraint.kappa, restraint.period, restraint.flat, None, owner=owner)[:4]
+    o = (oc,) + _check_opes_args(name, x, len(oc), opes.centers, opes.heights, opes.sigma, opes.scale, opes.norm, opes.epsilon, opes.cutoff,
+                                 opes.period, None, owner=owner)[:8]
+    if grid is not None:
+        g = (gc,) + _check_grid_args(name, x, len(gc), grid.table, grid.lower, grid.spacing, grid.periodic, None, owner=owner, unit="grid column")[:4]
+    return (r, g, o) + _check_into_triple(name, x, into, out_dim, _BIAS_OPES)
 
 
 def _check_grad_out(name, x, out_dim, grad_out):
@@ -1256,6 +1292,9 @@ def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=
     elif kind == _BIAS:
         checked = _check_bias_args(name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:3], checked[3], (checked[4], checked[5]) if checked[3] is not None else None, (n, n_inp, 3)
+    elif kind == _BIAS_OPES:
+        checked = _check_bias_opes_args(name, x, out_dim, *extra, into, owner=owner)
+        return x, checked[:3], checked[3], (checked[4], checked[5]) if checked[3] is not None else None, (n, n_inp, 3)
     elif kind == _OPES:
         checked = _check_opes_args(name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:8], checked[8], (checked[9], checked[10]) if checked[8] is not None else None, (n, n_inp, 3)
@@ -1278,6 +1317,9 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
         if kind == _OPES:
             if not plan.supports_value_and_opes_f64():
                 raise NotImplementedError("value_and_opes: one frame's rows exceed the LDS of a compute unit for this model; " + _OPES_ROUTE)
+        elif kind == _BIAS_OPES:
+            if not plan.supports_value_and_bias_opes_f64():
+                raise NotImplementedError("value_and_bias: one frame's rows exceed the LDS of a compute unit for this model; " + _BIAS_OPES_ROUTE)
         elif kind in _BIAS_KINDS or kind == _BIAS:
             if not (plan.supports_value_and_restraint_f64, plan.supports_value_and_hills_f64, plan.supports_value_and_grid_f64,
                     plan.supports_value_and_bias_f64)[kind - _RESTRAINT]():
@@ -1297,8 +1339,13 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
             second = torch.empty(shape, dtype=torch.float64, device=x.device)
             if kind in _BIAS_KINDS or kind == _OPES:
                 second = (torch.empty((x.shape[0],), dtype=torch.float64, device=x.device), second)
-            if kind == _BIAS:
-                second = (torch.empty((x.shape[0], 3), dtype=torch.float64, device=x.device), second)
+            if kind == _BIAS or kind == _BIAS_OPES:
+                second = (torch.empty((x.shape[0], 3 if kind == _BIAS else 4), dtype=torch.float64, device=x.device), second)
+        if kind == _BIAS_OPES:
+            if x.shape[0] > 0:
+                plan.value_and_bias_opes_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
+                                             y, *second, extra[2], restraint=extra[0], grid=extra[1])
+            return (y,) + tuple(second)
         if kind == _BIAS:
             if x.shape[0] > 0:
                 plan.value_and_bias_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
@@ -1418,15 +1465,19 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
         No autograd graph is recorded; ``into=(feat, bias, dx)`` reuses the caller's buffers.  The same bits on every call."""
         return self._bias_on_features(_GRID, x, (table, lower, spacing, periodic), into)
 
-    def value_and_bias(self, x, restraint=None, hills=None, grid=None, into=None):
+    def value_and_bias(self, x, restraint=None, hills=None, grid=None, into=None, opes=None):
         """``(feat, energies, dx)``: `MolANN.value_and_bias` on the features themselves, float64, in ONE kernel launch
         (`molann_value_and_bias_f64`, frames_value_bias_f64_kernel, on this module's float64 feature plan; no head): a restraint on
         all features, hills on up to 8 chosen features and a table on up to 3, ``energies[f] = (E_r, V_h, V_g)`` and ``dx`` the gradient
         of their sum; forces are ``-dx``.  Position columns under walls and two raw dihedral angles under metadynamics:
         ``use_angle_value=True``, the angles' indices as ``columns`` and ``period = 2 pi``.  The terms are `molann_amd.bias.Restraint`,
         `Hills` and `Grid`, as `MolANN.value_and_bias` takes them.  No autograd graph is recorded; ``into=(feat, energies, dx)``
-        reuses the caller's buffers.  The same bits on every call."""
-        _check_bias_terms("value_and_bias", restraint, hills, grid)
+        reuses the caller's buffers.  The same bits on every call.  ``opes``: a `molann_amd.bias.Opes` in the place of ``hills``, as
+        `MolANN.value_and_bias` takes it (frames_value_bias_opes_f64_kernel, ``energies`` [N, 4] = ``(E_r, 0, V_g, V_o)``): OPES on two raw
+        dihedral angles of a module with any number of features, with walls and a periodic table next to it."""
+        _check_bias_terms("value_and_bias", restraint, hills, grid, opes)
+        if opes is not None:
+            return self._bias_on_features(_BIAS_OPES, x, (restraint, grid, opes), into)
         return self._bias_on_features(_BIAS, x, (restraint, hills, grid), into)
 
     def value_and_opes(self, x, centers, heights, sigma, scale, norm, epsilon, cutoff=None, period=None, into=None):
@@ -1587,6 +1638,10 @@ class MolANN(_PlanOwner, torch.nn.Module):
             r, h, g = extra
             return tuple(op(x, st["handle"], ref, W, B, *(r or (None,) * 4), *((list(h[0]),) + h[1:] if h else ([], None, None, None, None)),
                             *((list(g[0]),) + g[1:] if g else ([], None, [], [], [])), into))
+        if kind == _BIAS_OPES:
+            r, g, o = extra
+            return tuple(op(x, st["handle"], ref, W, B, *(r or (None,) * 4), list(o[0]), *o[1:],
+                            *((list(g[0]),) + g[1:] if g else ([], None, [], [], [])), into))
         y, second = op(x, st["handle"], ref, W, B, into) if kind == _JACOBIAN else op(x, st["handle"], ref, W, B, extra, into)
         return y, second
 
@@ -1680,9 +1735,9 @@ class MolANN(_PlanOwner, torch.nn.Module):
         ``into=(y, bias, dx)`` reuses the caller's buffers.  Every sum has a fixed order and every row of dx is stored once: the same
         bits on every call, whatever N.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at
         most 8 outputs (NotImplementedError beyond).  Out of scope: depositing, merging or compressing kernels and the update of Z
-        (between steps, on your own tensors: `molann_amd.bias.opes_kernel_sum` gives P at the kernel centres), an OPES term inside
-        `value_and_bias`, float32, a `GraphedForces` replay of this launch, neighbour lists, gradients with respect to the table or the
-        parameters."""
+        (between steps, on your own tensors: `molann_amd.bias.opes_kernel_sum` gives P at the kernel centres), float32, a
+        `GraphedForces` replay of this launch, neighbour lists, gradients with respect to the table or the parameters.  OPES on some of
+        a wider model's outputs, or together with walls or a table: `value_and_bias` with ``opes=``."""
         return self._one_launch_f64(_OPES, self._one_launch_state(x, _OPES, "float64"), x,
                                     (centers, heights, sigma, scale, norm, epsilon, cutoff, period), into)
 
@@ -1711,7 +1766,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
         a `GraphedForces` replay of this launch, gradients with respect to the table or the parameters."""
         return self._one_launch_f64(_GRID, self._one_launch_state(x, _GRID, "float64"), x, (table, lower, spacing, periodic), into)
 
-    def value_and_bias(self, x, restraint=None, hills=None, grid=None, into=None):
+    def value_and_bias(self, x, restraint=None, hills=None, grid=None, into=None, opes=None):
         """``(y, energies, dx)`` with ``y = self(x)`` [N, d_out], up to three bias terms on chosen outputs, ``energies[f] = (E_r, V_h,
         V_g)`` [N, 3], and ``dx = d(E_r + V_h + V_g) / d x`` [N, n_inp, 3] (the gradient: forces are ``-dx``), float64, in ONE kernel
         launch (`molann_value_and_bias_f64`, frames_value_bias_f64_kernel): what a production step of enhanced sampling carries -
@@ -1734,8 +1789,24 @@ class MolANN(_PlanOwner, torch.nn.Module):
         IndexError; more than 8 / 3 columns: NotImplementedError.  No autograd graph is recorded; ``into=(y, energies, dx)`` reuses
         the caller's buffers.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan.  Out of scope:
         float32, more than one term of a kind, a restraint on a list of columns (use ``kappa = 0``), a `GraphedForces` replay of this
-        launch, gradients with respect to parameters or bias tables."""
-        _check_bias_terms("value_and_bias", restraint, hills, grid)
+        launch, gradients with respect to parameters or bias tables.
+
+        ``opes``: a `molann_amd.bias.Opes` ``(centers, heights, sigma, scale, norm, epsilon, cutoff=None, period=None, columns=None)``, the
+        kernel density of `value_and_opes` on the outputs ``columns`` (distinct, any order, at most 8; None: the first
+        ``centers.shape[1]``) - an OPES run with walls (a flat-bottom ``restraint``) and, if there is one, a static table from an earlier
+        run, on a model with any number of outputs, still ONE launch (`molann_value_and_bias_opes_f64`,
+        frames_value_bias_opes_f64_kernel: a kernel of its own, `value_and_bias` without ``opes`` is what it was).  Then ``energies`` is
+        [N, 4] ``= (E_r, V_h, V_g, V_o)``: columns 0 to 2 mean what they mean without ``opes``, ``V_h`` is exactly 0.0 and ``V_o = scale
+        log(P / norm + epsilon)``; ``dx = d(E_r + V_o + V_g) / d x``, an output's cotangent being the restraint's, then the OPES
+        derivative, then the table's.  The record's arguments are checked as `value_and_opes` checks them, with ``len(columns)`` in the
+        place of d_out (conversions, the remembered ``sigma`` read-back, the scalars' ValueErrors); ``H = 0`` gives ``V_o = scale
+        log(epsilon)`` and no share of dx.  With ``opes`` alone on identity columns ``V_o`` and ``dx`` are `value_and_opes`', bit for
+        bit.  ``hills`` and ``opes`` together: NotImplementedError - move the hills onto a table with
+        `molann_amd.bias.add_hills_to_grid` and pass it as ``grid``, or make two calls.  Out of scope as well: more than one OPES term,
+        depositing or compressing kernels."""
+        _check_bias_terms("value_and_bias", restraint, hills, grid, opes)
+        if opes is not None:
+            return self._one_launch_f64(_BIAS_OPES, self._one_launch_state(x, _BIAS_OPES, "float64"), x, (restraint, grid, opes), into)
         return self._one_launch_f64(_BIAS, self._one_launch_state(x, _BIAS, "float64"), x, (restraint, hills, grid), into)
 
     def _tangent_present(self, x):
@@ -1794,7 +1865,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
                                                                     torch.ops.molann.value_and_metric_h)
                 st["op_restraint"], st["op_hills"] = torch.ops.molann.value_and_restraint_h, torch.ops.molann.value_and_hills_h
                 st["op_grid"], st["op_bias"] = torch.ops.molann.value_and_grid_h, torch.ops.molann.value_and_bias_h
-                st["op_opes"] = torch.ops.molann.value_and_opes_h
+                st["op_opes"], st["op_bias_opes"] = torch.ops.molann.value_and_opes_h, torch.ops.molann.value_and_bias_opes_h
                 from . import script
                 st["desc"] = script.make_desc(script.KIND_FORWARD, fl.input_atom_num,
                                               align_idx=al._local_align_atom_indices if al is not None else None,

@@ -7,14 +7,15 @@ has period ``n_k * spacing[k]`` (so the point after the last is the first again)
 with `add_hills_to_grid`: deposit each new hill onto the table and call `value_and_grid`, whose cost does not grow with the run.
 
 An OPES run (`MolANN.value_and_opes`) keeps its own kernel table; `opes_kernel_sum` gives the kernel density at any points - at the
-kernel centres for the normalisation Z, at a new sample for the weight of its deposit."""
+kernel centres for the normalisation Z, at a new sample for the weight of its deposit.  With walls or a table next to it, or on some
+of a wider model's outputs, the kernel table goes into `MolANN.value_and_bias` as an `Opes` record."""
 
 import collections
 import operator
 
 import torch
 
-__all__ = ["grid_points", "add_hills_to_grid", "opes_kernel_sum", "Restraint", "Hills", "Grid"]
+__all__ = ["grid_points", "add_hills_to_grid", "opes_kernel_sum", "Restraint", "Hills", "Grid", "Opes"]
 
 HILLS_MAX_COLUMNS = 8     # HILLS_MAX_D of csrc/molann_math.h
 GRID_MAX_COLUMNS = 3      # GRID_MAX_D of csrc/molann_math.h
@@ -78,6 +79,19 @@ class Grid(collections.namedtuple("Grid", "table lower spacing periodic columns"
         columns = _columns("Grid", columns, GRID_MAX_COLUMNS, "interpolate the table and its derivative on `model(x)[:, columns]` with "
                            "torch, scatter it into a cotangent, then `value_and_vjp`")
         return super().__new__(cls, table, lower, spacing, periodic, columns)
+
+
+class Opes(collections.namedtuple("Opes", "centers heights sigma scale norm epsilon cutoff period columns")):
+    """The OPES term of `MolANN.value_and_bias` on the outputs ``columns`` (distinct indices in any order, at most 8; None: the first
+    ``centers.shape[1]``): `MolANN.value_and_opes`' arguments, ``centers`` [H, len(columns)], ``sigma`` and ``period`` laid out over the
+    chosen outputs in the order of the list; ``scale``, ``norm``, ``epsilon`` Python floats, ``cutoff`` None (no cutoff) or > 0.
+    Immutable (a deposit makes a new record: the tensors are held, not copied, and a new ``norm`` costs nothing)."""
+    __slots__ = ()
+
+    def __new__(cls, centers, heights, sigma, scale, norm, epsilon, cutoff=None, period=None, columns=None):
+        columns = _columns("Opes", columns, HILLS_MAX_COLUMNS, "form the kernel sum on `model(x)[:, columns]` with `opes_kernel_sum`, its "
+                           "logarithm and its derivative with torch, scatter it into a cotangent, then `value_and_vjp`")
+        return super().__new__(cls, centers, heights, sigma, scale, norm, epsilon, cutoff, period, columns)
 
 
 def grid_points(shape, lower, spacing, device=None):

@@ -67,6 +67,7 @@ using namespace molann;
 #include "molann_dev_jac_f64.inc"
 #include "molann_dev_metric_f64.inc"
 #include "molann_dev_opes_f64.inc"
+#include "molann_dev_bias_opes_f64.inc"
 // Host code (what `make san` instruments: -fno-gpu-sanitize leaves the device code alone):
 #include "molann_host_plan.inc"
 #include "molann_host_jit.inc"

@@ -969,6 +969,133 @@ std::vector<at::Tensor> value_and_bias_h_hip(const at::Tensor& x_in, int64_t han
     return value_and_bias_impl(x_in, *desc_of(handle, "molann::value_and_bias_h"), MOLANN_BIAS_OP_ARGS);
 }
 
+// {out, energies, grad_x}: value_and_bias with an OPES term in the place of the hills - the restraint of value_and_restraint on all outputs, the
+// kernel density of value_and_opes on `opes_columns` (required, at most 8), the table of value_and_grid on `grid_columns` - energies[N, 4] =
+// (E_r, 0, V_g, V_o) and the gradient of their sum grad_x[N, n_inp, 3] in ONE launch (molann_value_and_bias_opes_f64 on the float64 Linear
+// tensors).  The restraint is absent where `kappa` is none, the table where `grid_columns` is empty.  The kernel table is laid out over
+// `opes_columns` in the order of the list; scale, norm, epsilon and cutoff (inf: none) are host values, checked here as the C entry checks
+// them.  bias_tensor and bias_columns are value_and_bias': the Python method of both operators is value_and_bias.
+std::vector<at::Tensor> value_and_bias_opes_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                                 const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                                                 const c10::optional<at::Tensor>& center_in, const c10::optional<at::Tensor>& kappa_in,
+                                                 const c10::optional<at::Tensor>& rperiod_in, const c10::optional<at::Tensor>& flat_in,
+                                                 const std::vector<int64_t>& opes_columns, const at::Tensor& centers_in, const at::Tensor& heights_in,
+                                                 const at::Tensor& sigma_in, const c10::optional<at::Tensor>& operiod_in, double scale, double norm,
+                                                 double epsilon, double cutoff, const std::vector<int64_t>& grid_columns,
+                                                 const c10::optional<at::Tensor>& table_in, const std::vector<double>& lower,
+                                                 const std::vector<double>& spacing, const c10::List<bool>& periodic_in,
+                                                 const std::vector<at::Tensor>& into) {
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_bias_opes is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_bias_opes: a forward or a features description");
+    TORCH_CHECK_VALUE(std::isfinite(scale) && std::isfinite(norm) && norm > 0.0 && std::isfinite(epsilon) && epsilon > 0.0 && cutoff > 0.0,
+                      "molann::value_and_bias_opes: `scale` must be finite, `norm` and `epsilon` finite and > 0, `cutoff` > 0 (inf: none); got ", scale,
+                      ", ", norm, ", ", epsilon, ", ", cutoff);
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    const bool has_r = kappa_in.has_value() && kappa_in->defined(), has_g = !grid_columns.empty();
+    TORCH_CHECK_VALUE(!opes_columns.empty(), "molann::value_and_bias_opes: `opes_columns` must name at least one output");
+    const std::vector<int32_t> oc = bias_columns("opes_columns", opes_columns, 8, cols), gc = bias_columns("grid_columns", grid_columns, 3, cols);
+    const int64_t dop = (int64_t)oc.size(), dg = (int64_t)gc.size();
+    molann_bias_terms_f64 t;
+    molann_opes_term_f64 o;
+    memset(&t, 0, sizeof(t));
+    memset(&o, 0, sizeof(o));
+    at::Tensor center, kappa, rperiod, flat, table;
+    if (has_r) {
+        center = bias_tensor("center", center_in, x, true); kappa = bias_tensor("kappa", kappa_in, x, true);
+        rperiod = bias_tensor("restraint_period", rperiod_in, x, false); flat = bias_tensor("flat", flat_in, x, false);
+        const bool per_frame = center.dim() == 2 && center.size(0) == n && center.size(1) == cols;
+        TORCH_CHECK_VALUE(per_frame || (center.dim() == 1 && center.size(0) == cols), "molann::value_and_bias_opes: `center` must be [", cols,
+                          "] or [N, out_dim]");
+        TORCH_CHECK_VALUE(kappa.dim() == 1 && kappa.size(0) == cols && (!rperiod.defined() || (rperiod.dim() == 1 && rperiod.size(0) == cols)) &&
+                              (!flat.defined() || (flat.dim() == 1 && flat.size(0) == cols)),
+                          "molann::value_and_bias_opes: `kappa`, `restraint_period` and `flat` must be [", cols, "]");
+        t.center = center.data_ptr<double>(); t.center_stride = per_frame ? cols : 0; t.kappa = kappa.data_ptr<double>();
+        t.restraint_period = rperiod.defined() ? rperiod.data_ptr<double>() : nullptr;
+        t.flat = flat.defined() ? flat.data_ptr<double>() : nullptr;
+    }
+    const at::Tensor centers = opes_table("centers", centers_in, x, centers_in.dim() == 2 && centers_in.size(1) == dop, "[H, opes columns]");
+    const int64_t n_kernels = centers.size(0);
+    const at::Tensor heights = opes_table("heights", heights_in, x, heights_in.dim() == 1 && heights_in.size(0) == n_kernels, "[H]");
+    const bool per_kernel = sigma_in.dim() == 2 && sigma_in.size(0) == n_kernels && sigma_in.size(1) == dop;
+    const at::Tensor sigma = opes_table("sigma", sigma_in, x, per_kernel || (sigma_in.dim() == 1 && sigma_in.size(0) == dop),
+                                        "[opes columns] or [H, opes columns]");
+    at::Tensor operiod;
+    if (operiod_in.has_value() && operiod_in->defined())
+        operiod = opes_table("period", *operiod_in, x, operiod_in->dim() == 1 && operiod_in->size(0) == dop, "[opes columns]");
+    o.n_columns = (int32_t)dop; o.columns = oc.data(); o.n_kernels = n_kernels;
+    o.centers = n_kernels > 0 ? centers.data_ptr<double>() : nullptr; o.heights = n_kernels > 0 ? heights.data_ptr<double>() : nullptr;
+    o.sigma = n_kernels > 0 ? sigma.data_ptr<double>() : nullptr; o.sigma_stride = per_kernel ? dop : 0;
+    o.period = operiod.defined() ? operiod.data_ptr<double>() : nullptr;
+    o.scale = scale; o.norm = norm; o.epsilon = epsilon; o.cutoff = cutoff;
+    int64_t shape[3] = {4, 4, 4};
+    int32_t periodic[3] = {0, 0, 0};
+    if (has_g) {
+        table = bias_tensor("table", table_in, x, true);
+        TORCH_CHECK_VALUE(table.dim() == dg && table_in->is_contiguous(), "molann::value_and_bias_opes: `table` must be contiguous with one dimension per "
+                          "grid column (", dg, ")");
+        TORCH_CHECK_VALUE((int64_t)lower.size() == dg && (int64_t)spacing.size() == dg && (periodic_in.size() == 0 || (int64_t)periodic_in.size() == dg),
+                          "molann::value_and_bias_opes: `lower`, `spacing` and `periodic` must hold one value per grid column (", dg, ")");
+        for (int64_t k = 0; k < dg; ++k) {
+            shape[k] = table.size(k);
+            TORCH_CHECK_VALUE(shape[k] >= 4, "molann::value_and_bias_opes: every dimension of `table` must have at least 4 points (got ", shape[k], ")");
+            TORCH_CHECK_VALUE(std::isfinite(spacing[k]) && spacing[k] > 0.0 && std::isfinite(lower[k]),
+                              "molann::value_and_bias_opes: `spacing` must be finite and > 0 and `lower` finite");
+            periodic[k] = periodic_in.size() > 0 && periodic_in.get(k) ? 1 : 0;
+        }
+        TORCH_CHECK_VALUE(table.numel() < (int64_t(1) << 31), "molann::value_and_bias_opes: `table` must hold fewer than 2^31 points");
+        t.n_grid_columns = (int32_t)dg; t.grid_columns = gc.data(); t.table = table.data_ptr<double>();
+        t.shape = shape; t.lower = lower.data(); t.spacing = spacing.data(); t.periodic = periodic;
+    }
+    TORCH_CHECK(into.empty() || into.size() == 3, "molann::value_and_bias_opes: `into` must be a triple of tensors (out, energies, grad_x)");
+    at::Tensor out, energies, gx;
+    if (into.empty()) {
+        out = at::empty({n, cols}, x.options()); energies = at::empty({n, 4}, x.options()); gx = at::empty_like(x);
+    } else {
+        out = into[0]; energies = into[1]; gx = into[2];
+        const int64_t counts[3] = {n * cols, 4 * n, x.numel()};
+        for (int i = 0; i < 3; ++i) {
+            TORCH_CHECK_TYPE(into[i].scalar_type() == at::kDouble, "molann::value_and_bias_opes: `into` must be float64 like x");
+            TORCH_CHECK_VALUE(into[i].is_contiguous() && into[i].numel() == counts[i] && into[i].device() == x.device(),
+                              "molann::value_and_bias_opes: `into` must be contiguous {[N, out_dim], [N, 4], [N, n_inp, 3]} on x's device");
+        }
+    }
+    F64Linears lin;
+    f64_linears("molann::value_and_bias_opes", *e, x, weights, biases, lin, ": call .double()");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_bias_opes_f64(e->plan) == 1,
+                                "molann::value_and_bias_opes: one frame's rows exceed the LDS of a compute unit for this model; use run, form the "
+                                "terms on the chosen columns with torch, then value_and_vjp");
+    if (n == 0) return {out, energies, gx};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_bias_opes_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), &t, &o, out.data_ptr<double>(),
+                                         energies.data_ptr<double>(), gx.data_ptr<double>(), stream),
+          "molann_value_and_bias_opes_f64");
+    return {out, energies, gx};
+}
+#define MOLANN_BIAS_OPES_OP_PARAMS                                                                                                                   \
+    const at::Tensor &ref_x, std::vector<at::Tensor> weights, std::vector<at::Tensor> biases, const c10::optional<at::Tensor>&center,                \
+        const c10::optional<at::Tensor>&kappa, const c10::optional<at::Tensor>&rperiod, const c10::optional<at::Tensor>&flat,                        \
+        std::vector<int64_t> opes_columns, const at::Tensor &centers, const at::Tensor &heights, const at::Tensor &sigma,                            \
+        const c10::optional<at::Tensor>&operiod, double scale, double norm, double epsilon, double cutoff, std::vector<int64_t> grid_columns,        \
+        const c10::optional<at::Tensor>&table, std::vector<double> lower, std::vector<double> spacing, c10::List<bool> periodic,                     \
+        std::vector<at::Tensor> into
+#define MOLANN_BIAS_OPES_OP_ARGS                                                                                                                     \
+    ref_x, weights, biases, center, kappa, rperiod, flat, opes_columns, centers, heights, sigma, operiod, scale, norm, epsilon, cutoff, grid_columns, \
+        table, lower, spacing, periodic, into
+std::vector<at::Tensor> value_and_bias_opes_hip(const at::Tensor& x_in, std::vector<int64_t> desc, MOLANN_BIAS_OPES_OP_PARAMS) {
+    return value_and_bias_opes_impl(x_in, desc, MOLANN_BIAS_OPES_OP_ARGS);
+}
+std::vector<at::Tensor> value_and_bias_opes_h_hip(const at::Tensor& x_in, int64_t handle, MOLANN_BIAS_OPES_OP_PARAMS) {
+    return value_and_bias_opes_impl(x_in, *desc_of(handle, "molann::value_and_bias_opes_h"), MOLANN_BIAS_OPES_OP_ARGS);
+}
+
 // The fused forward that also keeps the features: {out, features} - or {out, empty} where the plan has no such twin of its
 // kernel (molann_plan_backward_kind != 1 ... != 2 plans recompute in molann_backward_f32).  float32 fused plans.
 std::vector<at::Tensor> run_train_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -1614,6 +1741,12 @@ TORCH_LIBRARY(molann, m) {
     m.def("value_and_bias(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, Tensor? restraint_period, "
           "Tensor? flat, int[] hills_columns, Tensor? centers, Tensor? heights, Tensor? sigma, Tensor? hills_period, int[] grid_columns, Tensor? table, "
           "float[] lower, float[] spacing, bool[] periodic, Tensor[] into) -> Tensor[]");
+    m.def("value_and_bias_opes_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, Tensor? restraint_period, "
+          "Tensor? flat, int[] opes_columns, Tensor centers, Tensor heights, Tensor sigma, Tensor? opes_period, float scale, float norm, float epsilon, "
+          "float cutoff, int[] grid_columns, Tensor? table, float[] lower, float[] spacing, bool[] periodic, Tensor[] into) -> Tensor[]");
+    m.def("value_and_bias_opes(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, Tensor? restraint_period, "
+          "Tensor? flat, int[] opes_columns, Tensor centers, Tensor heights, Tensor sigma, Tensor? opes_period, float scale, float norm, float epsilon, "
+          "float cutoff, int[] grid_columns, Tensor? table, float[] lower, float[] spacing, bool[] periodic, Tensor[] into) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
     m.def("run_head(Tensor feat, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases) -> Tensor", run_head);
@@ -1648,6 +1781,8 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_grid_h", value_and_grid_h_hip);
     m.impl("value_and_bias", value_and_bias_hip);
     m.impl("value_and_bias_h", value_and_bias_h_hip);
+    m.impl("value_and_bias_opes", value_and_bias_opes_hip);
+    m.impl("value_and_bias_opes_h", value_and_bias_opes_h_hip);
 }
 
 TORCH_LIBRARY_IMPL(molann, Autograd, m) { m.impl("run", run_autograd); }

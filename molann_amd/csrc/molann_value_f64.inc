@@ -4,9 +4,10 @@
 // molann_value_and_metric_f64 (frames_value_metric_f64_kernel, molann_dev_metric_f64.inc), molann_value_and_restraint_f64
 // (frames_value_restraint_f64_kernel, molann_dev_restraint_f64.inc), molann_value_and_hills_f64 (frames_value_hills_f64_kernel,
 // molann_dev_hills_f64.inc), molann_value_and_grid_f64 (frames_value_grid_f64_kernel, molann_dev_grid_f64.inc),
-// molann_value_and_bias_f64 (frames_value_bias_f64_kernel, molann_dev_bias_f64.inc) and molann_value_and_opes_f64
-// (frames_value_opes_f64_kernel, molann_dev_opes_f64.inc).  One argument front end, one launch and one dispatch over the lane group serve
-// the eight; an entry names its kernel, its pointers and its rows.
+// molann_value_and_bias_f64 (frames_value_bias_f64_kernel, molann_dev_bias_f64.inc), molann_value_and_opes_f64
+// (frames_value_opes_f64_kernel, molann_dev_opes_f64.inc) and molann_value_and_bias_opes_f64 (frames_value_bias_opes_f64_kernel,
+// molann_dev_bias_opes_f64.inc).  One argument front end, one launch and one dispatch over the lane group serve the nine; an entry names
+// its kernel, its pointers and its rows.
 namespace {
 
 constexpr size_t VJP64_LDS_DEFAULT = 65536;    // dynamic LDS a launch may ask for as it is
@@ -94,6 +95,7 @@ inline void f64_entry_rows(const molann_plan* p, HillsF64Args& a) { restraint64_
 inline void f64_entry_rows(const molann_plan* p, GridF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, BiasF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, OpesF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }   // the hills' rows, geometry and cap: F64_HILLS
+inline void f64_entry_rows(const molann_plan* p, BiasOpesF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }   // the bias' rows and geometry: F64_BIAS
 
 // geometry for this entry: the forces' rows, the restraint's (the hills' and the grid's too), the bias' or the Jacobian's, and the
 // metric's, the hills' and the grid's caps on the outputs
@@ -118,7 +120,7 @@ struct F64Call {    // what a launch takes besides the caller's pointers
     F64Mlp m;
 };
 
-// The argument front end of the seven entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
+// The argument front end of the entries, in this order: plan, n (MOLANN_OK at n == 0: the caller returns), the pointers that
 // must be there (`required`), their and the `optional` ones' 8-byte alignment (a null optional pointer passes), items, the head's
 // tensors layer by layer, geometry.  Nothing is dereferenced but W and b.
 template <class Args>
@@ -440,6 +442,50 @@ int molann_value_and_bias_f64(molann_plan* p, const double* x, int64_t n, const 
                             has_g ? t->table : none, out, energies, grad_x);
 }
 
+int molann_plan_supports_value_and_bias_opes_f64(const molann_plan* p) { return molann_plan_supports_value_and_bias_f64(p); }
+
+int molann_value_and_bias_opes_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b,
+                                   const molann_bias_terms_f64* t, const molann_opes_term_f64* o, double* out, double* energies, double* grad_x,
+                                   molann_stream_t stream) {
+    if (p && !o) return MOLANN_E_NULL;
+    // the host arrays of a present table are required pointers, as molann_value_and_bias_f64 has them
+    if (p && n > 0 && t && t->n_grid_columns > 0 && (!t->shape || !t->lower || !t->spacing)) return MOLANN_E_NULL;
+    F64Call<BiasOpesF64Args> c;
+    // An absent restraint or table has none of its pointers looked at (x stands in for them below); the kernel table is required where it
+    // has rows, as molann_value_and_opes_f64 has it.  The hills' pointers of `t` are never looked at: hills are refused below.
+    const bool has_r = t && t->kappa, has_g = t && t->n_grid_columns > 0, rows = o && o->n_kernels > 0;
+    const int e = f64_entry_arguments(p, F64_BIAS, n,
+                                      {x, out, energies, grad_x, has_r ? t->center : x, rows ? o->centers : x, rows ? o->heights : x,
+                                       rows ? o->sigma : x, has_g ? t->table : x},
+                                      {has_r ? t->restraint_period : nullptr, has_r ? t->flat : nullptr, o ? o->period : nullptr,
+                                       o && !rows ? o->centers : nullptr, o && !rows ? o->heights : nullptr, o && !rows ? o->sigma : nullptr},
+                                      W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    BiasOpesF64Args& a = c.a;
+    if (o->n_columns <= 0 || o->n_kernels < 0 || (t && t->n_grid_columns < 0)) return MOLANN_E_DESC;
+    if (has_r && t->center_stride != 0 && t->center_stride != a.d_out) return MOLANN_E_DESC;
+    if (o->sigma_stride != 0 && o->sigma_stride != o->n_columns) return MOLANN_E_DESC;
+    if (!opes_scalars_f64(o->scale, o->norm, o->epsilon, o->cutoff)) return MOLANN_E_DESC;
+    if (!grid_geometry_f64(has_g ? t->n_grid_columns : 0, has_g ? t->shape : nullptr, has_g ? t->lower : nullptr, has_g ? t->spacing : nullptr,
+                           has_g ? t->periodic : nullptr, a.n, a.lower, a.h, a.periodic))
+        return MOLANN_E_DESC;
+    if (t && t->n_hills_columns != 0) return MOLANN_E_UNSUPPORTED;   // hills and OPES in one launch: out of scope
+    int rc = bias_columns_f64(o->n_columns, o->columns, HILLS_MAX_D, a.d_out, a.oc);
+    if (rc == MOLANN_OK) rc = bias_columns_f64(has_g ? t->n_grid_columns : 0, has_g ? t->grid_columns : nullptr, GRID_MAX_D, a.d_out, a.gc);
+    if (rc != MOLANN_OK) return rc;
+    a.has_restraint = has_r ? 1 : 0;
+    a.n_oc = o->n_columns; a.n_gc = has_g ? t->n_grid_columns : 0;
+    a.center_stride = has_r ? (long)t->center_stride : 0;
+    a.n_kernels = (long)o->n_kernels;
+    a.sigma_stride = (long)o->sigma_stride;
+    a.scale = o->scale; a.norm = o->norm; a.epsilon = o->epsilon; a.cutoff = o->cutoff;
+    const double* none = nullptr;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_bias_opes_f64_kernel, c.g.G), "frames_value_bias_opes_f64_kernel", "bias + opes", p, c, stream,
+                            x, has_r ? t->center : none, has_r ? t->kappa : none, has_r ? t->restraint_period : none, has_r ? t->flat : none,
+                            rows ? o->centers : none, rows ? o->heights : none, rows ? o->sigma : none, o->period, has_g ? t->table : none, out,
+                            energies, grad_x);
+}
+
 double molann_selftest_act_derivative_f64(int act, double z) { return act_derivative_f64(act, z); }
 
 double molann_selftest_restraint_f64(double y, double z, double kappa, double period, double flat, double* dy) {
@@ -509,6 +555,45 @@ int molann_selftest_bias_f64(const double* y, int d_out, const molann_bias_terms
     for (int j = 0; j < t->n_hills_columns; ++j) dy[hc[j]] += dh[j];
     for (int j = 0; j < t->n_grid_columns; ++j) dy[gc[j]] += dg[j];
     energies[0] = e; energies[1] = vh; energies[2] = vg;
+    return MOLANN_OK;
+}
+
+int molann_selftest_bias_opes_f64(const double* y, int d_out, const molann_bias_terms_f64* t, const molann_opes_term_f64* o, double* energies, double* dy) {
+    if (!y || !o || !energies || !dy) return MOLANN_E_NULL;
+    const bool has_r = t && t->kappa, has_g = t && t->n_grid_columns > 0;
+    if ((has_r && !t->center) || (o->n_kernels > 0 && (!o->centers || !o->heights || !o->sigma)) ||
+        (has_g && (!t->table || !t->shape || !t->lower || !t->spacing)))
+        return MOLANN_E_NULL;
+    if (d_out < 1 || o->n_columns <= 0 || o->n_kernels < 0 || (t && t->n_grid_columns < 0)) return MOLANN_E_DESC;
+    if (o->sigma_stride != 0 && o->sigma_stride != o->n_columns) return MOLANN_E_DESC;
+    if (!opes_scalars_f64(o->scale, o->norm, o->epsilon, o->cutoff)) return MOLANN_E_DESC;
+    int oc[HILLS_MAX_D], gc[GRID_MAX_D], per[GRID_MAX_D];
+    long gn[GRID_MAX_D];
+    double lo[GRID_MAX_D], gh[GRID_MAX_D];
+    if (!grid_geometry_f64(has_g ? t->n_grid_columns : 0, has_g ? t->shape : nullptr, has_g ? t->lower : nullptr, has_g ? t->spacing : nullptr,
+                           has_g ? t->periodic : nullptr, gn, lo, gh, per))
+        return MOLANN_E_DESC;
+    if (t && t->n_hills_columns != 0) return MOLANN_E_UNSUPPORTED;
+    int rc = bias_columns_f64(o->n_columns, o->columns, HILLS_MAX_D, d_out, oc);
+    if (rc == MOLANN_OK) rc = bias_columns_f64(has_g ? t->n_grid_columns : 0, has_g ? t->grid_columns : nullptr, GRID_MAX_D, d_out, gc);
+    if (rc != MOLANN_OK) return rc;
+    const int n_gc = has_g ? t->n_grid_columns : 0;
+    double ysel[BIAS_SEL] = {}, dvo[HILLS_MAX_D] = {}, dg[GRID_MAX_D] = {};
+    for (int j = 0; j < o->n_columns; ++j) ysel[j] = y[oc[j]];
+    for (int j = 0; j < n_gc; ++j) ysel[HILLS_MAX_D + j] = y[gc[j]];
+    double e = 0., vg = 0.;
+    for (int k = 0; k < d_out; ++k) {
+        dy[k] = 0.;
+        if (has_r)
+            e += restraint_term_f64(y[k], t->center[k], t->kappa[k], t->restraint_period ? t->restraint_period[k] : 0.0, t->flat ? t->flat[k] : 0.0,
+                                    dy[k]);
+    }
+    const double vo = host_opes_f64(ysel, o->n_columns, o->centers, o->heights, o->n_kernels, o->sigma, o->sigma_stride, o->period, o->scale, o->norm,
+                                    o->epsilon, o->cutoff, dvo);
+    if (has_g) vg = host_grid_f64(ysel + HILLS_MAX_D, n_gc, t->table, t->shape, t->lower, t->spacing, t->periodic, dg);
+    for (int j = 0; j < o->n_columns; ++j) dy[oc[j]] += dvo[j];
+    for (int j = 0; j < n_gc; ++j) dy[gc[j]] += dg[j];
+    energies[0] = e; energies[1] = 0.; energies[2] = vg; energies[3] = vo;
     return MOLANN_OK;
 }
 
