@@ -392,9 +392,10 @@ int molann_plan_supports_value_and_hills_f64(const molann_plan* plan);
  * of grad_x is stored once: no atomics, the same bits on every run, whatever n_frames.  Plans, argument checks, their order and their
  * codes are molann_value_and_hills_f64's (out_dim <= 8: MOLANN_E_UNSUPPORTED beyond); after them a scale that is not finite, a norm or
  * an epsilon that is not finite and > 0, a cutoff that is NaN or not > 0: MOLANN_E_DESC.  The call only enqueues on `stream` (no
- * workspace, no event): thread-safe and capturable.  Out of scope: depositing, merging or compressing kernels and the update of the
- * normalisation (between steps, on the caller's own tensors); float32; neighbour lists; gradients with respect to the table or the
- * parameters.  An OPES term on some of a wider model's outputs, or together with walls or a table: molann_value_and_bias_opes_f64. */
+ * workspace, no event): thread-safe and capturable.  Depositing, merging and compressing kernels and the sum the normalisation is
+ * formed from: molann_opes_deposit_f64, between steps, on the same table.  Out of scope: float32; neighbour lists; gradients with
+ * respect to the table or the parameters.  An OPES term on some of a wider model's outputs, or together with walls or a table:
+ * molann_value_and_bias_opes_f64. */
 int molann_value_and_opes_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
                               const double* centers, const double* heights, int64_t n_kernels, const double* sigma, int64_t sigma_stride,
                               const double* period, double scale, double norm, double epsilon, double cutoff, double* out, double* bias,
@@ -519,6 +520,46 @@ int molann_value_and_bias_opes_f64(molann_plan* plan, const double* x, int64_t n
 /* 1 when molann_value_and_bias_opes_f64 serves the plan (molann_value_and_bias_f64 serves it), 0 otherwise. */
 int molann_plan_supports_value_and_bias_opes_f64(const molann_plan* plan);
 
+/* The deposit step of an OPES run in ONE launch of opes_deposit_f64_kernel (one block of 256 threads, ahead of time: no hipRTC, no plan):
+ * n_new new kernels (new_centers[n_new, d], new_sigma[n_new, d], new_heights[n_new]) are compressed, in order, into a table in
+ * caller-owned device memory, in place - centers[capacity, d], sigma[capacity, d] (a row per kernel: sigma_stride = d for
+ * molann_value_and_opes_f64) and heights[capacity], 1 <= d <= 8, period[d] or NULL as the OPES entries take it - and
+ *   state[0] = n, the live kernels (an exact integer in a double; rows >= n are dead storage, rows >= capacity are never touched),
+ *   state[1] = S = sum_{i<n} sum_{j<n} heights_j K_j(centers_i), the sum OPES normalises with (the caller's Z = S / (n kde_norm)),
+ *   state[2] = the merges performed so far,     state[3] = the new kernels refused so far
+ * are updated.  K_j is molann_value_and_opes_f64's kernel with the cutoff given here.  The launch reads n and S on the device and stores
+ * them at its end: the host needs neither to enqueue, so deposits queue back to back and the new kernels may come from torch
+ * arithmetic on a bias kernel's outputs with no synchronisation.  Per new kernel a:
+ *   1. a value that is not finite, a width or a height that is not > 0: refused += 1 and nothing else changes;
+ *   2. where threshold > 0 and n > 0, the live kernel t with the smallest q = sum_k (wrap(c_ak - c_tk) / sigma_tk)^2 (the smallest slot
+ *      on a tie) takes a when q < threshold^2: h' = h_t + h_a, delta = wrap(c_a - c_t), c' = c_t + (h_a / h') delta,
+ *      sigma'^2 = (h_t sigma_t^2 + h_a sigma_a^2) / h' + (h_t h_a / h'^2) delta^2, merges += 1, the merged kernel stays in slot t;
+ *   3. the search is repeated from the merged kernel, its own slot left out: while a kernel t2 lies within the threshold the merged
+ *      kernel merges into t2 by the same formulas, the last live kernel moves into the slot it leaves and n -= 1;
+ *   4. otherwise a is appended at slot n while n < capacity, and refused += 1 when the table is full.
+ * S follows by removing and adding whole kernels (for e against the live set R without it: sum_{i in R} [h_e K_e(c_i) + h_i K_i(c_e)] +
+ * h_e (1 - exp(-cutoff^2 / 2))), every sum in a fixed order with no atomics: the same bits on every run, and two queued deposits give
+ * the bits of one deposit of the concatenated kernels.  threshold = 0 only appends.  Refusals, in this order, with nothing enqueued: a
+ * NULL table, state or new pointer where n_new > 0: MOLANN_E_NULL; a pointer that is not 8-byte aligned: MOLANN_E_ALIGNMENT; d outside
+ * 1..8, capacity < 1, n_new < 0, a threshold that is not finite or < 0, a cutoff that is NaN or not > 0 (+inf: none): MOLANN_E_DESC.
+ * n_new == 0: MOLANN_OK, nothing launched.  The call only enqueues on `stream` (no workspace, no event): thread-safe on distinct tables
+ * and capturable.  Out of scope: kde_norm, neff, the bandwidth rescaling and Z from S (the caller's scalars); more than one block;
+ * neighbour lists; float32. */
+int molann_opes_deposit_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
+                            const double* new_centers, const double* new_sigma, const double* new_heights, int64_t n_new, double threshold,
+                            double cutoff, molann_stream_t stream);
+
+/* The kernel density of an OPES table at arbitrary points in ONE launch of opes_kernel_sum_f64_kernel (no plan): P[m] = sum_h heights[h]
+ * K_h(points[m]) for points[n_points, d] and, where dP is not NULL, dP[n_points, d] = dP / dpoints - molann_value_and_opes_f64's P and
+ * its walk, before the logarithm.  centers, heights, n_kernels, sigma, sigma_stride (0 or d), period and cutoff as that entry takes
+ * them; n_kernels == 0: P = 0, dP = 0, no table pointer read.  The sum over a table's own centres is the S of molann_opes_deposit_f64
+ * from scratch.  The same bits on every run.  Refusals: a negative count: MOLANN_E_DESC (n_points == 0: MOLANN_OK); a NULL points, P or
+ * table pointer where n_kernels > 0: MOLANN_E_NULL; 8-byte alignment: MOLANN_E_ALIGNMENT; d outside 1..8: MOLANN_E_UNSUPPORTED; a
+ * sigma_stride that is neither 0 nor d, a cutoff that is NaN or not > 0: MOLANN_E_DESC. */
+int molann_opes_kernel_sum_f64(const double* points, int64_t n_points, int32_t d, const double* centers, const double* heights, int64_t n_kernels,
+                               const double* sigma, int64_t sigma_stride, const double* period, double cutoff, double* P, double* dP,
+                               molann_stream_t stream);
+
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
  * is fused into the lane kernel, and large-frame plans with a head within the fused MLP's limits (the features are written
@@ -594,6 +635,11 @@ double molann_selftest_hills_f64(const double* y, int d, const double* centers, 
 double molann_selftest_opes_f64(const double* y, int d, const double* centers, const double* heights, int64_t n_kernels, const double* sigma,
                                 int64_t sigma_stride, const double* period, double scale, double norm, double epsilon, double cutoff,
                                 double* dy);
+/* molann_opes_deposit_f64 on the host: the same arguments as HOST pointers, the same steps through the functions its kernel calls, the
+ * same refusals and the device's order of every sum */
+int molann_selftest_opes_deposit_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period,
+                                     double* state, const double* new_centers, const double* new_sigma, const double* new_heights, int64_t n_new,
+                                     double threshold, double cutoff);
 /* one axis' step of molann_value_and_grid_f64 on the host, through the function its kernel calls: the four table indices, the four
  * weights and the four derivative weights (s w' / spacing) for output value y on an axis of n points; any of the three may be NULL */
 void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]);

@@ -208,6 +208,8 @@ def lib():
             "molann_value_and_bias_opes_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(BiasTermsF64),
                                                ctypes.POINTER(OpesTermF64), vp, vp, vp, vp]),
             "molann_plan_supports_value_and_bias_opes_f64": (i32, [vp]),
+            "molann_opes_deposit_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, ctypes.c_double, ctypes.c_double, vp]),
+            "molann_opes_kernel_sum_f64": (i32, [vp, i64, i32, vp, vp, i64, vp, i64, vp, ctypes.c_double, vp, vp, vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -225,6 +227,7 @@ def lib():
             "molann_selftest_restraint_f64": (ctypes.c_double, [ctypes.c_double] * 5 + [ctypes.POINTER(ctypes.c_double)]),
             "molann_selftest_hills_f64": (ctypes.c_double, [vp, i32, vp, vp, i64, vp, i64, vp, vp]),
             "molann_selftest_opes_f64": (ctypes.c_double, [vp, i32, vp, vp, i64, vp, i64, vp] + [ctypes.c_double] * 4 + [vp]),
+            "molann_selftest_opes_deposit_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, ctypes.c_double, ctypes.c_double]),
             "molann_selftest_grid_axis_f64": (None, [ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32, vp, vp, vp]),
             "molann_selftest_grid_f64": (ctypes.c_double, [vp, i32, vp, vp, vp, vp, vp, vp]),
             "molann_selftest_bias_f64": (i32, [vp, i32, ctypes.POINTER(BiasTermsF64), vp, vp]),
@@ -681,6 +684,35 @@ class Plan(object):
         buf = ctypes.create_string_buffer(256)
         lib().molann_plan_last_launch_info(self._handle, buf, 256)
         return buf.value.decode()
+
+
+def _address(t):
+    return None if t is None else t.data_ptr()
+
+
+def opes_deposit_f64(centers, sigma, heights, state, period, new_centers, new_sigma, new_heights, threshold, cutoff=None):
+    """`molann_opes_deposit_f64` on torch's current stream: the new kernels (`new_centers` [W, d], `new_sigma` [W, d], `new_heights` [W])
+    are compressed into the table `centers` [cap, d], `sigma` [cap, d], `heights` [cap] in place and `state` [4] = (n, S, merges, refused)
+    is updated, in one launch; nothing is read back.  Contiguous float64 tensors on one device (`period`: [d] or None); `cutoff` None
+    is +inf.  The tensors' shapes are the caller's to check (`molann_amd.bias.OpesTable` does)."""
+    code = lib().molann_opes_deposit_f64(centers.data_ptr(), sigma.data_ptr(), heights.data_ptr(), centers.shape[0], centers.shape[1],
+                                         _address(period), state.data_ptr(), new_centers.data_ptr(), new_sigma.data_ptr(),
+                                         new_heights.data_ptr(), new_centers.shape[0], float(threshold),
+                                         float("inf") if cutoff is None else float(cutoff), torch.cuda.current_stream().cuda_stream)
+    _check(code, "molann_opes_deposit_f64")
+
+
+def opes_kernel_sum_f64(points, centers, heights, sigma, period, cutoff, P, dP=None):
+    """`molann_opes_kernel_sum_f64` on torch's current stream: P[M] (and dP[M, d] where given) of `points` [M, d] under the table
+    `centers` [H, d], `heights` [H], `sigma` [d] or [H, d]; one launch.  Contiguous float64 tensors on one device; `cutoff` None is
+    +inf.  Returns P, or (P, dP)."""
+    n_kernels, d = centers.shape[0], points.shape[1]
+    code = lib().molann_opes_kernel_sum_f64(points.data_ptr(), points.shape[0], d, centers.data_ptr() if n_kernels else None,
+                                            heights.data_ptr() if n_kernels else None, n_kernels, sigma.data_ptr() if n_kernels else None,
+                                            d if sigma.dim() == 2 else 0, _address(period), float("inf") if cutoff is None else float(cutoff),
+                                            P.data_ptr(), _address(dP), torch.cuda.current_stream().cuda_stream)
+    _check(code, "molann_opes_kernel_sum_f64")
+    return P if dP is None else (P, dP)
 
 
 def workload_desc(w):

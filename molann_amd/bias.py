@@ -6,16 +6,19 @@ has period ``n_k * spacing[k]`` (so the point after the last is the first again)
 ``[lower[k], lower[k] + (n_k - 1) * spacing[k]]``.  A metadynamics run that starts with `MolANN.value_and_hills` moves to the table
 with `add_hills_to_grid`: deposit each new hill onto the table and call `value_and_grid`, whose cost does not grow with the run.
 
-An OPES run (`MolANN.value_and_opes`) keeps its own kernel table; `opes_kernel_sum` gives the kernel density at any points - at the
-kernel centres for the normalisation Z, at a new sample for the weight of its deposit.  With walls or a table next to it, or on some
-of a wider model's outputs, the kernel table goes into `MolANN.value_and_bias` as an `Opes` record."""
+An OPES run (`MolANN.value_and_opes`) keeps its kernel table on the device in an `OpesTable`: `deposit` compresses new kernels into it and
+keeps the sum its normalisation Z is formed from, in one launch and with no read-back; `kernel_sum` gives the kernel density at any
+points; `record` hands the live rows to `value_and_opes` / `value_and_bias` as an `Opes` record.  `opes_kernel_sum` is the same density
+in plain torch, differentiable by autograd.  With walls or a table next to it, or on some of a wider model's outputs, the kernel table
+goes into `MolANN.value_and_bias` as an `Opes` record."""
 
 import collections
+import math
 import operator
 
 import torch
 
-__all__ = ["grid_points", "add_hills_to_grid", "opes_kernel_sum", "Restraint", "Hills", "Grid", "Opes"]
+__all__ = ["grid_points", "add_hills_to_grid", "opes_kernel_sum", "Restraint", "Hills", "Grid", "Opes", "OpesTable"]
 
 HILLS_MAX_COLUMNS = 8     # HILLS_MAX_D of csrc/molann_math.h
 GRID_MAX_COLUMNS = 3      # GRID_MAX_D of csrc/molann_math.h
@@ -180,3 +183,108 @@ def opes_kernel_sum(points, centers, heights, sigma, period=None, cutoff=None, c
         kernel = torch.where(q >= c2, torch.zeros_like(q), torch.exp(-0.5 * q) - c0)
         total = total + (heights[rows] * kernel).sum(dim=1)
     return total
+
+
+class OpesTable(object):
+    """The kernel table of an OPES run in device memory, updated in place by one launch per deposit (`molann_opes_deposit_f64`).
+
+    ``centers`` [capacity, d], ``sigma`` [capacity, d] and ``heights`` [capacity] hold the kernels, rows ``>= n`` are dead storage;
+    ``state`` [4] holds ``(n, S, merges, refused)`` with ``S = sum_{i<n} sum_{j<n} heights_j K_j(centers_i)``, the sum OPES normalises
+    with (``Z = S / (n * kde_norm)`` is the caller's, like ``kde_norm``, ``neff`` and the bandwidth rescaling: a few scalars).
+    ``period``: None or [d] (> 0: that output is periodic); ``cutoff``: None (no cutoff) or > 0, in widths; ``threshold``: a new kernel
+    closer than this many widths to a live one is merged into it (0: every kernel is appended).  1 <= d <= 8; a CUDA / HIP device."""
+
+    def __init__(self, capacity, d, device, period=None, cutoff=None, threshold=1.0):
+        if isinstance(capacity, bool) or isinstance(d, bool):
+            raise TypeError("OpesTable: `capacity` and `d` must be integers")
+        capacity, d = operator.index(capacity), operator.index(d)
+        if capacity < 1:
+            raise ValueError("OpesTable: `capacity` must be >= 1; got %d" % capacity)
+        if not 1 <= d <= HILLS_MAX_COLUMNS:
+            raise ValueError("OpesTable: `d` must be 1..%d (the one-launch kernels' widest kernel); got %d" % (HILLS_MAX_COLUMNS, d))
+        threshold = float(threshold)
+        if not (math.isfinite(threshold) and threshold >= 0.0):
+            raise ValueError("OpesTable: `threshold` must be finite and >= 0; got %r" % (threshold,))
+        if cutoff is not None and not float(cutoff) > 0.0:
+            raise ValueError("OpesTable: `cutoff` must be None or > 0; got %r" % (cutoff,))
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("OpesTable: the table lives in device memory and its kernels are HIP kernels; got device %s" % device)
+        f64 = dict(dtype=torch.float64, device=device)
+        if period is not None:
+            period = torch.as_tensor(period, **f64)
+            if period.shape != (d,):
+                raise ValueError("OpesTable: `period` must be None or [%d]; got %s" % (d, list(period.shape)))
+            period = period.contiguous()
+        self.capacity, self.d, self.device = capacity, d, device
+        self.period, self.cutoff, self.threshold = period, None if cutoff is None else float(cutoff), threshold
+        self.centers = torch.zeros(capacity, d, **f64)
+        self.sigma = torch.zeros(capacity, d, **f64)
+        self.heights = torch.zeros(capacity, **f64)
+        self.state = torch.zeros(4, **f64)
+
+    def _tensor(self, name, value, shape, what):
+        if not isinstance(value, torch.Tensor):
+            raise TypeError("OpesTable.%s must be a tensor on %s; got %s" % (name, self.device, type(value).__name__))
+        if value.dtype != torch.float64:
+            raise TypeError("OpesTable.%s must be float64; got %s" % (name, value.dtype))
+        if value.device != self.centers.device or tuple(value.shape) not in shape:
+            raise ValueError("OpesTable.%s must be %s on %s; got %s on %s" % (name, what, self.centers.device, list(value.shape), value.device))
+        return value.detach()
+
+    def deposit(self, centers, sigma, heights):
+        """Compress the new kernels ``centers`` [W, d], ``sigma`` [W, d] or [d], ``heights`` [W] or a float into the table, in order:
+        one launch on the current stream, nothing read back, returns None - the tensors may come from torch arithmetic on
+        `value_and_opes`' outputs, and deposits may be queued back to back.  A kernel that is not finite, or whose widths or height
+        are not > 0, is counted in ``refused`` and changes nothing else; so is a kernel that finds the table full."""
+        from . import _capi
+        if not (isinstance(centers, torch.Tensor) and centers.dim() == 2):
+            raise ValueError("OpesTable.deposit: `centers` must be a [W, %d] tensor" % self.d)
+        n_new = centers.shape[0]
+        centers = self._tensor("deposit: `centers`", centers, [(n_new, self.d)], "[W, %d]" % self.d).contiguous()
+        sigma = self._tensor("deposit: `sigma`", sigma, [(n_new, self.d), (self.d,)], "[W, %d] or [%d]" % (self.d, self.d))
+        sigma = sigma.expand(n_new, self.d).contiguous()
+        if isinstance(heights, torch.Tensor):
+            heights = self._tensor("deposit: `heights`", heights, [(n_new,), ()], "[W] or a scalar").expand(n_new).contiguous()
+        else:
+            heights = torch.full((n_new,), float(heights), dtype=torch.float64, device=self.centers.device)
+        if n_new == 0:
+            return None
+        with torch.cuda.device(self.centers.device):
+            _capi.opes_deposit_f64(self.centers, self.sigma, self.heights, self.state, self.period, centers, sigma, heights, self.threshold,
+                                   self.cutoff)
+        return None
+
+    def read_state(self):
+        """``(n, S, merges, refused)`` as Python numbers: the one 32-byte read-back (it waits for the deposits queued before it)."""
+        n, total, merges, refused = self.state.tolist()
+        return int(n), total, int(merges), int(refused)
+
+    def kernel_sum(self, points, with_grad=False, n=None):
+        """``P[m] = sum_h heights_h K_h(points[m])`` [M] over the live rows, and with ``with_grad`` ``(P, dP)`` with dP [M, d]: one launch
+        (`molann_opes_kernel_sum_f64`, the bias kernels' walk).  ``n``: the live count where the caller has it; None reads the state."""
+        from . import _capi
+        n = self.read_state()[0] if n is None else operator.index(n)
+        if not (isinstance(points, torch.Tensor) and points.dim() == 2):
+            raise ValueError("OpesTable.kernel_sum: `points` must be a [M, %d] tensor" % self.d)
+        points = self._tensor("kernel_sum: `points`", points, [(points.shape[0], self.d)], "[M, %d]" % self.d).contiguous()
+        out = torch.empty(points.shape[0], dtype=torch.float64, device=points.device)
+        grad = torch.empty(points.shape[0], self.d, dtype=torch.float64, device=points.device) if with_grad else None
+        if points.shape[0] == 0:
+            return (out, grad) if with_grad else out
+        with torch.cuda.device(points.device):
+            return _capi.opes_kernel_sum_f64(points, self.centers[:n], self.heights[:n], self.sigma[:n], self.period, self.cutoff, out, grad)
+
+    def recompute_sum(self, n=None):
+        """S from scratch, ``kernel_sum(centers[:n]).sum()``, written into ``state[1]`` (a restart, a table the caller edited, a check on
+        the incremental sum).  Returns the sum as a tensor on the device."""
+        n = self.read_state()[0] if n is None else operator.index(n)
+        total = self.kernel_sum(self.centers[:n], n=n).sum()
+        self.state[1] = total
+        return total
+
+    def record(self, scale, norm, epsilon, columns=None, n=None):
+        """The `Opes` record of the live rows - contiguous views ``[:n]``, nothing copied - for `value_and_opes` (unpack its fields)
+        and `value_and_bias(opes=...)`.  ``n``: the live count where the caller has it; None reads the state."""
+        n = self.read_state()[0] if n is None else operator.index(n)
+        return Opes(self.centers[:n], self.heights[:n], self.sigma[:n], scale, norm, epsilon, self.cutoff, self.period, columns)

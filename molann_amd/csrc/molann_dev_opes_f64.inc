@@ -1,8 +1,7 @@
 // molann_dev_opes_f64.inc - part of libmolann_hip.so, included by molann_kernels.hip after molann_dev_metric_f64.inc.  Float64 values, an
 // OPES bias on them - the logarithm of a kernel density - and its gradient in one launch (molann_value_and_opes_f64 launches it).
-// Out of scope: depositing, merging or compressing kernels and the update of the normalisation (the caller's, between steps, with
-// molann_amd.bias.opes_kernel_sum); float32; a GraphedForces replay; neighbour lists; gradients with respect to the table or the
-// parameters.  An OPES term next to walls and a table, on chosen outputs: frames_value_bias_opes_f64_kernel of
+// Depositing, merging and compressing kernels and the sum the normalisation is formed from: molann_dev_opes_deposit_f64.inc.  Out of
+// scope: float32; a GraphedForces replay; neighbour lists; gradients with respect to the table or the parameters.  An OPES term next to walls and a table, on chosen outputs: frames_value_bias_opes_f64_kernel of
 // molann_dev_bias_opes_f64.inc, a kernel instance of its own that calls this file's walk, so that the instances here keep their code.
 namespace {
 

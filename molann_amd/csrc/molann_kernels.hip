@@ -68,6 +68,7 @@ using namespace molann;
 #include "molann_dev_metric_f64.inc"
 #include "molann_dev_opes_f64.inc"
 #include "molann_dev_bias_opes_f64.inc"
+#include "molann_dev_opes_deposit_f64.inc"
 // Host code (what `make san` instruments: -fno-gpu-sanitize leaves the device code alone):
 #include "molann_host_plan.inc"
 #include "molann_host_jit.inc"
@@ -77,3 +78,4 @@ using namespace molann;
 #include "molann_jvp.inc"
 #include "molann_hvp.inc"
 #include "molann_value_f64.inc"
+#include "molann_opes_deposit_f64.inc"

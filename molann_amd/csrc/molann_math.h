@@ -659,6 +659,146 @@ MOLANN_HD double opes_transform_f64(double P, const double (&acc)[HILLS_MAX_D], 
     return scale * log(u);
 }
 
+// The per-kernel arithmetic of an OPES deposit (opes_deposit_f64_kernel and its host twin): compressing a new kernel into the table and
+// keeping S = sum_i sum_j h_j K_j(c_i) over the live kernels, the sum the normalisation Z is formed from.  Nothing is contracted.
+//
+// opes_merge_distance_f64: q = sum_k (wrap(a_k - c_k) / sigma_k)^2 of a candidate centre `a` from the table kernel (c, sigma), in the
+// table kernel's widths: opes_term_f64's d_k, wrap, 1 / sigma_k, product and ascending-k sum, operation for operation, and no exp, so
+// the host and the device get the same bits and take the same decisions.
+MOLANN_HD double opes_merge_distance_f64(const double* a, const double* c, const double* sigma, const double* period, int d) {
+#pragma clang fp contract(off)
+    double q = 0.0;
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k) {
+        if (k < d) {
+            double dk = a[k] - c[k];
+            const double P = period ? period[k] : 0.0;
+            if (P > 0.0) {
+                const double turns = rint(dk / P);
+                const double whole = P * turns;
+                dk = dk - whole;
+            }
+            const double inv = 1.0 / sigma[k];
+            const double s = dk * inv;
+            q = q + s * s;
+        }
+    }
+    return q;
+}
+
+// opes_merge_f64: the giver (cg, sg, hg) merges into the taker (ct, st, ht): h' = ht + hg, delta_k = wrap(cg_k - ct_k),
+// c'_k = ct_k + (hg / h') delta_k and sigma'_k^2 = (ht st_k^2 + hg sg_k^2) / h' + (ht hg / h'^2) delta_k^2 - the weight, mean and variance
+// of the two kernels' mixture, the mean taken along the shorter way round a periodic output (c' is not wrapped back: every reader wraps
+// differences).  Returns h'; co and so may be either kernel's arrays (column k is read before it is written).  Only +, -, *, /, rint and
+// sqrt: the host and the device round alike up to sqrt.
+MOLANN_HD double opes_merge_f64(const double* ct, const double* st, double ht, const double* cg, const double* sg, double hg, const double* period,
+                                int d, double* co, double* so) {
+#pragma clang fp contract(off)
+    const double h = ht + hg;
+    const double wg = hg / h;
+    const double wtg = (ht * hg) / (h * h);
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k) {
+        if (k < d) {
+            double dk = cg[k] - ct[k];
+            const double P = period ? period[k] : 0.0;
+            if (P > 0.0) {
+                const double turns = rint(dk / P);
+                const double whole = P * turns;
+                dk = dk - whole;
+            }
+            const double var = (ht * (st[k] * st[k]) + hg * (sg[k] * sg[k])) / h + wtg * (dk * dk);
+            co[k] = ct[k] + wg * dk;
+            so[k] = sqrt(var);
+        }
+    }
+    return h;
+}
+
+// opes_pair_term_f64: what the kernels e and i add to S together, h_e K_e(c_i) + h_i K_i(c_e), each half opes_term_f64 with its result
+// taken and its acc ignored; inv_e is hill_inverse_widths_f64 of e's widths, formed once per walk (the same rounded values as 1 / sigma
+// per term).  A kernel's own term is h (1 - c0): opes_self_term_f64.
+MOLANN_HD double opes_pair_term_f64(const double* ce, const double* se, const double (&inv_e)[HILLS_MAX_D], double he, const double* ci,
+                                    const double* si, double hi, const double* period, double c2, double c0, int d) {
+#pragma clang fp contract(off)
+    double ignored[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
+    const double at_i = opes_term_f64(ci, ce, se, inv_e, true, period, he, c2, c0, d, ignored);
+    const double at_e = opes_term_f64(ce, ci, si, inv_e, false, period, hi, c2, c0, d, ignored);
+    return at_i + at_e;
+}
+MOLANN_HD double opes_self_term_f64(double h, double c0) {
+#pragma clang fp contract(off)
+    return h * (1.0 - c0);
+}
+
+// a new kernel is taken when every value is finite, every width > 0 and the height > 0 (a NaN fails every comparison)
+MOLANN_HD bool opes_kernel_valid_f64(const double* c, const double* sigma, double h, int d) {
+    bool ok = h > 0.0 && h <= 1.7976931348623157e308;
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k)
+        if (k < d) ok = ok && fabs(c[k]) <= 1.7976931348623157e308 && sigma[k] > 0.0 && sigma[k] <= 1.7976931348623157e308;
+    return ok;
+}
+
+// the live count of a deposit's state: an exact integer in a double, held to [0, capacity] whatever the bits (a NaN gives 0)
+MOLANN_HD long opes_live_count_f64(double n, long capacity) {
+    return n >= (double)capacity ? capacity : n >= 1.0 ? (long)n : 0;
+}
+
+// The deposit itself, one copy for the device and the host: `ex` gives the table (load_new, load, store, move), the search
+// (nearest: the live kernel with the smallest opes_merge_distance_f64 from a centre, then the smallest slot, one slot left out; false
+// where there is none) and the walk (pair_sum: sum of opes_pair_term_f64 over the live kernels, two slots left out, in its fixed
+// order); every thread of the device's block runs these steps on the same values and takes the same decisions.  Per new kernel, in
+// order: refused unless opes_kernel_valid_f64; then, as the giver g (not in the table yet: slot -1), while a live kernel t other than g
+// lies within the threshold (q < threshold^2, strict): S loses g's terms (where g is in the table) and t's, t takes g by
+// opes_merge_f64 and stays in its slot, S gains the merged kernel's terms, g's slot is filled by the last live kernel (which may be t),
+// and the merged kernel is the next giver.  Every round but a new kernel's first removes a kernel, so the chain ends.  A new kernel
+// that met nobody is appended while there is room and refused otherwise.  n, S, merges and refused are the state's four values.
+template <class Ex>
+MOLANN_HD void opes_deposit_steps_f64(Ex& ex, long capacity, int d, const double* period, long n_new, double threshold, double cutoff, long& n,
+                                      double& S, double& merges, double& refused) {
+#pragma clang fp contract(off)
+    double c2, c0;
+    opes_cutoff_f64(cutoff, c2, c0);
+    const double thr2 = threshold * threshold;
+    for (long a = 0; a < n_new; ++a) {
+        double cg[HILLS_MAX_D], sg[HILLS_MAX_D], hg;
+        ex.load_new(a, cg, sg, hg);
+        if (!opes_kernel_valid_f64(cg, sg, hg, d)) {
+            refused = refused + 1.0;
+            continue;
+        }
+        long g = -1;
+        for (;;) {
+            double q = 0.0;
+            long t = -1;
+            if (!(threshold > 0.0 && ex.nearest(cg, n, g, q, t) && q < thr2)) break;
+            double ct[HILLS_MAX_D], st[HILLS_MAX_D], ht;
+            ex.load(t, ct, st, ht);
+            if (g >= 0) S = S - (ex.pair_sum(cg, sg, hg, n, g, -1, c2, c0) + opes_self_term_f64(hg, c0));   // remove g; t is still live
+            S = S - (ex.pair_sum(ct, st, ht, n, t, g, c2, c0) + opes_self_term_f64(ht, c0));                 // remove t
+            hg = opes_merge_f64(ct, st, ht, cg, sg, hg, period, d, cg, sg);
+            S = S + (ex.pair_sum(cg, sg, hg, n, t, g, c2, c0) + opes_self_term_f64(hg, c0));                 // add the merged kernel
+            ex.store(t, cg, sg, hg);
+            merges = merges + 1.0;
+            if (g >= 0) {
+                if (g != n - 1) ex.move(n - 1, g);
+                if (t == n - 1) t = g;
+                n -= 1;
+            }
+            g = t;
+        }
+        if (g >= 0) continue;
+        if (n < capacity) {
+            S = S + (ex.pair_sum(cg, sg, hg, n, -1, -1, c2, c0) + opes_self_term_f64(hg, c0));
+            ex.store(n, cg, sg, hg);
+            n += 1;
+        } else {
+            refused = refused + 1.0;
+        }
+    }
+}
+
 // A bias tabulated on a regular grid over d <= GRID_MAX_D outputs, interpolated by cubic convolution (Catmull-Rom): V(y) = sum over the
 // 4^d stencil points of T[idx_0 j0, ...] prod_k a_k jk, dV/dy_k the same sum with b_k jk in place of a_k jk.  grid_axis_f64 is one
 // axis' step: u = (y - lower) / h; periodic: u <- u - n floor(u / n), i = floor(u) held in [0, n - 1], idx_j = (i - 1 + j) mod n;

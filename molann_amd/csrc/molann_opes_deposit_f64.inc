@@ -1,0 +1,132 @@
+// molann_opes_deposit_f64.inc - part of libmolann_hip.so, included by molann_kernels.hip after molann_value_f64.inc.  The host side of
+// molann_dev_opes_deposit_f64.inc (see include/molann_hip.h): molann_opes_deposit_f64 and molann_opes_kernel_sum_f64 check their
+// arguments and enqueue one launch each - no plan, no workspace, no event - and molann_selftest_opes_deposit_f64 runs the deposit on host
+// arrays through the same steps and the same per-kernel functions, with the device's order of every sum.
+namespace {
+
+// the device's block on the host: the same strided partials, the same butterfly, the same order of the four waves
+struct OpesDepositHost {
+    double* centers;
+    double* sigma;
+    double* heights;
+    const double* period;
+    const double* new_centers;
+    const double* new_sigma;
+    const double* new_heights;
+    int d;
+
+    void read_row(const double* c, const double* s, const double* h, long row, double (&co)[HILLS_MAX_D], double (&so)[HILLS_MAX_D], double& ho) const {
+        for (int k = 0; k < HILLS_MAX_D; ++k) {
+            co[k] = k < d ? c[row * d + k] : 0.0;
+            so[k] = k < d ? s[row * d + k] : 1.0;
+        }
+        ho = h[row];
+    }
+    void load_new(long a, double (&c)[HILLS_MAX_D], double (&s)[HILLS_MAX_D], double& h) const { read_row(new_centers, new_sigma, new_heights, a, c, s, h); }
+    void load(long slot, double (&c)[HILLS_MAX_D], double (&s)[HILLS_MAX_D], double& h) const { read_row(centers, sigma, heights, slot, c, s, h); }
+    void store(long slot, const double (&c)[HILLS_MAX_D], const double (&s)[HILLS_MAX_D], double h) const {
+        for (int k = 0; k < d; ++k) { centers[slot * d + k] = c[k]; sigma[slot * d + k] = s[k]; }
+        heights[slot] = h;
+    }
+    void move(long from, long to) const {
+        for (int k = 0; k < d; ++k) { centers[to * d + k] = centers[from * d + k]; sigma[to * d + k] = sigma[from * d + k]; }
+        heights[to] = heights[from];
+    }
+    // the smallest q, then the smallest slot: ascending slots and a strict comparison give the pair the device's reduction gives
+    bool nearest(const double (&c)[HILLS_MAX_D], long n, long skip, double& q_out, long& slot_out) const {
+        double q = HUGE_VAL;
+        long slot = -1;
+        bool any = false;
+        for (long k = 0; k < n; ++k) {
+            if (k == skip) continue;
+            const double qk = opes_merge_distance_f64(c, centers + k * d, sigma + k * d, period, d);
+            if (qk < q) { q = qk; slot = k; any = true; }
+        }
+        q_out = q; slot_out = slot;
+        return any;
+    }
+    double pair_sum(const double (&ce)[HILLS_MAX_D], const double (&se)[HILLS_MAX_D], double he, long n, long skip_a, long skip_b, double c2,
+                    double c0) const {
+        double inv[HILLS_MAX_D];
+        hill_inverse_widths_f64(se, d, inv);
+        double part[256], next[64];
+        for (int t = 0; t < 256; ++t) {
+            part[t] = 0.0;
+            for (long i = t; i < n; i += 256) {
+                if (i == skip_a || i == skip_b) continue;
+                part[t] = part[t] + opes_pair_term_f64(ce, se, inv, he, centers + i * d, sigma + i * d, heights[i], period, c2, c0, d);
+            }
+        }
+        for (int w = 0; w < 4; ++w)
+            for (int m = 32; m >= 1; m >>= 1) {
+                for (int l = 0; l < 64; ++l) next[l] = part[64 * w + l] + part[64 * w + (l ^ m)];
+                for (int l = 0; l < 64; ++l) part[64 * w + l] = next[l];
+            }
+        return ((part[0] + part[64]) + part[128]) + part[192];
+    }
+};
+
+// the arguments molann_opes_deposit_f64 and its host twin share, in the order of the refusals
+inline int opes_deposit_arguments(const double* centers, const double* sigma, const double* heights, int64_t capacity, int32_t d,
+                                  const double* period, const double* state, const double* new_centers, const double* new_sigma,
+                                  const double* new_heights, int64_t n_new, double threshold, double cutoff) {
+    if (n_new > 0 && (!centers || !sigma || !heights || !state || !new_centers || !new_sigma || !new_heights)) return MOLANN_E_NULL;
+    if (((uintptr_t)centers | (uintptr_t)sigma | (uintptr_t)heights | (uintptr_t)period | (uintptr_t)state | (uintptr_t)new_centers |
+         (uintptr_t)new_sigma | (uintptr_t)new_heights) & 7)
+        return MOLANN_E_ALIGNMENT;
+    if (d < 1 || d > HILLS_MAX_D) return MOLANN_E_DESC;
+    if (capacity < 1) return MOLANN_E_DESC;
+    if (n_new < 0) return MOLANN_E_DESC;
+    if (!std::isfinite(threshold) || threshold < 0.0) return MOLANN_E_DESC;
+    if (!(cutoff > 0.0)) return MOLANN_E_DESC;
+    return MOLANN_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int molann_opes_deposit_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
+                            const double* new_centers, const double* new_sigma, const double* new_heights, int64_t n_new, double threshold,
+                            double cutoff, molann_stream_t stream) {
+    const int e = opes_deposit_arguments(centers, sigma, heights, capacity, d, period, state, new_centers, new_sigma, new_heights, n_new, threshold,
+                                         cutoff);
+    if (e != MOLANN_OK || n_new == 0) return e;
+    hipLaunchKernelGGL(opes_deposit_f64_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, centers, sigma, heights, (long)capacity, (int)d, period,
+                       state, new_centers, new_sigma, new_heights, (long)n_new, threshold, cutoff);
+    return (int)hipGetLastError();
+}
+
+int molann_selftest_opes_deposit_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period,
+                                     double* state, const double* new_centers, const double* new_sigma, const double* new_heights, int64_t n_new,
+                                     double threshold, double cutoff) {
+    const int e = opes_deposit_arguments(centers, sigma, heights, capacity, d, period, state, new_centers, new_sigma, new_heights, n_new, threshold,
+                                         cutoff);
+    if (e != MOLANN_OK || n_new == 0) return e;
+    OpesDepositHost ex = {centers, sigma, heights, period, new_centers, new_sigma, new_heights, (int)d};
+    long n = opes_live_count_f64(state[0], (long)capacity);
+    double S = state[1], merges = state[2], refused = state[3];
+    opes_deposit_steps_f64(ex, (long)capacity, (int)d, period, (long)n_new, threshold, cutoff, n, S, merges, refused);
+    state[0] = (double)n; state[1] = S; state[2] = merges; state[3] = refused;
+    return MOLANN_OK;
+}
+
+int molann_opes_kernel_sum_f64(const double* points, int64_t n_points, int32_t d, const double* centers, const double* heights, int64_t n_kernels,
+                               const double* sigma, int64_t sigma_stride, const double* period, double cutoff, double* P, double* dP,
+                               molann_stream_t stream) {
+    if (n_points < 0 || n_kernels < 0) return MOLANN_E_DESC;
+    if (n_points == 0) return MOLANN_OK;
+    if (!points || !P || (n_kernels > 0 && (!centers || !heights || !sigma))) return MOLANN_E_NULL;
+    if (((uintptr_t)points | (uintptr_t)P | (uintptr_t)dP | (uintptr_t)centers | (uintptr_t)heights | (uintptr_t)sigma | (uintptr_t)period) & 7)
+        return MOLANN_E_ALIGNMENT;
+    if (d < 1 || d > HILLS_MAX_D) return MOLANN_E_UNSUPPORTED;
+    if (sigma_stride != 0 && sigma_stride != d) return MOLANN_E_DESC;
+    if (!(cutoff > 0.0)) return MOLANN_E_DESC;
+    const int64_t blocks = (n_points + 3) / 4;
+    const int grid = (int)std::min<int64_t>(blocks, 2048);    // 8 blocks of 4 waves per compute unit; the loop strides over the rest
+    hipLaunchKernelGGL(opes_kernel_sum_f64_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, points, centers, heights, sigma, period, P, dP,
+                       (long)n_points, (long)n_kernels, (long)sigma_stride, cutoff, (int)d);
+    return (int)hipGetLastError();
+}
+
+} // extern "C"

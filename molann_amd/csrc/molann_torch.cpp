@@ -1079,6 +1079,80 @@ std::vector<at::Tensor> value_and_bias_opes_impl(const at::Tensor& x_in, const s
           "molann_value_and_bias_opes_f64");
     return {out, energies, gx};
 }
+// The deposit step of an OPES run (molann_opes_deposit_f64): the new kernels are compressed into the caller's table in place and `state` =
+// (n, S, merges, refused) is updated, in ONE launch on the current stream; nothing is read back.  The table: centers [cap, d], sigma [cap, d],
+// heights [cap], state [4], contiguous float64 on one device (they are written: no copy is made); the new kernels: [W, d], [W, d], [W].
+at::Tensor opes_tensor(const char* op, const char* what, const at::Tensor& t, const at::Tensor& like, bool ok, const char* shape, bool written) {
+    TORCH_CHECK_TYPE(t.scalar_type() == at::kDouble, op, ": `", what, "` must be float64 (got ", t.scalar_type(), ")");
+    TORCH_CHECK_VALUE(ok && t.device() == like.device(), op, ": `", what, "` must be ", shape, " on ", like.device());
+    TORCH_CHECK_VALUE(!written || t.is_contiguous(), op, ": `", what, "` is written in place and must be contiguous");
+    return written ? t : t.detach().contiguous();
+}
+void opes_deposit_hip(at::Tensor centers_in, at::Tensor sigma_in, at::Tensor heights_in, at::Tensor state_in, const c10::optional<at::Tensor>& period_in,
+                      const at::Tensor& new_centers_in, const at::Tensor& new_sigma_in, const at::Tensor& new_heights_in, double threshold,
+                      double cutoff) {
+    const char* const op = "molann::opes_deposit";
+    TORCH_CHECK_VALUE(centers_in.dim() == 2 && centers_in.size(0) >= 1 && centers_in.size(1) >= 1 && centers_in.size(1) <= 8,
+                      "molann::opes_deposit: `centers` must be [capacity >= 1, 1 <= d <= 8]");
+    TORCH_CHECK_VALUE(std::isfinite(threshold) && threshold >= 0.0 && cutoff > 0.0,
+                      "molann::opes_deposit: `threshold` must be finite and >= 0, `cutoff` > 0 (inf: none); got ", threshold, ", ", cutoff);
+    const int64_t cap = centers_in.size(0), d = centers_in.size(1);
+    const at::Tensor centers = opes_tensor(op, "centers", centers_in, centers_in, true, "[capacity, d]", true);
+    const at::Tensor sigma = opes_tensor(op, "sigma", sigma_in, centers, sigma_in.dim() == 2 && sigma_in.size(0) == cap && sigma_in.size(1) == d,
+                                            "[capacity, d]", true);
+    const at::Tensor heights = opes_tensor(op, "heights", heights_in, centers, heights_in.dim() == 1 && heights_in.size(0) == cap, "[capacity]", true);
+    const at::Tensor state = opes_tensor(op, "state", state_in, centers, state_in.dim() == 1 && state_in.size(0) == 4, "[4]", true);
+    at::Tensor period;
+    if (period_in.has_value() && period_in->defined())
+        period = opes_tensor(op, "period", *period_in, centers, period_in->dim() == 1 && period_in->size(0) == d, "[d]", false);
+    const at::Tensor new_centers = opes_tensor(op, "new_centers", new_centers_in, centers, new_centers_in.dim() == 2 && new_centers_in.size(1) == d,
+                                                  "[W, d]", false);
+    const int64_t n_new = new_centers.size(0);
+    const at::Tensor new_sigma = opes_tensor(op, "new_sigma", new_sigma_in, centers,
+                                                new_sigma_in.dim() == 2 && new_sigma_in.size(0) == n_new && new_sigma_in.size(1) == d, "[W, d]", false);
+    const at::Tensor new_heights = opes_tensor(op, "new_heights", new_heights_in, centers, new_heights_in.dim() == 1 && new_heights_in.size(0) == n_new,
+                                                  "[W]", false);
+    if (n_new == 0) return;
+    const c10::DeviceGuard guard(centers.device());
+    hipStream_t stream = c10::hip::getCurrentHIPStream(centers.get_device()).stream();
+    check(molann_opes_deposit_f64(centers.data_ptr<double>(), sigma.data_ptr<double>(), heights.data_ptr<double>(), cap, (int32_t)d,
+                                  period.defined() ? period.data_ptr<double>() : nullptr, state.data_ptr<double>(), new_centers.data_ptr<double>(),
+                                  new_sigma.data_ptr<double>(), new_heights.data_ptr<double>(), n_new, threshold, cutoff, stream),
+          "molann_opes_deposit_f64");
+}
+
+// {P} or {P, dP}: the kernel density of an OPES table at points [M, d] and, with `with_grad`, its derivative [M, d] in ONE launch
+// (molann_opes_kernel_sum_f64).  The table as value_and_opes takes it.
+std::vector<at::Tensor> opes_kernel_sum_hip(const at::Tensor& points_in, const at::Tensor& centers_in, const at::Tensor& heights_in,
+                                            const at::Tensor& sigma_in, const c10::optional<at::Tensor>& period_in, double cutoff, bool with_grad) {
+    const char* const op = "molann::opes_kernel_sum";
+    TORCH_CHECK_TYPE(points_in.scalar_type() == at::kDouble, "molann::opes_kernel_sum: `points` must be float64 (got ", points_in.scalar_type(), ")");
+    TORCH_CHECK_VALUE(points_in.dim() == 2 && points_in.size(1) >= 1 && points_in.size(1) <= 8, "molann::opes_kernel_sum: `points` must be [M, 1 <= d <= 8]");
+    TORCH_CHECK_VALUE(cutoff > 0.0, "molann::opes_kernel_sum: `cutoff` must be > 0 (inf: none); got ", cutoff);
+    const at::Tensor points = points_in.detach().contiguous();
+    const int64_t m = points.size(0), d = points.size(1);
+    const at::Tensor centers = opes_tensor(op, "centers", centers_in, points, centers_in.dim() == 2 && centers_in.size(1) == d, "[H, d]", false);
+    const int64_t n_kernels = centers.size(0);
+    const at::Tensor heights = opes_tensor(op, "heights", heights_in, points, heights_in.dim() == 1 && heights_in.size(0) == n_kernels, "[H]", false);
+    const bool per_kernel = sigma_in.dim() == 2 && sigma_in.size(0) == n_kernels && sigma_in.size(1) == d;
+    const at::Tensor sigma = opes_tensor(op, "sigma", sigma_in, points, per_kernel || (sigma_in.dim() == 1 && sigma_in.size(0) == d), "[d] or [H, d]", false);
+    at::Tensor period;
+    if (period_in.has_value() && period_in->defined()) period = opes_tensor(op, "period", *period_in, points, period_in->dim() == 1 && period_in->size(0) == d, "[d]", false);
+    at::Tensor P = at::empty({m}, points.options()), dP;
+    if (with_grad) dP = at::empty({m, d}, points.options());
+    if (m > 0) {
+        const c10::DeviceGuard guard(points.device());
+        hipStream_t stream = c10::hip::getCurrentHIPStream(points.get_device()).stream();
+        check(molann_opes_kernel_sum_f64(points.data_ptr<double>(), m, (int32_t)d, n_kernels > 0 ? centers.data_ptr<double>() : nullptr,
+                                         n_kernels > 0 ? heights.data_ptr<double>() : nullptr, n_kernels, n_kernels > 0 ? sigma.data_ptr<double>() : nullptr,
+                                         per_kernel ? d : 0, period.defined() ? period.data_ptr<double>() : nullptr, cutoff, P.data_ptr<double>(),
+                                         with_grad ? dP.data_ptr<double>() : nullptr, stream),
+              "molann_opes_kernel_sum_f64");
+    }
+    if (with_grad) return {P, dP};
+    return {P};
+}
+
 #define MOLANN_BIAS_OPES_OP_PARAMS                                                                                                                   \
     const at::Tensor &ref_x, std::vector<at::Tensor> weights, std::vector<at::Tensor> biases, const c10::optional<at::Tensor>&center,                \
         const c10::optional<at::Tensor>&kappa, const c10::optional<at::Tensor>&rperiod, const c10::optional<at::Tensor>&flat,                        \
@@ -1747,6 +1821,9 @@ TORCH_LIBRARY(molann, m) {
     m.def("value_and_bias_opes(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, Tensor? restraint_period, "
           "Tensor? flat, int[] opes_columns, Tensor centers, Tensor heights, Tensor sigma, Tensor? opes_period, float scale, float norm, float epsilon, "
           "float cutoff, int[] grid_columns, Tensor? table, float[] lower, float[] spacing, bool[] periodic, Tensor[] into) -> Tensor[]");
+    m.def("opes_deposit(Tensor(a!) centers, Tensor(b!) sigma, Tensor(c!) heights, Tensor(d!) state, Tensor? period, Tensor new_centers, "
+          "Tensor new_sigma, Tensor new_heights, float threshold, float cutoff) -> ()");
+    m.def("opes_kernel_sum(Tensor points, Tensor centers, Tensor heights, Tensor sigma, Tensor? period, float cutoff, bool with_grad) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
     m.def("run_head(Tensor feat, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases) -> Tensor", run_head);
@@ -1783,6 +1860,8 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_bias_h", value_and_bias_h_hip);
     m.impl("value_and_bias_opes", value_and_bias_opes_hip);
     m.impl("value_and_bias_opes_h", value_and_bias_opes_h_hip);
+    m.impl("opes_deposit", opes_deposit_hip);
+    m.impl("opes_kernel_sum", opes_kernel_sum_hip);
 }
 
 TORCH_LIBRARY_IMPL(molann, Autograd, m) { m.impl("run", run_autograd); }
