@@ -543,8 +543,9 @@ int molann_plan_supports_value_and_bias_opes_f64(const molann_plan* plan);
  * NULL table, state or new pointer where n_new > 0: MOLANN_E_NULL; a pointer that is not 8-byte aligned: MOLANN_E_ALIGNMENT; d outside
  * 1..8, capacity < 1, n_new < 0, a threshold that is not finite or < 0, a cutoff that is NaN or not > 0 (+inf: none): MOLANN_E_DESC.
  * n_new == 0: MOLANN_OK, nothing launched.  The call only enqueues on `stream` (no workspace, no event): thread-safe on distinct tables
- * and capturable.  Out of scope: kde_norm, neff, the bandwidth rescaling and Z from S (the caller's scalars); more than one block;
- * neighbour lists; float32. */
+ * and capturable.  neff, the bandwidth rescaling and the heights of a step's kernels, formed on the device from a bias launch's outputs:
+ * molann_opes_step_f64; the bias from this state with no read-back: molann_value_and_opes_table_f64.  Out of scope: more than one
+ * block; neighbour lists; float32. */
 int molann_opes_deposit_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
                             const double* new_centers, const double* new_sigma, const double* new_heights, int64_t n_new, double threshold,
                             double cutoff, molann_stream_t stream);
@@ -559,6 +560,54 @@ int molann_opes_deposit_f64(double* centers, double* sigma, double* heights, int
 int molann_opes_kernel_sum_f64(const double* points, int64_t n_points, int32_t d, const double* centers, const double* heights, int64_t n_kernels,
                                const double* sigma, int64_t sigma_stride, const double* period, double cutoff, double* P, double* dP,
                                molann_stream_t stream);
+
+/* molann_value_and_opes_f64 on a table kept by molann_opes_deposit_f64 / molann_opes_step_f64, in ONE launch of
+ * frames_value_opes_table_f64_kernel (ahead of time: no hipRTC): the live count and the normalisation are read from the table's state in
+ * device memory, not passed by value, so the host needs neither - no read-back between a deposit and the next bias, and the launch can
+ * be captured in a graph and replayed while the table grows.  centers[capacity, out_dim], sigma[capacity, out_dim] (a row per kernel) and
+ * heights[capacity] are the table's storage, state[4] = (n, S, merges, refused) its state; every lane forms n = state[0] held to
+ * [0, capacity] (a NaN or a negative value: 0) and norm = S / n - OPES' Z kde_norm, with Z = S / (n kde_norm) - and from there on the
+ * kernel is molann_value_and_opes_f64's: called with that n, that norm and sigma_stride = out_dim it gives the same bits in out, bias and
+ * grad_x.  scale, epsilon and cutoff travel by value as there.  n == 0 (the first step of a run): bias = scale log(epsilon), grad_x
+ * exactly 0, nothing of the table is read and norm is not formed.  A state whose S is not finite and > 0 while n >= 1 gives NaN or inf
+ * for every frame: it is not guarded - a table whose state the caller broke is the caller's (molann_opes_kernel_sum_f64 over the
+ * centres restores S).  Refusals, in molann_value_and_vjp_f64's order and with nothing written: a NULL plan, x, table pointer, state, out,
+ * bias or grad_x: MOLANN_E_NULL; 8-byte alignment (period too): MOLANN_E_ALIGNMENT; a plan without items: MOLANN_E_STAGE; the head's
+ * tensors; a plan molann_value_and_opes_f64 does not serve: MOLANN_E_UNSUPPORTED; capacity < 1, a scale that is not finite, an epsilon
+ * that is not finite and > 0, a cutoff that is NaN or not > 0 (+inf: none): MOLANN_E_DESC.  n_frames == 0: MOLANN_OK.  Out of scope:
+ * molann_value_and_bias_opes_f64 reading the state (a second instance family); float32. */
+int molann_value_and_opes_table_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                                    const double* centers, const double* heights, const double* sigma, int64_t capacity, const double* state,
+                                    const double* period, double scale, double epsilon, double cutoff, double* out, double* bias, double* grad_x,
+                                    molann_stream_t stream);
+
+/* 1 when molann_value_and_opes_table_f64 serves the plan (molann_value_and_opes_f64 serves it), 0 otherwise. */
+int molann_plan_supports_value_and_opes_table_f64(const molann_plan* plan);
+
+/* A whole OPES step after the bias launch, in ONE launch of opes_step_f64_kernel (one block of 256 threads, ahead of time: no hipRTC, no
+ * plan): from y[n_walkers, d] and V[n_walkers] - the out and bias that molann_value_and_opes_table_f64 (or molann_value_and_opes_f64) just
+ * wrote, read only here - it forms this step's kernels and deposits them as molann_opes_deposit_f64 does, on the same table and state,
+ * and keeps run[8] = (counter, sum_w, sum_w2, neff, sigma_scale, rct, 0, 0) in device memory.  OPES_METAD's update with a fixed sigma0
+ * (not the explore variant):
+ *   1. w_a = exp(beta V_a), beta = 1 / kT.  A walker is valid when V_a, w_a and every y[a, k] are finite and w_a > 0; over the valid
+ *      walkers counter += 1, sum_w += w_a, sum_w2 += w_a^2 (the step's sums are formed first, in a fixed order, then added);
+ *   2. neff = (1 + sum_w)^2 / (1 + sum_w2); rct = log(sum_w / counter) / beta, 0 while counter == 0; sigma_scale = 1 where fixed_sigma
+ *      is not 0, else (neff (d + 2) / 4)^(-1 / (d + 4));
+ *   3. sigma_k = sigma0_k sigma_scale, raised to sigma_min_k where sigma_min is not NULL, the same for every walker of the step;
+ *      height_a = w_a prod_k (sigma0_k / sigma_k);
+ *   4. the kernels (y[a], sigma, height_a), a ascending, go through molann_opes_deposit_f64's steps.  An invalid walker's height is NaN,
+ *      so it is refused and counted in state[3]; a sigma0 or sigma_min that is not > 0 and finite makes every kernel of the step
+ *      invalid (they live in device memory: check them where they are made).
+ * The bias kernel's norm needs none of these: it is S / n.  Every sum has a fixed order and there are no atomics: the same bits on
+ * every run.  Refusals, in molann_opes_deposit_f64's order, with nothing enqueued: a NULL table, state, run, y, V or sigma0 where
+ * n_walkers > 0: MOLANN_E_NULL; a pointer that is not 8-byte aligned (period and sigma_min too): MOLANN_E_ALIGNMENT; d outside 1..8,
+ * capacity < 1, n_walkers < 0, a beta that is not finite and > 0, a threshold that is not finite or < 0, a cutoff that is NaN or not > 0:
+ * MOLANN_E_DESC.  n_walkers == 0: MOLANN_OK, nothing launched.  The call only enqueues on `stream` (no workspace, no event, nothing
+ * allocated): capturable, and a bias launch and this one queue back to back with nothing read back.  Out of scope: adaptive sigma, the
+ * explore variant, walkers on several ranks; more than one block; float32. */
+int molann_opes_step_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
+                         double* run, const double* y, const double* V, int64_t n_walkers, const double* sigma0, const double* sigma_min,
+                         double beta, double threshold, double cutoff, int32_t fixed_sigma, molann_stream_t stream);
 
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
@@ -640,6 +689,16 @@ double molann_selftest_opes_f64(const double* y, int d, const double* centers, c
 int molann_selftest_opes_deposit_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period,
                                      double* state, const double* new_centers, const double* new_sigma, const double* new_heights, int64_t n_new,
                                      double threshold, double cutoff);
+/* one frame's bias of molann_value_and_opes_table_f64 on the host: n and norm from state[4] as its kernel forms them (state[0] NaN or
+ * below 1: no kernel; above capacity: capacity), then molann_selftest_opes_f64 on the first n rows with a row of widths per kernel.
+ * d outside 1..8, capacity < 1 or a missing pointer: NaN, dy untouched */
+double molann_selftest_opes_table_f64(const double* y, int d, const double* centers, const double* heights, const double* sigma, int64_t capacity,
+                                      const double* state, const double* period, double scale, double epsilon, double cutoff, double* dy);
+/* molann_opes_step_f64 on the host: the same arguments as HOST pointers, the same steps through the functions its kernel calls, the
+ * same refusals and the device's order of every sum */
+int molann_selftest_opes_step_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
+                                  double* run, const double* y, const double* V, int64_t n_walkers, const double* sigma0, const double* sigma_min,
+                                  double beta, double threshold, double cutoff, int32_t fixed_sigma);
 /* one axis' step of molann_value_and_grid_f64 on the host, through the function its kernel calls: the four table indices, the four
  * weights and the four derivative weights (s w' / spacing) for output value y on an axis of n points; any of the three may be NULL */
 void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]);

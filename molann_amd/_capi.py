@@ -210,6 +210,10 @@ def lib():
             "molann_plan_supports_value_and_bias_opes_f64": (i32, [vp]),
             "molann_opes_deposit_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, ctypes.c_double, ctypes.c_double, vp]),
             "molann_opes_kernel_sum_f64": (i32, [vp, i64, i32, vp, vp, i64, vp, i64, vp, ctypes.c_double, vp, vp, vp]),
+            "molann_value_and_opes_table_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp, i64, vp, vp]
+                                                + [ctypes.c_double] * 3 + [vp, vp, vp, vp]),
+            "molann_plan_supports_value_and_opes_table_f64": (i32, [vp]),
+            "molann_opes_step_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp] + [ctypes.c_double] * 3 + [i32, vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -228,6 +232,8 @@ def lib():
             "molann_selftest_hills_f64": (ctypes.c_double, [vp, i32, vp, vp, i64, vp, i64, vp, vp]),
             "molann_selftest_opes_f64": (ctypes.c_double, [vp, i32, vp, vp, i64, vp, i64, vp] + [ctypes.c_double] * 4 + [vp]),
             "molann_selftest_opes_deposit_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, ctypes.c_double, ctypes.c_double]),
+            "molann_selftest_opes_table_f64": (ctypes.c_double, [vp, i32, vp, vp, vp, i64, vp, vp] + [ctypes.c_double] * 3 + [vp]),
+            "molann_selftest_opes_step_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp] + [ctypes.c_double] * 3 + [i32]),
             "molann_selftest_grid_axis_f64": (None, [ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32, vp, vp, vp]),
             "molann_selftest_grid_f64": (ctypes.c_double, [vp, i32, vp, vp, vp, vp, vp, vp]),
             "molann_selftest_bias_f64": (i32, [vp, i32, ctypes.POINTER(BiasTermsF64), vp, vp]),
@@ -569,6 +575,23 @@ class Plan(object):
 
     value_and_opes = value_and_opes_f64
 
+    def supports_value_and_opes_table_f64(self):
+        """True when `value_and_opes_table_f64` serves this plan: `value_and_opes_f64` serves it (nothing is built)."""
+        return lib().molann_plan_supports_value_and_opes_table_f64(self._handle) == 1
+
+    def value_and_opes_table_f64(self, x, weights, biases, centers, heights, sigma, state, period, scale, epsilon, cutoff, out, bias, grad_x):
+        """`value_and_opes_f64` on a table whose live count and normalisation the kernel reads from `state` [4] = (n, S, merges, refused)
+        in device memory (n held to [0, capacity], norm = S / n), one launch of frames_value_opes_table_f64_kernel: nothing is read
+        back.  `centers` [capacity, d_out], `heights` [capacity] and `sigma` [capacity, d_out] are the table's storage (an
+        `OpesTable`'s tensors); `period` d_out values or None; `scale`, `epsilon`, `cutoff` floats (`cutoff` None or +inf: no cutoff)."""
+        W, B = _layer_pointers(weights, biases)
+        self._launch("molann_value_and_opes_table_f64", x.data_ptr(), x.shape[0], W, B, centers.data_ptr(), heights.data_ptr(), sigma.data_ptr(),
+                     centers.shape[0], state.data_ptr(), period.data_ptr() if period is not None else None, float(scale), float(epsilon),
+                     float("inf") if cutoff is None else float(cutoff), out.data_ptr(), bias.data_ptr(), grad_x.data_ptr())
+        return out, bias, grad_x
+
+    value_and_opes_table = value_and_opes_table_f64
+
     def supports_value_and_grid_f64(self):
         """True when `value_and_grid_f64` serves this plan: `value_and_restraint_f64` serves it and it has at most 3 outputs (nothing
         is built)."""
@@ -700,6 +723,21 @@ def opes_deposit_f64(centers, sigma, heights, state, period, new_centers, new_si
                                          new_heights.data_ptr(), new_centers.shape[0], float(threshold),
                                          float("inf") if cutoff is None else float(cutoff), torch.cuda.current_stream().cuda_stream)
     _check(code, "molann_opes_deposit_f64")
+
+
+def opes_step_f64(centers, sigma, heights, state, run, period, y, V, sigma0, sigma_min, beta, threshold, cutoff=None, fixed_sigma=False):
+    """`molann_opes_step_f64` on torch's current stream: from `y` [W, d] and `V` [W] (the outputs and biases a bias launch just wrote, read
+    only) this step's kernels are formed - weights exp(beta V), the effective sample size, the rescaled widths `sigma0` [d] held above
+    `sigma_min` ([d] or None), the heights - and compressed into the table `centers` [cap, d], `sigma` [cap, d], `heights` [cap] in place;
+    `state` [4] = (n, S, merges, refused) and `run` [8] = (counter, sum_w, sum_w2, neff, sigma_scale, rct, 0, 0) are updated, in one
+    launch; nothing is read back.  Contiguous float64 tensors on one device (`period`: [d] or None); `cutoff` None is +inf.  The tensors'
+    shapes are the caller's to check (`molann_amd.bias.OpesRun` does)."""
+    code = lib().molann_opes_step_f64(centers.data_ptr(), sigma.data_ptr(), heights.data_ptr(), centers.shape[0], centers.shape[1],
+                                      _address(period), state.data_ptr(), run.data_ptr(), y.data_ptr(), V.data_ptr(), y.shape[0],
+                                      sigma0.data_ptr(), _address(sigma_min), float(beta), float(threshold),
+                                      float("inf") if cutoff is None else float(cutoff), 1 if fixed_sigma else 0,
+                                      torch.cuda.current_stream().cuda_stream)
+    _check(code, "molann_opes_step_f64")
 
 
 def opes_kernel_sum_f64(points, centers, heights, sigma, period, cutoff, P, dP=None):

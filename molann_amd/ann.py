@@ -922,9 +922,9 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
 
 # ---- The calls that give the values and a derivative in one launch: MolANN.value_and_vjp / value_and_jacobian / value_and_metric /
 # value_and_restraint / value_and_hills / value_and_grid / value_and_bias and PreprocessingANN.value_and_metric / value_and_restraint /
-# value_and_hills / value_and_grid / value_and_bias, and value_and_opes of both.  What differs
+# value_and_hills / value_and_grid / value_and_bias, and value_and_opes and value_and_opes_table of both.  What differs
 # between them, by kind; the checks and the two ways to the kernel are written once below.
-_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID, _BIAS, _OPES, _BIAS_OPES = 0, 1, 2, 3, 4, 5, 6, 7, 8
+_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID, _BIAS, _OPES, _BIAS_OPES, _OPES_TABLE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 _HILLS_MAX_D_OUT = 8      # HILLS64_MAX_D_OUT of csrc/molann_value_f64.inc: the kernel's cotangent sums are a register array
 _JACOBIAN_ROUTE = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
 _METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
@@ -948,16 +948,21 @@ _BIAS_OPES_FEATURES_ROUTE = ("use `module(x)` on an x that requires grad, form t
 _HILLS_AND_OPES_ROUTE = ("`hills` and `opes` in one launch are not served: move the hills onto a table with `molann_amd.bias.add_hills_to_grid` and "
                          "pass it as `grid`, or make two calls (`value_and_bias` with the hills, `value_and_opes` or `value_and_bias` with `opes`) "
                          "and add their dx")
+# value_and_opes_table (_OPES_TABLE): value_and_opes on an `OpesTable` whose state the kernel reads; what remains where it refuses
+_OPES_TABLE_ROUTE = "read the table's state (`OpesTable.read_state`), then `value_and_opes` on `table.record(scale, S / n, epsilon)`, or: " + _OPES_ROUTE
+_OPES_TABLE_FEATURES_ROUTE = ("read the table's state (`OpesTable.read_state`), then `value_and_opes` on `table.record(scale, S / n, epsilon)`, or: "
+                              + _OPES_FEATURES_ROUTE)
 _ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint", "value_and_hills", "value_and_grid",
-                    "value_and_bias", "value_and_opes", "value_and_bias")
+                    "value_and_bias", "value_and_opes", "value_and_bias", "value_and_opes_table")
 # the route that remains where the call refuses
-_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE, _BIAS_ROUTE, _OPES_ROUTE, _BIAS_OPES_ROUTE)
+_ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE, _BIAS_ROUTE, _OPES_ROUTE, _BIAS_OPES_ROUTE,
+                     _OPES_TABLE_ROUTE)
 _ONE_LAUNCH_FEATURES_ROUTE = (None, None, None, _RESTRAINT_FEATURES_ROUTE, _HILLS_FEATURES_ROUTE, _GRID_FEATURES_ROUTE, _BIAS_FEATURES_ROUTE,
-                              _OPES_FEATURES_ROUTE, _BIAS_OPES_FEATURES_ROUTE)
+                              _OPES_FEATURES_ROUTE, _BIAS_OPES_FEATURES_ROUTE, _OPES_TABLE_FEATURES_ROUTE)
 _ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)", "(y, bias, dx)", "(y, energies, dx)", "(y, bias, dx)",
-                    "(y, energies, dx)")   # what `into` holds
+                    "(y, energies, dx)", "(y, bias, dx)")   # what `into` holds
 # the dispatcher operator, in MolANN._fast_state
-_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid", "op_bias", "op_opes", "op_bias_opes")
+_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid", "op_bias", "op_opes", "op_bias_opes", "op_opes_table")
 _BIAS_KINDS = (_RESTRAINT, _HILLS, _GRID)      # the calls that return (y, a scalar per frame, dx)
 
 
@@ -1094,6 +1099,35 @@ def _check_opes_args(name, x, out_dim, centers, heights, sigma, scale, norm, eps
         raise NotImplementedError("%s: the one-launch kernel serves at most %d outputs (got %d); %s" % (name, _HILLS_MAX_D_OUT, out_dim, _OPES_ROUTE))
     checked = _check_hills_args(name, x, out_dim, centers, heights, sigma, period, into, owner=owner)
     return checked[:4] + (scale, norm, epsilon, cutoff) + checked[4:]
+
+
+def _check_opes_table_args(name, x, out_dim, table, scale, epsilon, into, owner=None):
+    """The checks of value_and_opes_table, all before any launch on x's device and with nothing read back: `table` a
+    `molann_amd.bias.OpesTable` (TypeError) with ``table.d == out_dim`` on x's device (ValueError), `scale` and `epsilon` as
+    `_check_opes_args` takes them, more than 8 outputs (NotImplementedError naming the route), `into`.  The widths are not looked at: they
+    are the deposits' and live in device memory.  Returns (centers, heights, sigma, state, period, scale, epsilon, cutoff, y, bias, dx) as
+    the kernel takes them, the cutoff and the period being the table's."""
+    if not isinstance(table, _bias.OpesTable):
+        raise TypeError("%s: `table` must be a molann_amd.bias.OpesTable; got %s" % (name, type(table).__name__))
+    vals = []
+    for what, v in (("scale", scale), ("epsilon", epsilon)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError("%s: `%s` must be a Python float; got %s" % (name, what, type(v).__name__))
+        vals.append(float(v))
+    scale, epsilon = vals
+    if not math.isfinite(scale):
+        raise ValueError("%s: `scale` must be finite; got %r" % (name, scale))
+    if not (math.isfinite(epsilon) and epsilon > 0.0):
+        raise ValueError("%s: `epsilon` must be finite and > 0; got %r" % (name, epsilon))
+    if out_dim > _HILLS_MAX_D_OUT:
+        raise NotImplementedError("%s: the one-launch kernel serves at most %d outputs (got %d); %s" % (name, _HILLS_MAX_D_OUT, out_dim, _OPES_ROUTE))
+    if table.d != out_dim:
+        raise ValueError("%s: `table` holds kernels of %d columns but the model has %d outputs" % (name, table.d, out_dim))
+    if table.centers.device != x.device:
+        raise ValueError("%s: `table` must be on %s; got %s" % (name, x.device, table.centers.device))
+    triple = _check_into_triple(name, x, into, out_dim, _HILLS)
+    return (table.centers, table.heights, table.sigma, table.state, table.period, scale, epsilon,
+            math.inf if table.cutoff is None else table.cutoff) + triple
 
 
 def _grid_floats(name, what, v, out_dim, unit="output"):
@@ -1298,6 +1332,9 @@ def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=
     elif kind == _OPES:
         checked = _check_opes_args(name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:8], checked[8], (checked[9], checked[10]) if checked[8] is not None else None, (n, n_inp, 3)
+    elif kind == _OPES_TABLE:
+        checked = _check_opes_table_args(name, x, out_dim, *extra, into, owner=owner)
+        return x, checked[:8], checked[8], (checked[9], checked[10]) if checked[8] is not None else None, (n, n_inp, 3)
     elif kind in _BIAS_KINDS:
         checked = (_check_restraint_args, _check_hills_args, _check_grid_args)[kind - _RESTRAINT](name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:4], checked[4], (checked[5], checked[6]) if checked[4] is not None else None, (n, n_inp, 3)
@@ -1317,6 +1354,9 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
         if kind == _OPES:
             if not plan.supports_value_and_opes_f64():
                 raise NotImplementedError("value_and_opes: one frame's rows exceed the LDS of a compute unit for this model; " + _OPES_ROUTE)
+        elif kind == _OPES_TABLE:
+            if not plan.supports_value_and_opes_table_f64():
+                raise NotImplementedError("value_and_opes_table: one frame's rows exceed the LDS of a compute unit for this model; " + _OPES_ROUTE)
         elif kind == _BIAS_OPES:
             if not plan.supports_value_and_bias_opes_f64():
                 raise NotImplementedError("value_and_bias: one frame's rows exceed the LDS of a compute unit for this model; " + _BIAS_OPES_ROUTE)
@@ -1337,7 +1377,7 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
         if y is None:
             y = torch.empty((x.shape[0], out_dim), dtype=torch.float64, device=x.device)
             second = torch.empty(shape, dtype=torch.float64, device=x.device)
-            if kind in _BIAS_KINDS or kind == _OPES:
+            if kind in _BIAS_KINDS or kind == _OPES or kind == _OPES_TABLE:
                 second = (torch.empty((x.shape[0],), dtype=torch.float64, device=x.device), second)
             if kind == _BIAS or kind == _BIAS_OPES:
                 second = (torch.empty((x.shape[0], 3 if kind == _BIAS else 4), dtype=torch.float64, device=x.device), second)
@@ -1365,6 +1405,11 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
             if x.shape[0] > 0:
                 plan.value_and_opes_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
                                         *extra, y, *second)
+            return (y,) + tuple(second)
+        if kind == _OPES_TABLE:
+            if x.shape[0] > 0:
+                plan.value_and_opes_table_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
+                                              *extra, y, *second)
             return (y,) + tuple(second)
         if kind == _GRID:
             if x.shape[0] > 0:
@@ -1490,8 +1535,15 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
         call."""
         return self._bias_on_features(_OPES, x, (centers, heights, sigma, scale, norm, epsilon, cutoff, period), into)
 
+    def value_and_opes_table(self, x, table, scale, epsilon, into=None):
+        """``(feat, bias, dx)``: `MolANN.value_and_opes_table` on the features themselves, float64, in ONE kernel launch
+        (`molann_value_and_opes_table_f64`, frames_value_opes_table_f64_kernel, on this module's float64 feature plan; no head):
+        `value_and_opes` on a `molann_amd.bias.OpesTable` whose live count and normalisation the kernel reads from the table's state
+        in device memory, so nothing is read back.  The arguments as `MolANN.value_and_opes_table` takes them; ``table.d`` features."""
+        return self._bias_on_features(_OPES_TABLE, x, (table, scale, epsilon), into)
+
     def _bias_on_features(self, kind, x, extra, into):
-        """value_and_restraint / value_and_hills / value_and_grid / value_and_bias / value_and_opes of this module: the gate, the checks and the ctypes plan of the features."""
+        """value_and_restraint / value_and_hills / value_and_grid / value_and_bias / value_and_opes / value_and_opes_table of this module: the gate, the checks and the ctypes plan of the features."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and self._fusable()):
             raise NotImplementedError("%s needs a FeatureLayer behind an AlignmentLayer or none, float64, on a HIP tensor; "
                                       "otherwise %s" % (_ONE_LAUNCH_NAME[kind], _ONE_LAUNCH_FEATURES_ROUTE[kind]))
@@ -1632,7 +1684,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
             return _one_launch_ctypes(kind, st["entry"](), x, extra, y, second, shape, out_dim, lins, al)
         op, ref = st[_ONE_LAUNCH_OP[kind]], _device_buffer(al.ref_x, x) if al is not None else st["no_ref"]
         W, B, into = [lin.weight for lin in lins], [lin.bias for lin in lins], list(into) if into is not None else []
-        if kind in _BIAS_KINDS or kind == _OPES:
+        if kind in _BIAS_KINDS or kind == _OPES or kind == _OPES_TABLE:
             return tuple(op(x, st["handle"], ref, W, B, *extra, into))
         if kind == _BIAS:
             r, h, g = extra
@@ -1735,11 +1787,29 @@ class MolANN(_PlanOwner, torch.nn.Module):
         ``into=(y, bias, dx)`` reuses the caller's buffers.  Every sum has a fixed order and every row of dx is stored once: the same
         bits on every call, whatever N.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at
         most 8 outputs (NotImplementedError beyond).  Out of scope: depositing, merging or compressing kernels and the update of Z
-        (between steps, on your own tensors: `molann_amd.bias.opes_kernel_sum` gives P at the kernel centres), float32, a
+        (between steps, on your own tensors: `molann_amd.bias.opes_kernel_sum` gives P at the kernel centres; on the device:
+        `molann_amd.bias.OpesTable`, and `value_and_opes_table` / `molann_amd.bias.OpesRun` for the whole loop), float32, a
         `GraphedForces` replay of this launch, neighbour lists, gradients with respect to the table or the parameters.  OPES on some of
         a wider model's outputs, or together with walls or a table: `value_and_bias` with ``opes=``."""
         return self._one_launch_f64(_OPES, self._one_launch_state(x, _OPES, "float64"), x,
                                     (centers, heights, sigma, scale, norm, epsilon, cutoff, period), into)
+
+    def value_and_opes_table(self, x, table, scale, epsilon, into=None):
+        """``(y, bias, dx)``: `value_and_opes` on a `molann_amd.bias.OpesTable`, with the live count and the normalisation read by the
+        kernel from the table's state in device memory - ``n = state[0]`` held to ``[0, capacity]`` and ``norm = S / n = state[1] /
+        state[0]``, OPES' ``Z kde_norm`` - instead of passed by value, float64, in ONE kernel launch
+        (`molann_value_and_opes_table_f64`, frames_value_opes_table_f64_kernel).  Nothing is read back and nothing about the table is
+        baked into the launch, so a bias and a deposit (`OpesTable.deposit`, `molann_amd.bias.OpesRun.deposit`) queue back to back
+        step after step, and the pair can be captured once in a ``torch.cuda.graph`` and replayed while the table grows.  For the same
+        n and norm, ``y``, ``bias`` and ``dx`` are `value_and_opes`' on ``table.record(scale, S / n, epsilon)``, bit for bit.
+        ``table``: an `OpesTable` with ``table.d == d_out`` on x's device; its ``cutoff``, ``period`` and capacity are used.
+        ``scale`` finite and ``epsilon`` finite and > 0, Python floats, else ValueError before any launch.  An empty table (the first
+        step of a run): ``bias = scale log(epsilon)`` and dx zeros, and nothing of the table is read.  A state whose S is not finite
+        and > 0 while n >= 1 gives NaN or inf for every frame: it is not guarded (`OpesTable.recompute_sum` restores S).  A NaN frame
+        poisons its own outputs only.  No autograd graph is recorded; ``into=(y, bias, dx)`` reuses the caller's buffers.  The same
+        bits on every call.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at most 8
+        outputs.  Out of scope: `value_and_bias` with ``opes=`` reading the state, float32, a `GraphedForces` wrapper."""
+        return self._one_launch_f64(_OPES_TABLE, self._one_launch_state(x, _OPES_TABLE, "float64"), x, (table, scale, epsilon), into)
 
     def value_and_grid(self, x, table, lower, spacing, periodic=None, into=None):
         """``(y, bias, dx)`` with ``y = self(x)`` [N, d_out], a bias interpolated from a table over it, ``bias[f] = V(y[f])`` [N], and
@@ -1866,6 +1936,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
                 st["op_restraint"], st["op_hills"] = torch.ops.molann.value_and_restraint_h, torch.ops.molann.value_and_hills_h
                 st["op_grid"], st["op_bias"] = torch.ops.molann.value_and_grid_h, torch.ops.molann.value_and_bias_h
                 st["op_opes"], st["op_bias_opes"] = torch.ops.molann.value_and_opes_h, torch.ops.molann.value_and_bias_opes_h
+                st["op_opes_table"] = torch.ops.molann.value_and_opes_table_h
                 from . import script
                 st["desc"] = script.make_desc(script.KIND_FORWARD, fl.input_atom_num,
                                               align_idx=al._local_align_atom_indices if al is not None else None,

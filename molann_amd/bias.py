@@ -9,7 +9,9 @@ with `add_hills_to_grid`: deposit each new hill onto the table and call `value_a
 An OPES run (`MolANN.value_and_opes`) keeps its kernel table on the device in an `OpesTable`: `deposit` compresses new kernels into it and
 keeps the sum its normalisation Z is formed from, in one launch and with no read-back; `kernel_sum` gives the kernel density at any
 points; `record` hands the live rows to `value_and_opes` / `value_and_bias` as an `Opes` record.  `opes_kernel_sum` is the same density
-in plain torch, differentiable by autograd.  With walls or a table next to it, or on some of a wider model's outputs, the kernel table
+in plain torch, differentiable by autograd.  An `OpesRun` is the whole loop on the device: `bias` evaluates the model and the bias from the
+table's state (`MolANN.value_and_opes_table`), `deposit` turns those outputs into the step's kernels and deposits them - two launches
+per step, nothing read back, capturable in a graph.  With walls or a table next to it, or on some of a wider model's outputs, the kernel table
 goes into `MolANN.value_and_bias` as an `Opes` record."""
 
 import collections
@@ -18,7 +20,7 @@ import operator
 
 import torch
 
-__all__ = ["grid_points", "add_hills_to_grid", "opes_kernel_sum", "Restraint", "Hills", "Grid", "Opes", "OpesTable"]
+__all__ = ["grid_points", "add_hills_to_grid", "opes_kernel_sum", "Restraint", "Hills", "Grid", "Opes", "OpesTable", "OpesRun"]
 
 HILLS_MAX_COLUMNS = 8     # HILLS_MAX_D of csrc/molann_math.h
 GRID_MAX_COLUMNS = 3      # GRID_MAX_D of csrc/molann_math.h
@@ -190,7 +192,8 @@ class OpesTable(object):
 
     ``centers`` [capacity, d], ``sigma`` [capacity, d] and ``heights`` [capacity] hold the kernels, rows ``>= n`` are dead storage;
     ``state`` [4] holds ``(n, S, merges, refused)`` with ``S = sum_{i<n} sum_{j<n} heights_j K_j(centers_i)``, the sum OPES normalises
-    with (``Z = S / (n * kde_norm)`` is the caller's, like ``kde_norm``, ``neff`` and the bandwidth rescaling: a few scalars).
+    with (``Z = S / (n * kde_norm)``, so the ``norm`` of `value_and_opes` is ``S / n``; `MolANN.value_and_opes_table` reads it from
+    here on the device, and `OpesRun` keeps ``neff`` and the bandwidth rescaling there too).
     ``period``: None or [d] (> 0: that output is periodic); ``cutoff``: None (no cutoff) or > 0, in widths; ``threshold``: a new kernel
     closer than this many widths to a live one is merged into it (0: every kernel is appended).  1 <= d <= 8; a CUDA / HIP device."""
 
@@ -288,3 +291,97 @@ class OpesTable(object):
         and `value_and_bias(opes=...)`.  ``n``: the live count where the caller has it; None reads the state."""
         n = self.read_state()[0] if n is None else operator.index(n)
         return Opes(self.centers[:n], self.heights[:n], self.sigma[:n], scale, norm, epsilon, self.cutoff, self.period, columns)
+
+
+def _positive(name, what, v, allow_inf=False):
+    """A scalar of OpesRun's constructor: a Python number (TypeError), finite - or +inf where allowed - and > 0 (ValueError)."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TypeError("%s: `%s` must be a Python float; got %s" % (name, what, type(v).__name__))
+    v = float(v)
+    if not (v > 0.0 and (math.isfinite(v) or (allow_inf and v == math.inf))):
+        raise ValueError("%s: `%s` must be %s and > 0; got %r" % (name, what, "finite or +inf" if allow_inf else "finite", v))
+    return v
+
+
+class OpesRun(object):
+    """A whole OPES run (PLUMED's ``OPES_METAD`` with a fixed ``sigma0``; not the explore variant) on the device: two launches per
+    step and nothing read back, so the loop queues ahead of the device and can be captured in one ``torch.cuda.graph``.
+
+    ``bias(x)`` is `MolANN.value_and_opes_table` on the table's current state; ``deposit(y, bias)`` is `molann_opes_step_f64` on the
+    outputs that call wrote: per walker ``w = exp(bias / kT)``, the running sums ``counter``, ``sum_w``, ``sum_w2``,
+    ``neff = (1 + sum_w)^2 / (1 + sum_w2)``, ``rct = kT log(sum_w / counter)``, the widths ``sigma0 * sigma_scale`` with
+    ``sigma_scale = (neff (d + 2) / 4)^(-1 / (d + 4))`` (1 with ``fixed_sigma``) held above ``sigma_min``, the heights
+    ``w prod_k(sigma0_k / sigma_k)``, and the deposit of the W kernels into ``table`` as `OpesTable.deposit` makes it.  ``run`` [8] on
+    the table's device holds ``(counter, sum_w, sum_w2, neff, sigma_scale, rct, 0, 0)``.
+
+    ``model``: a `MolANN` (or `PreprocessingANN`) whose outputs are the table's ``d`` columns; ``table``: an `OpesTable` (its
+    ``period``, ``cutoff`` and ``threshold`` are used); ``kT`` > 0; ``biasfactor`` > 1 (+inf: ``scale = kT``); ``barrier`` > 0:
+    ``scale = kT (1 - 1 / biasfactor)``, ``epsilon = exp(-barrier / scale)``, ``beta = 1 / kT``.  ``sigma0``, ``sigma_min``: [d]
+    numbers or tensors, finite and > 0 (checked here, once: on the device a width that is not > 0 makes every kernel of a step
+    invalid and refused).  A walker whose bias or outputs are not finite is counted in the table's ``refused`` and changes nothing
+    else.  Out of scope: adaptive sigma, explore mode, walkers on several ranks, float32, a `GraphedForces` wrapper."""
+
+    def __init__(self, model, table, kT, biasfactor, barrier, sigma0, sigma_min=None, fixed_sigma=False):
+        if not callable(getattr(model, "value_and_opes_table", None)):
+            raise TypeError("OpesRun: `model` must be a MolANN or a PreprocessingANN (it has no `value_and_opes_table`); got %s"
+                            % type(model).__name__)
+        if not isinstance(table, OpesTable):
+            raise TypeError("OpesRun: `table` must be an OpesTable; got %s" % type(table).__name__)
+        kT = _positive("OpesRun", "kT", kT)
+        biasfactor = _positive("OpesRun", "biasfactor", biasfactor, allow_inf=True)
+        barrier = _positive("OpesRun", "barrier", barrier)
+        if not biasfactor > 1.0:
+            raise ValueError("OpesRun: `biasfactor` must be > 1; got %r" % (biasfactor,))
+        if not isinstance(fixed_sigma, (bool, int)):
+            raise TypeError("OpesRun: `fixed_sigma` must be a bool; got %s" % type(fixed_sigma).__name__)
+        scale = kT * (1.0 - 1.0 / biasfactor)
+        epsilon = math.exp(-barrier / scale)
+        if not epsilon > 0.0:
+            raise ValueError("OpesRun: exp(-barrier / (kT (1 - 1 / biasfactor))) underflows to 0 for barrier %r; lower the barrier" % (barrier,))
+        rows = []
+        for what, v in (("sigma0", sigma0), ("sigma_min", sigma_min)):
+            if v is None and what == "sigma_min":
+                rows.append(None)
+                continue
+            try:
+                host = v.detach().to(device="cpu", dtype=torch.float64) if isinstance(v, torch.Tensor) else torch.as_tensor(v, dtype=torch.float64)
+            except (TypeError, ValueError, RuntimeError):
+                raise TypeError("OpesRun: `%s` must be a tensor or a sequence of %d numbers; got %s" % (what, table.d, type(v).__name__))
+            if host.shape != (table.d,):
+                raise ValueError("OpesRun: `%s` must be [%d]; got %s" % (what, table.d, list(host.shape)))
+            if not bool((torch.isfinite(host) & (host > 0)).all()):
+                raise ValueError("OpesRun: `%s` holds widths and must be finite and > 0 everywhere" % what)
+            rows.append(host)
+        self.model, self.table = model, table
+        self.kT, self.biasfactor, self.barrier, self.fixed_sigma = kT, biasfactor, barrier, bool(fixed_sigma)
+        self.scale, self.epsilon, self.beta = scale, epsilon, 1.0 / kT
+        self.sigma0 = rows[0].to(table.centers.device).contiguous()
+        self.sigma_min = None if rows[1] is None else rows[1].to(table.centers.device).contiguous()
+        self.run = torch.zeros(8, dtype=torch.float64, device=table.centers.device)
+
+    def bias(self, x, into=None):
+        """``(y, bias, dx)`` of the walkers ``x`` under the table as it is now: `MolANN.value_and_opes_table`, one launch."""
+        return self.model.value_and_opes_table(x, self.table, self.scale, self.epsilon, into=into)
+
+    def deposit(self, y, bias):
+        """The step after `bias`: ``y`` [W, d] and ``bias`` [W] as that call returned them (read only).  One launch on the current
+        stream, nothing read back, returns None."""
+        from . import _capi
+        t = self.table
+        if not (isinstance(y, torch.Tensor) and y.dim() == 2):
+            raise ValueError("OpesRun.deposit: `y` must be a [W, %d] tensor" % t.d)
+        n_walkers = y.shape[0]
+        y = t._tensor("deposit: `y`", y, [(n_walkers, t.d)], "[W, %d]" % t.d).contiguous()
+        bias = t._tensor("deposit: `bias`", bias, [(n_walkers,)], "[W]").contiguous()
+        if n_walkers == 0:
+            return None
+        with torch.cuda.device(t.centers.device):
+            _capi.opes_step_f64(t.centers, t.sigma, t.heights, t.state, self.run, t.period, y, bias, self.sigma0, self.sigma_min, self.beta,
+                                t.threshold, t.cutoff, self.fixed_sigma)
+        return None
+
+    def read_run(self):
+        """``run`` as a dict of Python numbers (``counter``, ``sum_w``, ``sum_w2``, ``neff``, ``sigma_scale``, ``rct``): the one 64-byte
+        read-back (it waits for the steps queued before it)."""
+        counter, sum_w, sum_w2, neff, sigma_scale, rct = self.run.tolist()[:6]
+        return dict(counter=int(counter), sum_w=sum_w, sum_w2=sum_w2, neff=neff, sigma_scale=sigma_scale, rct=rct)

@@ -1,9 +1,9 @@
 // molann_dev_opes_deposit_f64.inc - part of libmolann_hip.so, included by molann_kernels.hip after molann_dev_bias_opes_f64.inc.  The other
 // half of an OPES run, between the steps that molann_value_and_opes_f64 serves: opes_deposit_f64_kernel compresses new kernels into a
 // device-resident table in place and keeps the sum S its normalisation is formed from (molann_opes_deposit_f64 launches it), and
-// opes_kernel_sum_f64_kernel gives the kernel density at arbitrary points (molann_opes_kernel_sum_f64).  Out of scope: the scalar
-// bookkeeping of OPES (kde_norm, neff, the bandwidth rescaling, Z from S: a few scalars of the caller's); deposits on more than one
-// block; neighbour lists; float32.
+// opes_kernel_sum_f64_kernel gives the kernel density at arbitrary points (molann_opes_kernel_sum_f64).  The scalar bookkeeping of OPES
+// (neff, the bandwidth rescaling, the heights) on the device and the bias that reads this state: molann_dev_opes_table_f64.inc.  Out of
+// scope: deposits on more than one block; neighbour lists; float32.
 namespace {
 
 // =============================================================================================

@@ -799,6 +799,96 @@ MOLANN_HD void opes_deposit_steps_f64(Ex& ex, long capacity, int d, const double
     }
 }
 
+// The scalar arithmetic of a whole OPES step (opes_step_f64_kernel and its host twin; OPES_METAD's update with a fixed sigma0, not the
+// explore variant), on run[8] = (counter, sum_w, sum_w2, neff, sigma_scale, rct, 0, 0).  Nothing is contracted, so the host and the
+// device round alike up to exp, log and pow.
+//
+// opes_table_norm_f64: the `norm` of opes_transform_f64 from a table's state, Z kde_norm = S / n (Z = S / (n kde_norm)).  n >= 1.
+MOLANN_HD double opes_table_norm_f64(double S, long n) {
+    return S / (double)n;
+}
+
+// opes_walker_weight_f64: w = exp(beta V) of one walker, and whether the walker counts: V, w and every y_k finite and w > 0 (a NaN
+// fails every comparison; an exp that overflows, or underflows to 0, fails too).
+MOLANN_HD bool opes_walker_weight_f64(double beta, double V, const double* y, int d, double& w) {
+#pragma clang fp contract(off)
+    w = exp(beta * V);
+    bool ok = fabs(V) <= 1.7976931348623157e308 && w > 0.0 && w <= 1.7976931348623157e308;
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k)
+        if (k < d) ok = ok && fabs(y[k]) <= 1.7976931348623157e308;
+    return ok;
+}
+
+// one valid walker into a thread's three partial sums
+MOLANN_HD void opes_walker_add_f64(double w, double& count, double& sum_w, double& sum_w2) {
+#pragma clang fp contract(off)
+    const double w2 = w * w;
+    count = count + 1.0;
+    sum_w = sum_w + w;
+    sum_w2 = sum_w2 + w2;
+}
+
+// opes_run_scalars_f64: neff = (1 + sum_w)^2 / (1 + sum_w2), rct = log(sum_w / counter) / beta (0 while counter == 0) and the
+// bandwidth rescaling sigma_scale = (neff (d + 2) / 4)^(-1 / (d + 4)) (Silverman's rule on the effective sample size; 1 with
+// `fixed_sigma`), from the sums after this step's walkers.
+MOLANN_HD void opes_run_scalars_f64(double counter, double sum_w, double sum_w2, double beta, int d, int fixed_sigma, double& neff,
+                                    double& sigma_scale, double& rct) {
+#pragma clang fp contract(off)
+    const double a = 1.0 + sum_w;
+    neff = (a * a) / (1.0 + sum_w2);
+    rct = counter > 0.0 ? log(sum_w / counter) / beta : 0.0;
+    const double dd = (double)d;
+    sigma_scale = fixed_sigma ? 1.0 : pow((neff * (dd + 2.0)) / 4.0, -1.0 / (dd + 4.0));
+}
+
+// opes_step_widths_f64: the widths of this step's kernels, sigma_k = sigma0_k sigma_scale raised to sigma_min_k where sigma_min is
+// given (sigma_k < sigma_min_k: a NaN stays), the same for every walker.  Returns prod_k (sigma0_k / sigma_k), k ascending: what a
+// kernel's height gains where its width was held up, so that its integral stays its weight.
+MOLANN_HD double opes_step_widths_f64(const double* sigma0, const double* sigma_min, double sigma_scale, int d, double (&sigma)[HILLS_MAX_D]) {
+#pragma clang fp contract(off)
+    double ratio = 1.0;
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k) {
+        sigma[k] = 1.0;
+        if (k < d) {
+            double s = sigma0[k] * sigma_scale;
+            if (sigma_min && s < sigma_min[k]) s = sigma_min[k];
+            sigma[k] = s;
+            ratio = ratio * (sigma0[k] / s);
+        }
+    }
+    return ratio;
+}
+
+// the height of walker a's kernel: w_a ratio, or NaN for a walker that does not count - opes_kernel_valid_f64 refuses it
+MOLANN_HD double opes_walker_height_f64(double beta, double V, const double* y, int d, double ratio) {
+#pragma clang fp contract(off)
+    double w;
+    const bool ok = opes_walker_weight_f64(beta, V, y, d, w);
+    return ok ? w * ratio : __builtin_nan("");
+}
+
+// The step itself, one copy for the device and the host: `ex` is a deposit executor (opes_deposit_steps_f64) that also gives the
+// step's three sums over the valid walkers in their fixed order (walker_sums) and whose load_new(a) yields (y[a], ex.step_sigma,
+// opes_walker_height_f64 with ex.ratio).  In order: the sums join run[0..2]; the scalars; the widths; the deposit of the W kernels.
+template <class Ex>
+MOLANN_HD void opes_step_steps_f64(Ex& ex, long capacity, int d, const double* period, long n_walkers, double threshold, double cutoff,
+                                   double beta, int fixed_sigma, const double* sigma0, const double* sigma_min, long& n, double& S,
+                                   double& merges, double& refused, double (&run)[8]) {
+#pragma clang fp contract(off)
+    double count, sum_w, sum_w2;
+    ex.walker_sums(n_walkers, count, sum_w, sum_w2);
+    run[0] = run[0] + count;
+    run[1] = run[1] + sum_w;
+    run[2] = run[2] + sum_w2;
+    opes_run_scalars_f64(run[0], run[1], run[2], beta, d, fixed_sigma, run[3], run[4], run[5]);
+    run[6] = 0.0;
+    run[7] = 0.0;
+    ex.ratio = opes_step_widths_f64(sigma0, sigma_min, run[4], d, ex.step_sigma);
+    opes_deposit_steps_f64(ex, capacity, d, period, n_walkers, threshold, cutoff, n, S, merges, refused);
+}
+
 // A bias tabulated on a regular grid over d <= GRID_MAX_D outputs, interpolated by cubic convolution (Catmull-Rom): V(y) = sum over the
 // 4^d stencil points of T[idx_0 j0, ...] prod_k a_k jk, dV/dy_k the same sum with b_k jk in place of a_k jk.  grid_axis_f64 is one
 // axis' step: u = (y - lower) / h; periodic: u <- u - n floor(u / n), i = floor(u) held in [0, n - 1], idx_j = (i - 1 + j) mod n;

@@ -1,7 +1,8 @@
 // molann_opes_deposit_f64.inc - part of libmolann_hip.so, included by molann_kernels.hip after molann_value_f64.inc.  The host side of
 // molann_dev_opes_deposit_f64.inc (see include/molann_hip.h): molann_opes_deposit_f64 and molann_opes_kernel_sum_f64 check their
 // arguments and enqueue one launch each - no plan, no workspace, no event - and molann_selftest_opes_deposit_f64 runs the deposit on host
-// arrays through the same steps and the same per-kernel functions, with the device's order of every sum.
+// arrays through the same steps and the same per-kernel functions, with the device's order of every sum.  molann_opes_step_f64 (a whole
+// OPES step: opes_step_f64_kernel of molann_dev_opes_table_f64.inc) and its twin molann_selftest_opes_step_f64 follow the same pattern.
 namespace {
 
 // the device's block on the host: the same strided partials, the same butterfly, the same order of the four waves
@@ -49,7 +50,7 @@ struct OpesDepositHost {
                     double c0) const {
         double inv[HILLS_MAX_D];
         hill_inverse_widths_f64(se, d, inv);
-        double part[256], next[64];
+        double part[256];
         for (int t = 0; t < 256; ++t) {
             part[t] = 0.0;
             for (long i = t; i < n; i += 256) {
@@ -57,6 +58,11 @@ struct OpesDepositHost {
                 part[t] = part[t] + opes_pair_term_f64(ce, se, inv, he, centers + i * d, sigma + i * d, heights[i], period, c2, c0, d);
             }
         }
+        return block_sum(part);
+    }
+    // the block's sum of 256 partials: group_sum<64>'s butterfly in each wave, then ((w0 + w1) + w2) + w3
+    static double block_sum(double (&part)[256]) {
+        double next[64];
         for (int w = 0; w < 4; ++w)
             for (int m = 32; m >= 1; m >>= 1) {
                 for (int l = 0; l < 64; ++l) next[l] = part[64 * w + l] + part[64 * w + (l ^ m)];
@@ -65,6 +71,53 @@ struct OpesDepositHost {
         return ((part[0] + part[64]) + part[128]) + part[192];
     }
 };
+
+// opes_step_f64_kernel's executor on the host (OpesStepDev): the deposit's, the walkers' sums in the block's order, and the new kernels
+// formed from y, V and the step's widths
+struct OpesStepHost : OpesDepositHost {
+    const double* V;
+    double beta;
+    double ratio;
+    double step_sigma[HILLS_MAX_D];
+
+    void walker_sums(long n_walkers, double& count, double& sum_w, double& sum_w2) const {
+        double pc[256], pw[256], pw2[256];
+        for (int t = 0; t < 256; ++t) {
+            pc[t] = pw[t] = pw2[t] = 0.0;
+            for (long a = t; a < n_walkers; a += 256) {
+                double w;
+                if (opes_walker_weight_f64(beta, V[a], new_centers + a * d, d, w)) opes_walker_add_f64(w, pc[t], pw[t], pw2[t]);
+            }
+        }
+        count = block_sum(pc);
+        sum_w = block_sum(pw);
+        sum_w2 = block_sum(pw2);
+    }
+    void load_new(long a, double (&c)[HILLS_MAX_D], double (&s)[HILLS_MAX_D], double& h) const {
+        for (int k = 0; k < HILLS_MAX_D; ++k) {
+            c[k] = k < d ? new_centers[a * d + k] : 0.0;
+            s[k] = k < d ? step_sigma[k] : 1.0;
+        }
+        h = opes_walker_height_f64(beta, V[a], new_centers + a * d, d, ratio);
+    }
+};
+
+// the arguments molann_opes_step_f64 and its host twin share, in molann_opes_deposit_f64's order of refusals
+inline int opes_step_arguments(const double* centers, const double* sigma, const double* heights, int64_t capacity, int32_t d, const double* period,
+                               const double* state, const double* run, const double* y, const double* V, int64_t n_walkers, const double* sigma0,
+                               const double* sigma_min, double beta, double threshold, double cutoff) {
+    if (n_walkers > 0 && (!centers || !sigma || !heights || !state || !run || !y || !V || !sigma0)) return MOLANN_E_NULL;
+    if (((uintptr_t)centers | (uintptr_t)sigma | (uintptr_t)heights | (uintptr_t)period | (uintptr_t)state | (uintptr_t)run | (uintptr_t)y |
+         (uintptr_t)V | (uintptr_t)sigma0 | (uintptr_t)sigma_min) & 7)
+        return MOLANN_E_ALIGNMENT;
+    if (d < 1 || d > HILLS_MAX_D) return MOLANN_E_DESC;
+    if (capacity < 1) return MOLANN_E_DESC;
+    if (n_walkers < 0) return MOLANN_E_DESC;
+    if (!std::isfinite(beta) || !(beta > 0.0)) return MOLANN_E_DESC;
+    if (!std::isfinite(threshold) || threshold < 0.0) return MOLANN_E_DESC;
+    if (!(cutoff > 0.0)) return MOLANN_E_DESC;
+    return MOLANN_OK;
+}
 
 // the arguments molann_opes_deposit_f64 and its host twin share, in the order of the refusals
 inline int opes_deposit_arguments(const double* centers, const double* sigma, const double* heights, int64_t capacity, int32_t d,
@@ -108,6 +161,34 @@ int molann_selftest_opes_deposit_f64(double* centers, double* sigma, double* hei
     double S = state[1], merges = state[2], refused = state[3];
     opes_deposit_steps_f64(ex, (long)capacity, (int)d, period, (long)n_new, threshold, cutoff, n, S, merges, refused);
     state[0] = (double)n; state[1] = S; state[2] = merges; state[3] = refused;
+    return MOLANN_OK;
+}
+
+int molann_opes_step_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state, double* run,
+                         const double* y, const double* V, int64_t n_walkers, const double* sigma0, const double* sigma_min, double beta,
+                         double threshold, double cutoff, int32_t fixed_sigma, molann_stream_t stream) {
+    const int e = opes_step_arguments(centers, sigma, heights, capacity, d, period, state, run, y, V, n_walkers, sigma0, sigma_min, beta, threshold,
+                                      cutoff);
+    if (e != MOLANN_OK || n_walkers == 0) return e;
+    hipLaunchKernelGGL(opes_step_f64_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, centers, sigma, heights, (long)capacity, (int)d, period, state,
+                       run, y, V, (long)n_walkers, sigma0, sigma_min, beta, threshold, cutoff, fixed_sigma != 0 ? 1 : 0);
+    return (int)hipGetLastError();
+}
+
+int molann_selftest_opes_step_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
+                                  double* run, const double* y, const double* V, int64_t n_walkers, const double* sigma0, const double* sigma_min,
+                                  double beta, double threshold, double cutoff, int32_t fixed_sigma) {
+    const int e = opes_step_arguments(centers, sigma, heights, capacity, d, period, state, run, y, V, n_walkers, sigma0, sigma_min, beta, threshold,
+                                      cutoff);
+    if (e != MOLANN_OK || n_walkers == 0) return e;
+    OpesStepHost ex = {{centers, sigma, heights, period, y, nullptr, nullptr, (int)d}, V, beta, 1.0, {1., 1., 1., 1., 1., 1., 1., 1.}};
+    long n = opes_live_count_f64(state[0], (long)capacity);
+    double S = state[1], merges = state[2], refused = state[3];
+    double r[8] = {run[0], run[1], run[2], 0., 0., 0., 0., 0.};
+    opes_step_steps_f64(ex, (long)capacity, (int)d, period, (long)n_walkers, threshold, cutoff, beta, fixed_sigma != 0 ? 1 : 0, sigma0, sigma_min, n, S,
+                        merges, refused, r);
+    state[0] = (double)n; state[1] = S; state[2] = merges; state[3] = refused;
+    for (int i = 0; i < 8; ++i) run[i] = r[i];
     return MOLANN_OK;
 }
 

@@ -1121,6 +1121,121 @@ void opes_deposit_hip(at::Tensor centers_in, at::Tensor sigma_in, at::Tensor hei
           "molann_opes_deposit_f64");
 }
 
+// {out, bias, grad_x}: value_and_opes on a table whose live count and normalisation the kernel reads from `state` [4] in device memory
+// (molann_value_and_opes_table_f64): centers [capacity, out_dim], heights [capacity], sigma [capacity, out_dim] are the table's storage,
+// contiguous float64 on x's device and read where they are (no copy: a later deposit writes them); scale, epsilon and cutoff (inf: none)
+// are host values, checked here as the C entry checks them.  `into`: none or {out, bias, grad_x}.
+std::vector<at::Tensor> value_and_opes_table_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                                  const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                                                  const at::Tensor& centers_in, const at::Tensor& heights_in, const at::Tensor& sigma_in,
+                                                  const at::Tensor& state_in, const c10::optional<at::Tensor>& period_in, double scale, double epsilon,
+                                                  double cutoff, const std::vector<at::Tensor>& into) {
+    const char* const op = "molann::value_and_opes_table";
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_opes_table is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_opes_table: a forward or a features description");
+    TORCH_CHECK_VALUE(std::isfinite(scale) && std::isfinite(epsilon) && epsilon > 0.0 && cutoff > 0.0,
+                      "molann::value_and_opes_table: `scale` must be finite, `epsilon` finite and > 0, `cutoff` > 0 (inf: none); got ", scale, ", ",
+                      epsilon, ", ", cutoff);
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    TORCH_CHECK_VALUE(centers_in.dim() == 2 && centers_in.size(0) >= 1 && centers_in.size(1) == cols,
+                      "molann::value_and_opes_table: `centers` must be [capacity >= 1, out_dim]");
+    const int64_t cap = centers_in.size(0);
+    // `written`: the table is read where it lives, so it must be contiguous as it is
+    const at::Tensor centers = opes_tensor(op, "centers", centers_in, x, true, "[capacity, out_dim]", true);
+    const at::Tensor heights = opes_tensor(op, "heights", heights_in, x, heights_in.dim() == 1 && heights_in.size(0) == cap, "[capacity]", true);
+    const at::Tensor sigma = opes_tensor(op, "sigma", sigma_in, x, sigma_in.dim() == 2 && sigma_in.size(0) == cap && sigma_in.size(1) == cols,
+                                         "[capacity, out_dim]", true);
+    const at::Tensor state = opes_tensor(op, "state", state_in, x, state_in.dim() == 1 && state_in.size(0) == 4, "[4]", true);
+    at::Tensor period;
+    if (period_in.has_value() && period_in->defined())
+        period = opes_tensor(op, "period", *period_in, x, period_in->dim() == 1 && period_in->size(0) == cols, "[out_dim]", false);
+    TORCH_CHECK(into.empty() || into.size() == 3, "molann::value_and_opes_table: `into` must be a triple of tensors (out, bias, grad_x)");
+    at::Tensor out, bias, gx;
+    if (into.empty()) {
+        out = at::empty({n, cols}, x.options()); bias = at::empty({n}, x.options()); gx = at::empty_like(x);
+    } else {
+        out = into[0]; bias = into[1]; gx = into[2];
+        const int64_t counts[3] = {n * cols, n, x.numel()};
+        for (int i = 0; i < 3; ++i) {
+            TORCH_CHECK_TYPE(into[i].scalar_type() == at::kDouble, "molann::value_and_opes_table: `into` must be float64 like x");
+            TORCH_CHECK_VALUE(into[i].is_contiguous() && into[i].numel() == counts[i] && into[i].device() == x.device(),
+                              "molann::value_and_opes_table: `into` must be contiguous {[N, out_dim], [N], [N, n_inp, 3]} on x's device");
+        }
+    }
+    F64Linears lin;
+    f64_linears(op, *e, x, weights, biases, lin, ": call .double()");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_opes_table_f64(e->plan) == 1,
+                                "molann::value_and_opes_table: more than 8 outputs, or one frame's rows exceed the LDS of a compute unit for this "
+                                "model; use run, form the kernel sum, its logarithm and its derivative with torch, then value_and_vjp");
+    if (n == 0) return {out, bias, gx};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_opes_table_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), centers.data_ptr<double>(),
+                                          heights.data_ptr<double>(), sigma.data_ptr<double>(), cap, state.data_ptr<double>(),
+                                          period.defined() ? period.data_ptr<double>() : nullptr, scale, epsilon, cutoff, out.data_ptr<double>(),
+                                          bias.data_ptr<double>(), gx.data_ptr<double>(), stream),
+          "molann_value_and_opes_table_f64");
+    return {out, bias, gx};
+}
+std::vector<at::Tensor> value_and_opes_table_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                                 std::vector<at::Tensor> biases, const at::Tensor& centers, const at::Tensor& heights,
+                                                 const at::Tensor& sigma, const at::Tensor& state, const c10::optional<at::Tensor>& period, double scale,
+                                                 double epsilon, double cutoff, std::vector<at::Tensor> into) {
+    return value_and_opes_table_impl(x_in, desc, ref_x, weights, biases, centers, heights, sigma, state, period, scale, epsilon, cutoff, into);
+}
+std::vector<at::Tensor> value_and_opes_table_h_hip(const at::Tensor& x_in, int64_t handle, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
+                                                   std::vector<at::Tensor> biases, const at::Tensor& centers, const at::Tensor& heights,
+                                                   const at::Tensor& sigma, const at::Tensor& state, const c10::optional<at::Tensor>& period,
+                                                   double scale, double epsilon, double cutoff, std::vector<at::Tensor> into) {
+    return value_and_opes_table_impl(x_in, *desc_of(handle, "molann::value_and_opes_table_h"), ref_x, weights, biases, centers, heights, sigma, state,
+                                     period, scale, epsilon, cutoff, into);
+}
+
+// A whole OPES step after the bias launch (molann_opes_step_f64): this step's kernels are formed from y [W, d] and V [W] on the device and
+// compressed into the caller's table in place; `state` [4] and `run` [8] = (counter, sum_w, sum_w2, neff, sigma_scale, rct, 0, 0) are
+// updated, in ONE launch on the current stream; nothing is read back.  The table as opes_deposit takes it; sigma0 [d], sigma_min [d] or none.
+void opes_step_hip(at::Tensor centers_in, at::Tensor sigma_in, at::Tensor heights_in, at::Tensor state_in, at::Tensor run_in,
+                   const c10::optional<at::Tensor>& period_in, const at::Tensor& y_in, const at::Tensor& V_in, const at::Tensor& sigma0_in,
+                   const c10::optional<at::Tensor>& sigma_min_in, double beta, double threshold, double cutoff, bool fixed_sigma) {
+    const char* const op = "molann::opes_step";
+    TORCH_CHECK_VALUE(centers_in.dim() == 2 && centers_in.size(0) >= 1 && centers_in.size(1) >= 1 && centers_in.size(1) <= 8,
+                      "molann::opes_step: `centers` must be [capacity >= 1, 1 <= d <= 8]");
+    TORCH_CHECK_VALUE(std::isfinite(beta) && beta > 0.0 && std::isfinite(threshold) && threshold >= 0.0 && cutoff > 0.0,
+                      "molann::opes_step: `beta` must be finite and > 0, `threshold` finite and >= 0, `cutoff` > 0 (inf: none); got ", beta, ", ",
+                      threshold, ", ", cutoff);
+    const int64_t cap = centers_in.size(0), d = centers_in.size(1);
+    const at::Tensor centers = opes_tensor(op, "centers", centers_in, centers_in, true, "[capacity, d]", true);
+    const at::Tensor sigma = opes_tensor(op, "sigma", sigma_in, centers, sigma_in.dim() == 2 && sigma_in.size(0) == cap && sigma_in.size(1) == d,
+                                         "[capacity, d]", true);
+    const at::Tensor heights = opes_tensor(op, "heights", heights_in, centers, heights_in.dim() == 1 && heights_in.size(0) == cap, "[capacity]", true);
+    const at::Tensor state = opes_tensor(op, "state", state_in, centers, state_in.dim() == 1 && state_in.size(0) == 4, "[4]", true);
+    const at::Tensor run = opes_tensor(op, "run", run_in, centers, run_in.dim() == 1 && run_in.size(0) == 8, "[8]", true);
+    at::Tensor period, sigma_min;
+    if (period_in.has_value() && period_in->defined())
+        period = opes_tensor(op, "period", *period_in, centers, period_in->dim() == 1 && period_in->size(0) == d, "[d]", false);
+    const at::Tensor y = opes_tensor(op, "y", y_in, centers, y_in.dim() == 2 && y_in.size(1) == d, "[W, d]", false);
+    const int64_t n_walkers = y.size(0);
+    const at::Tensor V = opes_tensor(op, "V", V_in, centers, V_in.dim() == 1 && V_in.size(0) == n_walkers, "[W]", false);
+    const at::Tensor sigma0 = opes_tensor(op, "sigma0", sigma0_in, centers, sigma0_in.dim() == 1 && sigma0_in.size(0) == d, "[d]", false);
+    if (sigma_min_in.has_value() && sigma_min_in->defined())
+        sigma_min = opes_tensor(op, "sigma_min", *sigma_min_in, centers, sigma_min_in->dim() == 1 && sigma_min_in->size(0) == d, "[d]", false);
+    if (n_walkers == 0) return;
+    const c10::DeviceGuard guard(centers.device());
+    hipStream_t stream = c10::hip::getCurrentHIPStream(centers.get_device()).stream();
+    check(molann_opes_step_f64(centers.data_ptr<double>(), sigma.data_ptr<double>(), heights.data_ptr<double>(), cap, (int32_t)d,
+                               period.defined() ? period.data_ptr<double>() : nullptr, state.data_ptr<double>(), run.data_ptr<double>(),
+                               y.data_ptr<double>(), V.data_ptr<double>(), n_walkers, sigma0.data_ptr<double>(),
+                               sigma_min.defined() ? sigma_min.data_ptr<double>() : nullptr, beta, threshold, cutoff, fixed_sigma ? 1 : 0, stream),
+          "molann_opes_step_f64");
+}
+
 // {P} or {P, dP}: the kernel density of an OPES table at points [M, d] and, with `with_grad`, its derivative [M, d] in ONE launch
 // (molann_opes_kernel_sum_f64).  The table as value_and_opes takes it.
 std::vector<at::Tensor> opes_kernel_sum_hip(const at::Tensor& points_in, const at::Tensor& centers_in, const at::Tensor& heights_in,
@@ -1823,6 +1938,12 @@ TORCH_LIBRARY(molann, m) {
           "float cutoff, int[] grid_columns, Tensor? table, float[] lower, float[] spacing, bool[] periodic, Tensor[] into) -> Tensor[]");
     m.def("opes_deposit(Tensor(a!) centers, Tensor(b!) sigma, Tensor(c!) heights, Tensor(d!) state, Tensor? period, Tensor new_centers, "
           "Tensor new_sigma, Tensor new_heights, float threshold, float cutoff) -> ()");
+    m.def("value_and_opes_table_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor centers, Tensor heights, Tensor sigma, "
+          "Tensor state, Tensor? period, float scale, float epsilon, float cutoff, Tensor[] into) -> Tensor[]");
+    m.def("value_and_opes_table(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor centers, Tensor heights, Tensor sigma, "
+          "Tensor state, Tensor? period, float scale, float epsilon, float cutoff, Tensor[] into) -> Tensor[]");
+    m.def("opes_step(Tensor(a!) centers, Tensor(b!) sigma, Tensor(c!) heights, Tensor(d!) state, Tensor(e!) run, Tensor? period, Tensor y, Tensor V, "
+          "Tensor sigma0, Tensor? sigma_min, float beta, float threshold, float cutoff, bool fixed_sigma) -> ()");
     m.def("opes_kernel_sum(Tensor points, Tensor centers, Tensor heights, Tensor sigma, Tensor? period, float cutoff, bool with_grad) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
@@ -1861,6 +1982,9 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_bias_opes", value_and_bias_opes_hip);
     m.impl("value_and_bias_opes_h", value_and_bias_opes_h_hip);
     m.impl("opes_deposit", opes_deposit_hip);
+    m.impl("value_and_opes_table", value_and_opes_table_hip);
+    m.impl("value_and_opes_table_h", value_and_opes_table_h_hip);
+    m.impl("opes_step", opes_step_hip);
     m.impl("opes_kernel_sum", opes_kernel_sum_hip);
 }
 

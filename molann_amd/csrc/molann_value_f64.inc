@@ -5,9 +5,10 @@
 // (frames_value_restraint_f64_kernel, molann_dev_restraint_f64.inc), molann_value_and_hills_f64 (frames_value_hills_f64_kernel,
 // molann_dev_hills_f64.inc), molann_value_and_grid_f64 (frames_value_grid_f64_kernel, molann_dev_grid_f64.inc),
 // molann_value_and_bias_f64 (frames_value_bias_f64_kernel, molann_dev_bias_f64.inc), molann_value_and_opes_f64
-// (frames_value_opes_f64_kernel, molann_dev_opes_f64.inc) and molann_value_and_bias_opes_f64 (frames_value_bias_opes_f64_kernel,
-// molann_dev_bias_opes_f64.inc).  One argument front end, one launch and one dispatch over the lane group serve the nine; an entry names
-// its kernel, its pointers and its rows.
+// (frames_value_opes_f64_kernel, molann_dev_opes_f64.inc), molann_value_and_bias_opes_f64 (frames_value_bias_opes_f64_kernel,
+// molann_dev_bias_opes_f64.inc) and molann_value_and_opes_table_f64 (frames_value_opes_table_f64_kernel, molann_dev_opes_table_f64.inc).
+// One argument front end, one launch and one dispatch over the lane group serve the ten; an entry names its kernel, its pointers and
+// its rows.
 namespace {
 
 constexpr size_t VJP64_LDS_DEFAULT = 65536;    // dynamic LDS a launch may ask for as it is
@@ -96,6 +97,7 @@ inline void f64_entry_rows(const molann_plan* p, GridF64Args& a) { restraint64_r
 inline void f64_entry_rows(const molann_plan* p, BiasF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, OpesF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }   // the hills' rows, geometry and cap: F64_HILLS
 inline void f64_entry_rows(const molann_plan* p, BiasOpesF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }   // the bias' rows and geometry: F64_BIAS
+inline void f64_entry_rows(const molann_plan* p, OpesTableF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }   // as OpesF64Args: F64_HILLS
 
 // geometry for this entry: the forces' rows, the restraint's (the hills' and the grid's too), the bias' or the Jacobian's, and the
 // metric's, the hills' and the grid's caps on the outputs
@@ -234,6 +236,17 @@ inline double host_opes_f64(const double* y, int d, const double* centers, const
 // the four scalars of molann_value_and_opes_f64: scale finite; norm and epsilon finite and > 0; cutoff > 0, +inf for none (a NaN fails)
 inline bool opes_scalars_f64(double scale, double norm, double epsilon, double cutoff) {
     return std::isfinite(scale) && std::isfinite(norm) && norm > 0.0 && std::isfinite(epsilon) && epsilon > 0.0 && cutoff > 0.0;
+}
+// the three of them that molann_value_and_opes_table_f64 takes by value (its norm is formed on the device), by the same rules
+inline bool opes_table_scalars_f64(double scale, double epsilon, double cutoff) { return opes_scalars_f64(scale, 1.0, epsilon, cutoff); }
+
+// one frame's OPES bias on the host from a table's state: n and norm as frames_value_opes_table_f64_kernel forms them, a row of widths
+// per kernel
+inline double host_opes_table_f64(const double* y, int d, const double* centers, const double* heights, const double* sigma, int64_t capacity,
+                                  const double* state, const double* period, double scale, double epsilon, double cutoff, double* dy) {
+    const long n = opes_live_count_f64(state[0], (long)capacity);
+    const double norm = n > 0 ? opes_table_norm_f64(state[1], n) : 1.0;
+    return host_opes_f64(y, d, centers, heights, n, sigma, d, period, scale, norm, epsilon, cutoff, dy);
 }
 
 // one frame's interpolation on the host, the same way: returns V, dy[k < d] = dV/dy_k; NaN for a grid grid_geometry_f64 refuses
@@ -379,6 +392,23 @@ int molann_value_and_opes_f64(molann_plan* p, const double* x, int64_t n, const 
                             heights, sigma, period, out, bias, grad_x);
 }
 
+int molann_plan_supports_value_and_opes_table_f64(const molann_plan* p) { return molann_plan_supports_value_and_opes_f64(p); }
+
+int molann_value_and_opes_table_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b, const double* centers,
+                                    const double* heights, const double* sigma, int64_t capacity, const double* state, const double* period,
+                                    double scale, double epsilon, double cutoff, double* out, double* bias, double* grad_x, molann_stream_t stream) {
+    F64Call<OpesTableF64Args> c;
+    // the table has storage whatever its live count, which only the device knows: its three pointers and the state are required
+    const int e = f64_entry_arguments(p, F64_HILLS, n, {x, centers, heights, sigma, state, out, bias, grad_x}, {period}, W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    if (capacity < 1) return MOLANN_E_DESC;
+    if (!opes_table_scalars_f64(scale, epsilon, cutoff)) return MOLANN_E_DESC;
+    c.a.capacity = (long)capacity;
+    c.a.scale = scale; c.a.epsilon = epsilon; c.a.cutoff = cutoff;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_opes_table_f64_kernel, c.g.G), "frames_value_opes_table_f64_kernel", "opes from the table's state",
+                            p, c, stream, x, centers, heights, sigma, state, period, out, bias, grad_x);
+}
+
 int molann_plan_supports_value_and_grid_f64(const molann_plan* p) {
     if (!p) return MOLANN_E_NULL;
     return f64_entry_geometry(p, F64_GRID).ok ? 1 : 0;
@@ -505,6 +535,12 @@ double molann_selftest_opes_f64(const double* y, int d, const double* centers, c
                                 int64_t sigma_stride, const double* period, double scale, double norm, double epsilon, double cutoff, double* dy) {
     if (!y || d < 1 || d > HILLS64_MAX_D_OUT || n_kernels < 0 || (n_kernels > 0 && (!centers || !heights || !sigma))) return (double)NAN;
     return host_opes_f64(y, d, centers, heights, n_kernels, sigma, sigma_stride, period, scale, norm, epsilon, cutoff, dy);
+}
+
+double molann_selftest_opes_table_f64(const double* y, int d, const double* centers, const double* heights, const double* sigma, int64_t capacity,
+                                      const double* state, const double* period, double scale, double epsilon, double cutoff, double* dy) {
+    if (!y || d < 1 || d > HILLS64_MAX_D_OUT || capacity < 1 || !centers || !heights || !sigma || !state) return (double)NAN;
+    return host_opes_table_f64(y, d, centers, heights, sigma, capacity, state, period, scale, epsilon, cutoff, dy);
 }
 
 void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]) {
