@@ -193,7 +193,7 @@ def _item_atoms(cx, col=None):
 
 HEAD_ENTRIES = ("forward_packed", "forward_train", "backward_x", "backward_p", "backward_xp", "value_and_vjp", "forward_f64",
                 "value_and_vjp_f64", "value_and_jacobian_f64", "value_and_metric_f64", "value_and_restraint_f64", "value_and_hills_f64",
-                "value_and_grid_f64", "value_and_bias_f64")
+                "value_and_grid_f64", "value_and_bias_f64", "value_and_opes_f64", "value_and_bias_opes_f64", "value_and_opes_table_f64")
 FEATURE_OUT = {"features": "out", "features_f64": "out", "features_jvp": "out", "features_jvp_f64": "out", "forward_train": "features",
                "forward_f64": "work"}
 SCALARS = ("energy", "bias", "energies", "metric")

@@ -1,9 +1,12 @@
 """A non-finite frame changes no other frame, in every entry point of the C ABI and every kernel family (tests/isolation.py).
 
-The family table, the plans, the calls and the oracle are those of test_gpu_buffer_placement.py (imported, not copied), plus the two
-float64 entries that table lacks - molann_value_and_grid_f64 and molann_value_and_bias_f64, on small tables made the way their own
-test files make them (the grid from the REFERENCE's outputs, test_gpu_value_and_grid_f64._grid_from).  The grid entry takes at most
-three outputs: it runs on the cases whose head ends in 3.
+The family table, the plans, the calls and the oracle are those of test_gpu_buffer_placement.py (imported, not copied), plus the five
+float64 entries that table lacks - molann_value_and_grid_f64, molann_value_and_bias_f64, molann_value_and_opes_f64,
+molann_value_and_bias_opes_f64 and molann_value_and_opes_table_f64, on small tables made the way their own test files make them (the
+grid from the REFERENCE's outputs, test_gpu_value_and_grid_f64._grid_from; the OPES kernels on rows of the reference's outputs, a
+width of noise on each; the table entry's dead rows NaN, its state (n, S) with S summed on the host).  The grid entry takes at most
+three outputs: it runs on the cases whose head ends in 3; the OPES entries take at most eight: every head here.  The shared inputs of
+the OPES entries - the kernel table and, read by every block, the state - must come back from every launch bit for bit.
 
 Per case (family, frame size, head width), per entry and per poisonable input buffer of the entry:
 
@@ -41,6 +44,7 @@ import torch
 import isolation as iso
 import test_gpu_buffer_placement as bp
 import test_gpu_value_and_grid_f64 as vg
+import test_gpu_value_and_opes_f64 as vo
 from molann_amd import _capi
 from oracle import molann_oracle as mo
 from test_gpu_angular_edges import _wrapped
@@ -54,18 +58,22 @@ BASE = 251                              # seeded frames the dense batch repeats:
 N_FIRST = 20000                         # the dense phase's first guess; it grows to what the launch info asks for
 ONE_GB = 1 << 30
 GRID, BIAS = "value_and_grid_f64", "value_and_bias_f64"
-EXTRA = {"f64_small": {GRID: r"frames_value_grid_f64_kernel", BIAS: r"frames_value_bias_f64_kernel"},
-         "f64_mid": {GRID: r"frames_value_grid_f64_kernel", BIAS: r"frames_value_bias_f64_kernel"}}
+OPES, BIAS_OPES, OPES_TABLE = "value_and_opes_f64", "value_and_bias_opes_f64", "value_and_opes_table_f64"
+OPES_ENTRIES = (OPES, BIAS_OPES, OPES_TABLE)
+NEW = (GRID, BIAS) + OPES_ENTRIES       # the entries this file adds to the placement table's
+_EXTRA = {GRID: r"frames_value_grid_f64_kernel", BIAS: r"frames_value_bias_f64_kernel", OPES: r"frames_value_opes_f64_kernel",
+          BIAS_OPES: r"frames_value_bias_opes_f64_kernel", OPES_TABLE: r"frames_value_opes_table_f64_kernel"}
+EXTRA = {"f64_small": dict(_EXTRA), "f64_mid": dict(_EXTRA)}
 SMALL, DENSE = set(), {}                # (family, entry) that passed the small batch / {(family, entry): (N, rounds of the first kernel, chunk)}
 assert all({"v": 4, "tangent_out": 3}[k] - r - 1 == iso.frame_dim(k) for k, r in bp.ROW_DIMS.items()) and set(bp.ROW_DIMS) == set(iso.FRAME_DIM)
 
 
 def _patterns(cx):
-    extra = dict((e, p) for e, p in EXTRA.get(cx.family, {}).items() if e != GRID or cx.d_out <= 3)
+    extra = dict((e, p) for e, p in EXTRA.get(cx.family, {}).items() if (e != GRID or cx.d_out <= 3) and (e not in OPES_ENTRIES or cx.d_out <= 8))
     return dict(cx.patterns, **extra)
 
 
-# ---- the two entries the placement table lacks ---------------------------------------------------------------------------------------
+# ---- the five entries the placement table lacks ---------------------------------------------------------------------------------------
 _YREF = {}
 
 
@@ -92,16 +100,61 @@ def _tables(cx, entry):
 
 
 HILLS_COLUMNS, N_HILLS = [1, 0], 5
+N_KERNELS, CAPACITY, OPES_CUTOFF, OPES_EPS = 7, 12, 4.0, 1e-3
+
+
+def _opes_columns(cx, entry):
+    return list(HILLS_COLUMNS) if entry == BIAS_OPES else list(range(cx.d_out))
+
+
+def _opes_table(cx, entry):
+    """(columns, centers [K, d], heights [K], sigma [K, d], period [d], norm) of the entry's OPES term: K kernels on rows of the
+    reference's outputs, a width of noise on each, widths 0.3-0.6 of the outputs' spread, positive heights, column 0 periodic."""
+    cols = _opes_columns(cx, entry)
+    y = _y_ref(cx, entry)[:, cols]
+    g = torch.Generator().manual_seed(len(cols) + 17)
+    rand = lambda *shape: torch.rand(shape, generator=g, dtype=F64)       # noqa: E731
+    sigma = (0.3 + 0.3 * rand(N_KERNELS, len(cols))) * y.std(dim=0).clamp(min=1e-3)
+    centers = y[torch.arange(N_KERNELS) * 29 % y.shape[0]] + (rand(N_KERNELS, len(cols)) - 0.5) * sigma
+    heights = 0.2 + rand(N_KERNELS)
+    period = torch.zeros(len(cols), dtype=F64)
+    period[0] = 2.5
+    return cols, centers, heights, sigma, period, vo._norm(heights)
+
+
+def _opes_state(centers, heights, sigma, period):
+    """(n, S, 0, 0) of a table whose live rows are these: S = sum_i sum_j heights_j K_j(centers_i), on the host"""
+    total = float(vo._density(centers, centers, heights, sigma, period, OPES_CUTOFF)[0].sum())
+    return torch.tensor([float(centers.shape[0]), total, 0.0, 0.0], dtype=F64)
+
+
+def _dead_rows(t):
+    """the table tensor in a capacity of CAPACITY rows, the dead ones NaN"""
+    out = torch.full((CAPACITY,) + tuple(t.shape[1:]), float("nan"), dtype=F64)
+    out[:t.shape[0]] = t
+    return out
 
 
 def _entry2(cx, entry, n):
-    if entry not in (GRID, BIAS):
+    if entry not in NEW:
         return _entry(cx, entry, n)
     L, ni, do = _capi.lib(), cx.n_inp, cx.d_out
     lay, wn, bn = bp._layers(cx)
     WB = lambda p: (bp._ptr_array(p, wn), bp._ptr_array(p, bn))                    # noqa: E731
-    cols, table, shape, lower, spacing, periodic = _tables(cx, entry)
     x = ("x", "in", cx.x(n, entry))
+    if entry in (OPES, OPES_TABLE):
+        _, oc, oh, osig, operiod, norm = _opes_table(cx, entry)
+        outs = [("out", "out", (n, do)), ("bias", "out", (n,)), ("grad_x", "out", (n, ni, 3))]
+        if entry == OPES:
+            return [x] + lay + [("centers", "in", oc), ("heights", "in", oh), ("sigma", "in", osig), ("opes_period", "in", operiod)] + outs, \
+                lambda h, p, s: L.molann_value_and_opes_f64(h, p["x"], n, *WB(p), p["centers"], p["heights"], N_KERNELS, p["sigma"], do, p["opes_period"],
+                                                            vo.SCALE, norm, OPES_EPS, OPES_CUTOFF, p["out"], p["bias"], p["grad_x"], s), cx.plan
+        state = _opes_state(oc, oh, osig, operiod)
+        return [x] + lay + [("centers", "in", _dead_rows(oc)), ("heights", "in", _dead_rows(oh)), ("sigma", "in", _dead_rows(osig)), ("state", "in", state),
+                            ("opes_period", "in", operiod)] + outs, \
+            lambda h, p, s: L.molann_value_and_opes_table_f64(h, p["x"], n, *WB(p), p["centers"], p["heights"], p["sigma"], CAPACITY, p["state"],
+                                                              p["opes_period"], vo.SCALE, OPES_EPS, OPES_CUTOFF, p["out"], p["bias"], p["grad_x"], s), cx.plan
+    cols, table, shape, lower, spacing, periodic = _tables(cx, entry)
     if entry == GRID:
         sh, lo, sp = (ctypes.c_int64 * do)(*shape), (ctypes.c_double * do)(*lower), (ctypes.c_double * do)(*spacing)
         per = (ctypes.c_int32 * do)(*[int(v) for v in periodic])
@@ -110,6 +163,21 @@ def _entry2(cx, entry, n):
     center, kappa = cx.randn((n, do), entry, n, 3), 0.5 + cx.randn((do,), entry, n, 4).abs()
     period = torch.where(torch.arange(do) % 2 == 0, torch.full((do,), 2.5, dtype=F64), torch.zeros(do, dtype=F64))
     flat = 0.05 * (torch.arange(do) % 3).to(F64)
+    if entry == BIAS_OPES:
+        oc_cols, oc, oh, osig, operiod, norm = _opes_table(cx, entry)
+
+        def call_opes(h, p, s):
+            terms, keep = _capi.bias_terms_f64(("center", "kappa", "period", "flat", do), None, (cols, "table", shape, lower, spacing, periodic),
+                                               ptr=lambda name: p[name])
+            term, keep_o = _capi.opes_term_f64((oc_cols, "centers", "heights", "sigma", "opes_period", N_KERNELS, len(oc_cols), vo.SCALE, norm, OPES_EPS,
+                                                OPES_CUTOFF), ptr=lambda name: p[name])
+            rc = L.molann_value_and_bias_opes_f64(h, p["x"], n, *WB(p), ctypes.byref(terms), ctypes.byref(term), p["out"], p["energies"], p["grad_x"], s)
+            del keep, keep_o
+            return rc
+
+        return [x] + lay + [("center", "in", center), ("kappa", "in", kappa), ("period", "in", period), ("flat", "in", flat),
+                            ("centers", "in", oc), ("heights", "in", oh), ("sigma", "in", osig), ("opes_period", "in", operiod), ("table", "in", table),
+                            ("out", "out", (n, do)), ("energies", "out", (n, 4)), ("grad_x", "out", (n, ni, 3))], call_opes, cx.plan
     centers, heights = cx.randn((N_HILLS, 2), entry, n, 5), cx.randn((N_HILLS,), entry, n, 6)
     sigma = 0.5 + cx.randn((N_HILLS, 2), entry, n, 7).abs()
 
@@ -127,12 +195,20 @@ def _entry2(cx, entry, n):
 
 
 def _want2(cx, entry, data):
-    """bp._want, and the two new entries by float64 autograd of the formulas of include/molann_hip.h"""
-    if entry not in (GRID, BIAS):
+    """bp._want, and the five new entries by float64 autograd of the formulas of include/molann_hip.h"""
+    if entry not in NEW:
         return bp._want(cx, entry, data)
-    cols, table, shape, lower, spacing, periodic = _tables(cx, entry)
     xx = data["x"].double().clone().requires_grad_(True)
     y = cx.head.double()(mo.preprocessing_forward(xx, cx.items, False, cx.align, cx.ref))
+    if entry in OPES_ENTRIES:      # V_o = scale log(P / norm + epsilon), P the kernel sum under the cutoff; the table entry's norm is S / n
+        live = int(data["state"][0]) if entry == OPES_TABLE else N_KERNELS
+        norm = float(data["state"][1]) / live if entry == OPES_TABLE else _opes_table(cx, entry)[5]
+        kernels = tuple(data[k][:live] for k in ("centers", "heights", "sigma"))
+        v_o = vo._bias(y[:, _opes_columns(cx, entry)], kernels, data["opes_period"], norm, OPES_EPS, OPES_CUTOFF)
+        if entry != BIAS_OPES:
+            (gx,) = torch.autograd.grad(v_o.sum(), xx)
+            return {"out": y.detach(), "bias": v_o.detach(), "grad_x": gx}
+    cols, table, shape, lower, spacing, periodic = _tables(cx, entry)
     vgrid = vg._interp(y[:, cols], table, lower, spacing, periodic)[0]
     if entry == GRID:
         (gx,) = torch.autograd.grad(vgrid.sum(), xx)
@@ -140,6 +216,9 @@ def _want2(cx, entry, data):
     d = _wrapped(y - data["center"], data["period"])
     d = torch.where(d.abs() <= data["flat"], torch.zeros_like(d), torch.copysign(d.abs() - data["flat"], d))
     e_r = 0.5 * (data["kappa"] * d * d).sum(1)
+    if entry == BIAS_OPES:
+        (gx,) = torch.autograd.grad((e_r + vgrid + v_o).sum(), xx)
+        return {"out": y.detach(), "energies": torch.stack([e_r, torch.zeros_like(e_r), vgrid, v_o], 1).detach(), "grad_x": gx}
     dh = y[:, HILLS_COLUMNS].unsqueeze(1) - data["centers"].unsqueeze(0)
     v_h = (data["heights"] * torch.exp(-0.5 * ((dh / data["sigma"]) ** 2).sum(2))).sum(1)
     (gx,) = torch.autograd.grad((e_r + v_h + vgrid).sum(), xx)
@@ -149,7 +228,7 @@ def _want2(cx, entry, data):
 def _held(cx, entry, bufs, got, what, kept=None):
     """_against_oracle at that file's tolerances; the new entries bring their reference, and their energies - values, which that
     file's table does not know - are held to the float64 value bound 1e-10 max(1, |E|max) as well."""
-    if entry in (GRID, BIAS) and (kept is None or "want" not in kept):
+    if entry in NEW and (kept is None or "want" not in kept):
         kept = {} if kept is None else kept
         kept.update(want=_want2(cx, entry, dict((name, p.cpu().double()) for name, role, p in bufs if role == "in")), own=None)
     bad = _against_oracle(cx, entry, bufs, got, what, kept)
@@ -159,6 +238,14 @@ def _held(cx, entry, bufs, got, what, kept=None):
         if not err <= 1e-10:
             bad.append("%s energies: error %.3g over 1e-10" % (what, err))
     return bad
+
+
+def _shared_inputs_written(entry, bufs, views):
+    """The OPES entries' inputs that no frame owns - the kernel table, the state every block reads - that a launch changed"""
+    if entry not in OPES_ENTRIES:
+        return []
+    return ["%s: the shared input %s was written" % (entry, name) for name, role, payload in bufs
+            if role == "in" and name not in iso.PER_FRAME and not bp.pl.same_bits(views[name].cpu(), payload.to(views[name].dtype))]
 
 
 @contextlib.contextmanager
@@ -222,7 +309,7 @@ def _small(cx, entry, pattern):
     assert rc == 0, (what, rc, _capi.error_string(rc))
     assert re.search(pattern, info), (what, info, pattern)
     clean, kept = _outputs(bufs, views), {}
-    bad = _held(cx, entry, bufs, clean, what, kept)
+    bad = _held(cx, entry, bufs, clean, what, kept) + _shared_inputs_written(entry, bufs, views)
     bad += ["%s: clean %s is not finite" % (what, k) for k, v in clean.items() if not bool(torch.isfinite(v).all())]
     bad += ["%s: the reference's %s is not finite" % (what, k) for k, v in kept["want"].items() if not bool(torch.isfinite(v).all())]
     rc, _, _, views, _ = _launch(cx, entry, n, 0, spec, fresh=True)
@@ -243,12 +330,16 @@ def _small(cx, entry, pattern):
         targets.append(("x", dict(where, x=3 * lone + iso.COORD), lone))
     for buffer, where, atom in targets:
         masks = dict((v, iso.dependent_elements(cx, entry, atom, shapes, buffer, where[buffer], v)) for v in ("nan", "inf"))
+        if entry == BIAS_OPES:                               # the column of the hills, which this entry does not have, is 0.0
+            for m in masks.values():
+                m["energies"][1] = False
         for bad_set in BAD_SETS:
             tag = "%s, %s%s of frames %s poisoned" % (what, buffer, " (atom %d)" % atom if buffer == "x" else "", list(bad_set))
             data = iso.poison(inputs, bad_set, "mixed", where=where, only=(buffer,))
             rc, _, info2, views, _ = _launch(cx, entry, n, 0, (_with(bufs, data), call, plan), fresh=True)
             assert rc == 0 and info2 == info, (tag, rc, info2)
             got = _outputs(bufs, views)
+            bad += ["%s: %s" % (tag, c) for c in _shared_inputs_written(entry, _with(bufs, data), views)]
             keep = sorted(set(range(n)) - set(bad_set))
             if family in ATOMICS:
                 sub = {"want": dict((k, _rows(v.reshape(shapes[k]), k, keep)) for k, v in kept["want"].items()),
@@ -363,6 +454,7 @@ def _dense(cx, entry, pattern):
         rc, _, info, views, _ = _launch(cx, entry, n, 0, spec, fresh=True)
         assert rc == 0, (what, n, rc, _capi.error_string(rc))
         assert re.search(pattern, info), (what, info, pattern)
+        shared = _shared_inputs_written(entry, bufs, views)
         found, chunk, unread = _geometry(info, n, cx.dev)
         # a composite launch info cuts its parts short: a part without its geometry must still start with the name of a kernel the
         # table reads (that kernel has its own entry), and every part that names a geometry must have been read
@@ -393,7 +485,8 @@ def _dense(cx, entry, pattern):
     rc, _, info2, views, _ = _launch(cx, entry, n, 0, (_with(bufs, data), call, plan), fresh=True)
     assert rc == 0 and info2 == info, (what, rc, info2)
     got = dict((k, _rows(views[k], k, keep_t).clone()) for k in per_frame)
-    bad = ["%s: kept rows of %s are not finite" % (what, k) for k in per_frame if not bool(torch.isfinite(got[k]).all())]
+    bad = shared + _shared_inputs_written(entry, _with(bufs, data), views)
+    bad += ["%s: kept rows of %s are not finite" % (what, k) for k in per_frame if not bool(torch.isfinite(got[k]).all())]
     if family in ATOMICS:
         sub = [(name, role, _kept_shape(p, name, len(keep)) if role != "in" else (_rows(p, name, keep_t).cpu() if name in iso.PER_FRAME else p))
                for name, role, p in bufs]
@@ -434,14 +527,14 @@ def test_a_non_finite_frame_changes_no_other(family, n_inp, tail, hip_device, mo
 
 
 def test_every_family_and_entry_was_reached(request):
-    """Both phases passed for every (family, entry) of the placement table and the two entries added here; the families are recorded
+    """Both phases passed for every (family, entry) of the placement table and the five entries added here; the families are recorded
     as they pass, so this guard needs all of them in the same session."""
     here = {item.name for item in request.session.items if item.module is request.module}
     wanted = {"test_a_non_finite_frame_changes_no_other[%s-%d-%d]" % c for c in CASES}
     if not wanted <= here:
         pytest.skip("the coverage guard needs every family in this session: %d not selected" % len(wanted - here))
     want = {(f, e) for f, v in FAMILIES.items() for e in v[5]} | {(f, e) for f, v in EXTRA.items() for e in v}
-    assert {(f, e) for f in EXTRA for e in (GRID, BIAS)} <= want
+    assert {(f, e) for f in EXTRA for e in NEW} <= want and len(NEW) == 5
     missing = sorted((want - SMALL) | (want - set(DENSE)))
     assert not missing, ("not reached:", missing)
     for (f, e), (n, rounds, chunk) in sorted(DENSE.items()):
