@@ -609,6 +609,40 @@ int molann_opes_step_f64(double* centers, double* sigma, double* heights, int64_
                          double* run, const double* y, const double* V, int64_t n_walkers, const double* sigma0, const double* sigma_min,
                          double beta, double threshold, double cutoff, int32_t fixed_sigma, molann_stream_t stream);
 
+/* The deposit step of a METADYNAMICS run on a table, in ONE launch of metad_deposit_f64_kernel (ahead of time: no hipRTC, no plan): the
+ * hills of n_walkers walkers are added, in place, to the table molann_value_and_grid_f64 / molann_value_and_bias_f64 interpolate, with
+ * well-tempered heights formed on the device from the bias those launches wrote.  table: a DEVICE pointer to prod_k shape[k] doubles,
+ * 1 <= d <= 3 axes, layout and axes exactly molann_value_and_grid_f64's (row-major, output 0 slowest; point i of axis k at
+ * lower[k] + i spacing[k]; a periodic axis has period shape[k] spacing[k]); shape, lower, spacing, periodic (may be NULL: none),
+ * sigma[d] and columns[d] (may be NULL: 0..d-1) are HOST arrays, read during the call.  Walker a's centre is y[a y_stride + columns[k]]
+ * and its bias V[a v_stride] (DEVICE, read only), so the column V_g = energies[:, 2] of molann_value_and_bias_f64 and the chosen outputs
+ * of a wider model are read where they are.  Per walker a, ascending:
+ *   1. h_a = height0 exp(-V_a inv_dT), inv_dT = 1 / (kT (biasfactor - 1)); inv_dT = 0: plain metadynamics, h_a = height0;
+ *   2. the walker is valid when V_a, every y[a, columns[k]] and h_a are finite and h_a > 0; any other changes no table entry and is
+ *      counted in state[1];
+ *   3. every grid point g gets table[g] = table[g] + h_a prod_k exp(-1/2 (delta_k / sigma_k)^2), delta_k = g_k - y_ak, wrapped to
+ *      delta - P rint(delta / P) on a periodic axis (bias.add_hills_to_grid's rule); a hill centred outside a non-periodic range lands
+ *      on the points it reaches;
+ *   4. with a cutoff c (in widths) only where q = sum_k (delta_k / sigma_k)^2 <= c^2: an entry outside keeps its bits, and a tile of
+ *      the table (256 entries: 256, 16 x 16, 4 x 4 x 16) that no valid hill reaches is neither read nor written.  +inf: no cutoff.
+ * An entry is written by one thread, which adds the walkers' terms in their order, ((t + c_1) + c_2) + ...: no atomics, the same bits
+ * on every run and for every launch geometry, and two queued deposits give the bits of one deposit of the concatenated walkers.
+ * state[8] (DEVICE) = (hills, refused, sum_heights, steps, logged, 0, 0, 0), exact integers in doubles, updated by one thread in walker
+ * order (entries 5..7 are not touched); log (DEVICE, may be NULL) [log_capacity, 2 d + 1] gets one row (centre_k..., sigma_k..., height)
+ * per valid walker at row state[4] (held to [0, log_capacity] whatever its bits) while that is below log_capacity - a hill past the
+ * capacity is deposited and counted in hills all the same.  The host needs nothing of state to enqueue the next step.  Refusals, in
+ * this order, with nothing enqueued: a NULL table, state, y, V, shape, lower, spacing or sigma where n_walkers > 0: MOLANN_E_NULL; a
+ * table, state, y, V or log that is not 8-byte aligned: MOLANN_E_ALIGNMENT; d outside 1..3: MOLANN_E_UNSUPPORTED; a grid
+ * molann_value_and_grid_f64 refuses (shape[k] < 4, a spacing that is not finite and > 0, a lower that is not finite, 2^31 points or
+ * more), a sigma or a height0 that is not finite and > 0, an inv_dT that is not finite and >= 0, a cutoff that is NaN or not > 0, a
+ * negative stride, count or capacity, a column outside [0, y_stride): MOLANN_E_DESC.  n_walkers == 0: MOLANN_OK, nothing launched.
+ * The call only enqueues on `stream` (no workspace, no event, nothing allocated): thread-safe on distinct tables and capturable.  Out
+ * of scope: adaptive widths; the reweighting offset c(t); walkers on several ranks; float32; more than 3 axes. */
+int molann_metad_deposit_f64(double* table, int32_t d, const int64_t* shape, const double* lower, const double* spacing, const int32_t* periodic,
+                             const double* sigma, const int32_t* columns, const double* y, int64_t y_stride, const double* V, int64_t v_stride,
+                             int64_t n_walkers, double height0, double inv_dT, double cutoff, double* state, double* log, int64_t log_capacity,
+                             molann_stream_t stream);
+
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
  * is fused into the lane kernel, and large-frame plans with a head within the fused MLP's limits (the features are written
@@ -699,6 +733,12 @@ double molann_selftest_opes_table_f64(const double* y, int d, const double* cent
 int molann_selftest_opes_step_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
                                   double* run, const double* y, const double* V, int64_t n_walkers, const double* sigma0, const double* sigma_min,
                                   double beta, double threshold, double cutoff, int32_t fixed_sigma);
+/* molann_metad_deposit_f64 on the host: the same arguments as HOST pointers, the same refusals, the same tiles, and per entry the
+ * walkers' terms in their order through the functions its kernel calls */
+int molann_selftest_metad_deposit_f64(double* table, int32_t d, const int64_t* shape, const double* lower, const double* spacing,
+                                      const int32_t* periodic, const double* sigma, const int32_t* columns, const double* y, int64_t y_stride,
+                                      const double* V, int64_t v_stride, int64_t n_walkers, double height0, double inv_dT, double cutoff,
+                                      double* state, double* log, int64_t log_capacity);
 /* one axis' step of molann_value_and_grid_f64 on the host, through the function its kernel calls: the four table indices, the four
  * weights and the four derivative weights (s w' / spacing) for output value y on an axis of n points; any of the three may be NULL */
 void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]);

@@ -214,6 +214,7 @@ def lib():
                                                 + [ctypes.c_double] * 3 + [vp, vp, vp, vp]),
             "molann_plan_supports_value_and_opes_table_f64": (i32, [vp]),
             "molann_opes_step_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp] + [ctypes.c_double] * 3 + [i32, vp]),
+            "molann_metad_deposit_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64] + [ctypes.c_double] * 3 + [vp, vp, i64, vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -234,6 +235,8 @@ def lib():
             "molann_selftest_opes_deposit_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, ctypes.c_double, ctypes.c_double]),
             "molann_selftest_opes_table_f64": (ctypes.c_double, [vp, i32, vp, vp, vp, i64, vp, vp] + [ctypes.c_double] * 3 + [vp]),
             "molann_selftest_opes_step_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp] + [ctypes.c_double] * 3 + [i32]),
+            "molann_selftest_metad_deposit_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64] + [ctypes.c_double] * 3
+                                                  + [vp, vp, i64]),
             "molann_selftest_grid_axis_f64": (None, [ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32, vp, vp, vp]),
             "molann_selftest_grid_f64": (ctypes.c_double, [vp, i32, vp, vp, vp, vp, vp, vp]),
             "molann_selftest_bias_f64": (i32, [vp, i32, ctypes.POINTER(BiasTermsF64), vp, vp]),
@@ -738,6 +741,29 @@ def opes_step_f64(centers, sigma, heights, state, run, period, y, V, sigma0, sig
                                       float("inf") if cutoff is None else float(cutoff), 1 if fixed_sigma else 0,
                                       torch.cuda.current_stream().cuda_stream)
     _check(code, "molann_opes_step_f64")
+
+
+def metad_grid_arrays(shape, lower, spacing, periodic, sigma, columns):
+    """The host arrays `molann_metad_deposit_f64` reads during the call, as ctypes arrays: ``(shape, lower, spacing, periodic, sigma,
+    columns)``; `periodic` and `columns` may be None (NULL: no periodic axis, the first outputs)."""
+    d = len(shape)
+    I = lambda v: None if v is None else (ctypes.c_int32 * d)(*[int(c) for c in v])  # noqa: E731
+    F = lambda v: (ctypes.c_double * d)(*[float(c) for c in v])  # noqa: E731
+    return (ctypes.c_int64 * d)(*[int(n) for n in shape]), F(lower), F(spacing), I(periodic), F(sigma), I(columns)
+
+
+def metad_deposit_f64(table, arrays, y, V, height0, inv_dT, cutoff, state, log=None):
+    """`molann_metad_deposit_f64` on torch's current stream: the hills of the walkers `y` [W, n_out] (centres in the columns the arrays
+    name) with biases `V` ([W], or a column of a wider tensor: its stride is passed on) are added to `table` in place with heights
+    ``height0 exp(-V inv_dT)``; `state` [8] and `log` ([capacity, 2 d + 1] or None) are updated, in one launch; nothing is read back.
+    `arrays`: `metad_grid_arrays`, made once.  float64 tensors on one device, `table`, `y`, `state`, `log` contiguous; `cutoff` None is
+    +inf.  The tensors' shapes are the caller's to check (`molann_amd.bias.MetadRun` does)."""
+    shape, lower, spacing, periodic, sigma, columns = arrays
+    code = lib().molann_metad_deposit_f64(table.data_ptr(), len(shape), shape, lower, spacing, periodic, sigma, columns, y.data_ptr(), y.stride(0),
+                                          V.data_ptr(), V.stride(0), y.shape[0], float(height0), float(inv_dT),
+                                          float("inf") if cutoff is None else float(cutoff), state.data_ptr(), _address(log),
+                                          0 if log is None else log.shape[0], torch.cuda.current_stream().cuda_stream)
+    _check(code, "molann_metad_deposit_f64")
 
 
 def opes_kernel_sum_f64(points, centers, heights, sigma, period, cutoff, P, dP=None):

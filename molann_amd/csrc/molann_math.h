@@ -967,6 +967,105 @@ MOLANN_HD double grid_stencil_term_f64(int p, int d, const double* table, const 
     return T * (wa[0] * wa[1] * wa[2]);
 }
 
+// A metadynamics deposit onto the table above (metad_deposit_f64_kernel and its host twin): walker a adds the Gaussian hill
+// h_a prod_k exp(-1/2 (d_k / sigma_k)^2) to every grid point, d_k = g_k - y_ak with g_k = lower_k + i h_k, wrapped to d - P rint(d / P)
+// on a periodic axis (P = n_k h_k; `P` = 0 here: not periodic), where q = sum_k (d_k / sigma_k)^2 <= c2 = cutoff^2 (+inf: everywhere).
+// The Gaussian is a product over the axes, so the kernel forms q_k = (d_k / sigma_k)^2 and e_k = exp(-(0.5 q_k)) once per axis index of
+// a tile and an entry's term from them: metad_axis_delta_f64, metad_axis_factor_f64, metad_term_f64 (q and the product with k
+// ascending).  Nothing is contracted, so the host and the device round alike up to exp.
+//
+// The table is cut into tiles of metad_tile_extent(d, k) points along axis k, one block each, 256 entries.  metad_axis_reach_f64 is a
+// lower bound of q_k over the indices i0..i1 of a tile, from the two ends alone: the computed d is monotone in i but for the one jump a
+// wrap can make inside a tile (a tile spans less than a period), so the smallest |d| is an end's, or 0 where the sign changes; division
+// and square are monotone too, hence no index of the run has a smaller q_k, in the very numbers the entries use.  A hill whose bounds
+// sum (k ascending) to more than c2 adds nothing to the tile: the block skips it, and a tile that every hill skips is not touched.
+constexpr int METAD_TILE = 256;
+MOLANN_HD constexpr int metad_tile_extent(int d, int k) { return d == 1 ? 256 : d == 2 ? 16 : k == 2 ? 16 : 4; }
+MOLANN_HD constexpr int metad_tile_slots(int d) { return d == 1 ? 256 : d == 2 ? 32 : 24; }    // sum_k metad_tile_extent(d, k)
+MOLANN_HD constexpr int metad_chunk(int d) { return d == 1 ? 8 : 64; }                            // walkers staged at a time
+
+// h_a = height0 exp(-(V_a inv_dT)), inv_dT = 1 / (kT (biasfactor - 1)); inv_dT = 0: plain metadynamics, h_a = height0
+MOLANN_HD double metad_height_f64(double height0, double V, double inv_dT) {
+#pragma clang fp contract(off)
+    return inv_dT > 0.0 ? height0 * exp(-(V * inv_dT)) : height0;
+}
+// a walker deposits when V, every y_k and the height are finite and the height > 0 (a NaN fails every comparison)
+MOLANN_HD bool metad_walker_valid_f64(double V, const double (&y)[GRID_MAX_D], double h, int d) {
+    bool ok = fabs(V) <= 1.7976931348623157e308 && h > 0.0 && h <= 1.7976931348623157e308;
+#pragma unroll
+    for (int k = 0; k < GRID_MAX_D; ++k)
+        if (k < d) ok = ok && fabs(y[k]) <= 1.7976931348623157e308;
+    return ok;
+}
+MOLANN_HD double metad_axis_delta_f64(long i, double y, double lower, double h, double P) {
+#pragma clang fp contract(off)
+    const double g = lower + (double)i * h;
+    double dk = g - y;
+    if (P > 0.0) {
+        const double turns = rint(dk / P);
+        const double whole = P * turns;
+        dk = dk - whole;
+    }
+    return dk;
+}
+MOLANN_HD double metad_axis_q_f64(double dk, double sigma) {
+#pragma clang fp contract(off)
+    const double s = dk / sigma;
+    return s * s;
+}
+MOLANN_HD void metad_axis_factor_f64(double dk, double sigma, double& q, double& e) {
+#pragma clang fp contract(off)
+    q = metad_axis_q_f64(dk, sigma);
+    e = exp(-(0.5 * q));
+}
+MOLANN_HD double metad_axis_reach_f64(long i0, long i1, double y, double lower, double h, double P, double sigma) {
+#pragma clang fp contract(off)
+    const double lo = metad_axis_delta_f64(i0, y, lower, h, P), hi = metad_axis_delta_f64(i1, y, lower, h, P);
+    const double above = lo > 0.0 ? lo : 0.0;      // a run that starts at lo and rises: its smallest |d|, 0 where it crosses 0 ...
+    const double below = hi < 0.0 ? -hi : 0.0;     // ... and a run that rises to hi
+    double m;
+    if (lo <= hi) m = lo > 0.0 ? above : below;    // one run from lo to hi
+    else m = above < below ? above : below;        // a wrap inside the tile: lo .. P/2, then -P/2 .. hi (a NaN end: 0, reached)
+    return metad_axis_q_f64(m, sigma);
+}
+// q of an entry or its lower bound over a tile from the axes' q_k, k ascending; the entry's term from the axes' e_k
+MOLANN_HD double metad_q_f64(const double (&q)[GRID_MAX_D], int d) {
+#pragma clang fp contract(off)
+    double s = q[0];
+    if (d > 1) s = s + q[1];
+    if (d > 2) s = s + q[2];
+    return s;
+}
+MOLANN_HD double metad_term_f64(double h, const double (&e)[GRID_MAX_D], int d) {
+#pragma clang fp contract(off)
+    double p = e[0];
+    if (d > 1) p = p * e[1];
+    if (d > 2) p = p * e[2];
+    return h * p;
+}
+// One walker's step of state = (hills, refused, sum_heights, steps, logged, ...), in walker order by one thread: a valid walker is
+// counted, its height added and its row (y_k..., sigma_k..., h) appended to log[log_capacity, 2 d + 1] while there is room (a hill past
+// the capacity is deposited and counted all the same); any other is refused.  `logged` comes from opes_live_count_f64, so a row index
+// lies in [0, log_capacity) whatever the state held.
+MOLANN_HD void metad_state_walker_f64(bool valid, double h, const double (&y)[GRID_MAX_D], const double (&sigma)[GRID_MAX_D], int d, double* log,
+                                      long log_capacity, double& hills, double& refused, double& sum_heights, long& logged) {
+#pragma clang fp contract(off)
+    if (!valid) {
+        refused = refused + 1.0;
+        return;
+    }
+    hills = hills + 1.0;
+    sum_heights = sum_heights + h;
+    if (logged < log_capacity) {
+        double* row = log + logged * (2 * d + 1);
+#pragma unroll
+        for (int k = 0; k < GRID_MAX_D; ++k)
+            if (k < d) { row[k] = y[k]; row[d + k] = sigma[k]; }
+        row[2 * d] = h;
+        logged += 1;
+    }
+}
+
 // Backward of kabsch_rotation: given H, the rotation R it produced and G_R = dL/dR, returns G_H = dL/dH.
 // With S = R^T H (symmetric at the optimum) a perturbation dH turns R by dR = R [w]x where
 // (tr(S) I - S) w = vee(R^T dH - dH^T R); hence G_H = R [n]x, n = (tr(S) I - S)^-1 vee(M - M^T), M = R^T G_R.

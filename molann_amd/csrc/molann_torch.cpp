@@ -1236,6 +1236,60 @@ void opes_step_hip(at::Tensor centers_in, at::Tensor sigma_in, at::Tensor height
           "molann_opes_step_f64");
 }
 
+// The deposit step of a metadynamics run on a table (molann_metad_deposit_f64): the hills of the walkers y [W, n_out] (centres in `columns`;
+// empty: the first table.dim()) with biases V [W] - a column of a wider tensor is read where it is - are added to `table` in place with
+// heights height0 exp(-V inv_dT), and `state` [8] and `log` ([capacity, 2 d + 1] or none) are updated, in ONE launch on the current stream;
+// nothing is read back.  lower, spacing, sigma: one float per axis; periodic: one bool per axis or empty; the scalars are checked here as
+// the C entry checks them.
+void metad_step_hip(at::Tensor table_in, at::Tensor state_in, const c10::optional<at::Tensor>& log_in, std::vector<double> lower,
+                    std::vector<double> spacing, c10::List<bool> periodic, std::vector<double> sigma, std::vector<int64_t> columns,
+                    const at::Tensor& y_in, const at::Tensor& V_in, double height0, double inv_dT, double cutoff) {
+    const char* const op = "molann::metad_step";
+    TORCH_CHECK_VALUE(table_in.dim() >= 1 && table_in.dim() <= 3, "molann::metad_step: `table` must have 1 to 3 dimensions");
+    const int64_t d = table_in.dim();
+    TORCH_CHECK_VALUE((int64_t)lower.size() == d && (int64_t)spacing.size() == d && (int64_t)sigma.size() == d &&
+                          (periodic.size() == 0 || (int64_t)periodic.size() == d) && (columns.empty() || (int64_t)columns.size() == d),
+                      "molann::metad_step: `lower`, `spacing`, `sigma` must have one entry per axis of `table` (", d,
+                      "), `periodic` and `columns` that many or none");
+    TORCH_CHECK_VALUE(std::isfinite(height0) && height0 > 0.0 && std::isfinite(inv_dT) && inv_dT >= 0.0 && cutoff > 0.0,
+                      "molann::metad_step: `height0` must be finite and > 0, `inv_dT` finite and >= 0, `cutoff` > 0 (inf: none); got ", height0, ", ",
+                      inv_dT, ", ", cutoff);
+    const at::Tensor table = opes_tensor(op, "table", table_in, table_in, true, "[n_0, ...]", true);
+    const at::Tensor state = opes_tensor(op, "state", state_in, table, state_in.dim() == 1 && state_in.size(0) == 8, "[8]", true);
+    at::Tensor log;
+    if (log_in.has_value() && log_in->defined())
+        log = opes_tensor(op, "log", *log_in, table, log_in->dim() == 2 && log_in->size(1) == 2 * d + 1, "[capacity, 2 d + 1]", true);
+    int64_t widest = d - 1;
+    for (int64_t c : columns) {
+        TORCH_CHECK_INDEX(c >= 0, "molann::metad_step: `columns` holds output indices >= 0");
+        widest = std::max(widest, c);
+    }
+    TORCH_CHECK_TYPE(y_in.scalar_type() == at::kDouble && V_in.scalar_type() == at::kDouble, "molann::metad_step: `y` and `V` must be float64");
+    TORCH_CHECK_VALUE(y_in.dim() == 2 && y_in.size(1) > widest && y_in.device() == table.device(), "molann::metad_step: `y` must be [W, more than ",
+                      widest, " columns] on ", table.device());
+    const int64_t n_walkers = y_in.size(0);
+    TORCH_CHECK_VALUE(V_in.dim() == 1 && V_in.size(0) == n_walkers && V_in.device() == table.device(), "molann::metad_step: `V` must be [W] on ",
+                      table.device());
+    // read where they are: a row stride for y, an element stride for V (energies[:, 2] of value_and_bias)
+    const at::Tensor y = y_in.stride(1) == 1 || y_in.size(1) == 1 ? y_in.detach() : y_in.detach().contiguous();
+    const at::Tensor V = V_in.detach();
+    if (n_walkers == 0) return;
+    int64_t shape[3] = {4, 4, 4};
+    int32_t per[3] = {0, 0, 0}, cols[3] = {0, 1, 2};
+    for (int64_t k = 0; k < d; ++k) {
+        shape[k] = table.size(k);
+        per[k] = periodic.size() > 0 && periodic.get(k) ? 1 : 0;
+        if (!columns.empty()) cols[k] = (int32_t)columns[k];
+    }
+    const c10::DeviceGuard guard(table.device());
+    hipStream_t stream = c10::hip::getCurrentHIPStream(table.get_device()).stream();
+    check(molann_metad_deposit_f64(table.data_ptr<double>(), (int32_t)d, shape, lower.data(), spacing.data(), per, sigma.data(), cols,
+                                   y.data_ptr<double>(), n_walkers > 1 ? y.stride(0) : y.size(1), V.data_ptr<double>(), n_walkers > 1 ? V.stride(0) : 1,
+                                   n_walkers, height0, inv_dT, cutoff, state.data_ptr<double>(), log.defined() ? log.data_ptr<double>() : nullptr,
+                                   log.defined() ? log.size(0) : 0, stream),
+          "molann_metad_deposit_f64");
+}
+
 // {P} or {P, dP}: the kernel density of an OPES table at points [M, d] and, with `with_grad`, its derivative [M, d] in ONE launch
 // (molann_opes_kernel_sum_f64).  The table as value_and_opes takes it.
 std::vector<at::Tensor> opes_kernel_sum_hip(const at::Tensor& points_in, const at::Tensor& centers_in, const at::Tensor& heights_in,
@@ -1944,6 +1998,8 @@ TORCH_LIBRARY(molann, m) {
           "Tensor state, Tensor? period, float scale, float epsilon, float cutoff, Tensor[] into) -> Tensor[]");
     m.def("opes_step(Tensor(a!) centers, Tensor(b!) sigma, Tensor(c!) heights, Tensor(d!) state, Tensor(e!) run, Tensor? period, Tensor y, Tensor V, "
           "Tensor sigma0, Tensor? sigma_min, float beta, float threshold, float cutoff, bool fixed_sigma) -> ()");
+    m.def("metad_step(Tensor(a!) table, Tensor(b!) state, Tensor(c!)? log, float[] lower, float[] spacing, bool[] periodic, float[] sigma, "
+          "int[] columns, Tensor y, Tensor V, float height0, float inv_dT, float cutoff) -> ()");
     m.def("opes_kernel_sum(Tensor points, Tensor centers, Tensor heights, Tensor sigma, Tensor? period, float cutoff, bool with_grad) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
@@ -1985,6 +2041,7 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_opes_table", value_and_opes_table_hip);
     m.impl("value_and_opes_table_h", value_and_opes_table_h_hip);
     m.impl("opes_step", opes_step_hip);
+    m.impl("metad_step", metad_step_hip);
     m.impl("opes_kernel_sum", opes_kernel_sum_hip);
 }
 
