@@ -574,8 +574,8 @@ int molann_opes_kernel_sum_f64(const double* points, int64_t n_points, int32_t d
  * centres restores S).  Refusals, in molann_value_and_vjp_f64's order and with nothing written: a NULL plan, x, table pointer, state, out,
  * bias or grad_x: MOLANN_E_NULL; 8-byte alignment (period too): MOLANN_E_ALIGNMENT; a plan without items: MOLANN_E_STAGE; the head's
  * tensors; a plan molann_value_and_opes_f64 does not serve: MOLANN_E_UNSUPPORTED; capacity < 1, a scale that is not finite, an epsilon
- * that is not finite and > 0, a cutoff that is NaN or not > 0 (+inf: none): MOLANN_E_DESC.  n_frames == 0: MOLANN_OK.  Out of scope:
- * molann_value_and_bias_opes_f64 reading the state (a second instance family); float32. */
+ * that is not finite and > 0, a cutoff that is NaN or not > 0 (+inf: none): MOLANN_E_DESC.  n_frames == 0: MOLANN_OK.  The same on
+ * some of a wider model's outputs, or together with walls or a table: molann_value_and_bias_opes_table_f64.  Out of scope: float32. */
 int molann_value_and_opes_table_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
                                     const double* centers, const double* heights, const double* sigma, int64_t capacity, const double* state,
                                     const double* period, double scale, double epsilon, double cutoff, double* out, double* bias, double* grad_x,
@@ -608,6 +608,53 @@ int molann_plan_supports_value_and_opes_table_f64(const molann_plan* plan);
 int molann_opes_step_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
                          double* run, const double* y, const double* V, int64_t n_walkers, const double* sigma0, const double* sigma_min,
                          double beta, double threshold, double cutoff, int32_t fixed_sigma, molann_stream_t stream);
+
+/* molann_value_and_bias_opes_f64 on a table kept by molann_opes_deposit_f64 / molann_opes_step_f64 / molann_opes_step_columns_f64, in ONE
+ * launch of frames_value_bias_opes_table_f64_kernel (ahead of time: no hipRTC): the OPES term's live count and normalisation are read
+ * from the table's state in device memory, as molann_value_and_opes_table_f64 reads them, so an OPES run with walls, a table, or a model
+ * wider than the kernel table needs no read-back between a deposit and the next bias, and the launch can be captured in a graph and
+ * replayed while the table grows.  `terms` (the restraint and the tabulated bias; may be NULL) is molann_value_and_bias_opes_f64's.
+ * `opes_table` is required: centers[capacity, n_columns], sigma[capacity, n_columns] (a row per kernel) and heights[capacity] are the
+ * table's storage over the listed columns, in the order of the list, state[4] = (n, S, merges, refused) its state - DEVICE pointers, all
+ * four required whatever the live count, which only the device knows; period [n_columns] or NULL.  Every lane forms n = state[0] held
+ * to [0, capacity] (a NaN or a negative value: 0) and norm = S / n, and from there on the kernel is molann_value_and_bias_opes_f64's:
+ * called with that n, that norm and sigma_stride = n_columns it gives the same bits in out, energies[N, 4] = (E_r, 0, V_g, V_o) and
+ * grad_x.  n == 0: V_o = scale log(epsilon), its share of grad_x exactly 0, nothing of the kernel table is read and norm is not
+ * formed.  A state whose S is not finite and > 0 while n >= 1 gives NaN or inf for every frame: it is not guarded.  Refusals, in
+ * molann_value_and_bias_opes_f64's order and with nothing written: a NULL plan, opes_table, x, out, energies, grad_x, kernel table
+ * pointer, state, or pointer a present term requires: MOLANN_E_NULL; 8-byte alignment: MOLANN_E_ALIGNMENT; MOLANN_E_STAGE /
+ * MOLANN_E_UNSUPPORTED as molann_value_and_bias_f64; n_columns <= 0, a negative grid count, a center_stride other than 0 or out_dim,
+ * capacity < 1, scalars molann_value_and_opes_table_f64 refuses, a grid molann_value_and_grid_f64 refuses: MOLANN_E_DESC; hills columns
+ * in `terms`: MOLANN_E_UNSUPPORTED; then the lists as molann_value_and_bias_opes_f64 has them.  n_frames < 0: MOLANN_E_DESC;
+ * n_frames == 0: nothing is read or launched.  The call only enqueues on `stream` (no workspace, no atomics, no event): thread-safe and
+ * capturable.  Out of scope: hills and OPES in one launch; more than one OPES term; float32. */
+typedef struct molann_opes_table_term_f64 {
+    /* the outputs the kernels act on: a HOST list, distinct, any order, <= 8; NULL: 0..n_columns-1 */
+    int32_t n_columns; const int32_t* columns;
+    /* the kernel table's storage over the listed columns and its state: DEVICE pointers */
+    const double *centers, *heights, *sigma; int64_t capacity; const double* state; const double* period;
+    /* host values; cutoff = +inf: none */
+    double scale, epsilon, cutoff;
+} molann_opes_table_term_f64;
+int molann_value_and_bias_opes_table_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                                         const molann_bias_terms_f64* terms, const molann_opes_table_term_f64* opes_table, double* out,
+                                         double* energies, double* grad_x, molann_stream_t stream);
+
+/* 1 when molann_value_and_bias_opes_table_f64 serves the plan (molann_value_and_bias_f64 serves it), 0 otherwise. */
+int molann_plan_supports_value_and_bias_opes_table_f64(const molann_plan* plan);
+
+/* molann_opes_step_f64 on strided outputs and chosen columns, in ONE launch of opes_step_columns_f64_kernel: walker a's centre is
+ * y[a * y_stride + columns[k]], k < d, and its bias V[a * v_stride] - so the out[n_walkers, out_dim] (y_stride = out_dim) and column 3
+ * of the energies[n_walkers, 4] (V = energies + 3, v_stride = 4) that molann_value_and_bias_opes_table_f64 just wrote are read in
+ * place.  The weight uses that OPES bias alone, not the walls or the table, as OPES_METAD does.  columns: a HOST list of d distinct
+ * indices in [0, y_stride), NULL for 0..d-1, carried by value.  A walker's validity looks at its V and its d chosen outputs only.  On
+ * the same walkers the table, state and run are molann_opes_step_f64's on the gathered copy, bit for bit.  Refusals: molann_opes_step_f64's,
+ * in its order; then y_stride < d or v_stride < 1: MOLANN_E_DESC; a column outside [0, y_stride) or repeated: MOLANN_E_INDEX - with
+ * nothing enqueued.  n_walkers == 0: MOLANN_OK, nothing launched.  Capturable, as molann_opes_step_f64. */
+int molann_opes_step_columns_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
+                                 double* run, const double* y, int64_t y_stride, const int32_t* columns, const double* V, int64_t v_stride,
+                                 int64_t n_walkers, const double* sigma0, const double* sigma_min, double beta, double threshold, double cutoff,
+                                 int32_t fixed_sigma, molann_stream_t stream);
 
 /* The deposit step of a METADYNAMICS run on a table, in ONE launch of metad_deposit_f64_kernel (ahead of time: no hipRTC, no plan): the
  * hills of n_walkers walkers are added, in place, to the table molann_value_and_grid_f64 / molann_value_and_bias_f64 interpolate, with
@@ -757,6 +804,18 @@ int molann_selftest_bias_f64(const double* y, int d_out, const molann_bias_terms
  * the cotangent.  Returns MOLANN_OK, or the code molann_value_and_bias_opes_f64 gives the same terms (nothing written then) */
 int molann_selftest_bias_opes_f64(const double* y, int d_out, const molann_bias_terms_f64* terms, const molann_opes_term_f64* opes,
                                   double* energies4, double* dy);
+/* one frame of molann_value_and_bias_opes_table_f64 on the host (every pointer of `terms` and `opes_table` a HOST pointer here): n and
+ * norm from state[4] as its kernel forms them, then molann_selftest_bias_opes_f64's steps on the first n rows with a row of widths per
+ * kernel - the same code, so the same doubles.  Returns MOLANN_OK, or the code molann_value_and_bias_opes_table_f64 gives the same terms
+ * (nothing written then) */
+int molann_selftest_bias_opes_table_f64(const double* y, int d_out, const molann_bias_terms_f64* terms, const molann_opes_table_term_f64* opes_table,
+                                        double* energies4, double* dy);
+/* molann_opes_step_columns_f64 on the host: the same arguments as HOST pointers, the same steps through the functions its kernel calls,
+ * the same refusals and the device's order of every sum */
+int molann_selftest_opes_step_columns_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period,
+                                          double* state, double* run, const double* y, int64_t y_stride, const int32_t* columns, const double* V,
+                                          int64_t v_stride, int64_t n_walkers, const double* sigma0, const double* sigma_min, double beta,
+                                          double threshold, double cutoff, int32_t fixed_sigma);
 /* the unit-cotangent local Jacobian frames_value_jac_f64_kernel combines: jac36[c][j][xyz] = d(output column c of the item) /
  * d(atom j) for the item's 4 atoms (rows past the item's width are 0); returns the width */
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* atoms_xyz, double* jac36);

@@ -144,6 +144,32 @@ def opes_term_f64(opes, ptr=lambda t: t.data_ptr()):
     return o, keep
 
 
+class OpesTableTermF64(ctypes.Structure):
+    """molann_opes_table_term_f64 of include/molann_hip.h: the OPES term of `molann_value_and_bias_opes_table_f64`."""
+    _fields_ = [("n_columns", ctypes.c_int32), ("columns", ctypes.POINTER(ctypes.c_int32)),
+                ("centers", ctypes.c_void_p), ("heights", ctypes.c_void_p), ("sigma", ctypes.c_void_p), ("capacity", ctypes.c_int64),
+                ("state", ctypes.c_void_p), ("period", ctypes.c_void_p),
+                ("scale", ctypes.c_double), ("epsilon", ctypes.c_double), ("cutoff", ctypes.c_double)]
+
+
+def opes_table_term_f64(opes, ptr=lambda t: t.data_ptr()):
+    """An `OpesTableTermF64` and the host array it points into (keep both alive for the call).  opes: (columns, centers, heights, sigma,
+    capacity, state, period, scale, epsilon, cutoff); tensors give their addresses through `ptr`; columns None is the identity list and
+    needs the count in its place: (None, n); cutoff None is +inf."""
+    cols, centers, heights, sigma, capacity, state, period, scale, epsilon, cutoff = opes
+    o, keep = OpesTableTermF64(), []
+    if isinstance(cols, tuple) and len(cols) == 2 and cols[0] is None:
+        o.n_columns = int(cols[1])
+    else:
+        arr = _i32_array(cols)
+        keep.append(arr)
+        o.n_columns, o.columns = len(cols), arr
+    o.centers, o.heights, o.sigma, o.state, o.period = (None if v is None else ptr(v) for v in (centers, heights, sigma, state, period))
+    o.capacity = int(capacity)
+    o.scale, o.epsilon, o.cutoff = float(scale), float(epsilon), float("inf") if cutoff is None else float(cutoff)
+    return o, keep
+
+
 _lib = None
 
 
@@ -214,6 +240,14 @@ def lib():
                                                 + [ctypes.c_double] * 3 + [vp, vp, vp, vp]),
             "molann_plan_supports_value_and_opes_table_f64": (i32, [vp]),
             "molann_opes_step_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp] + [ctypes.c_double] * 3 + [i32, vp]),
+            "molann_value_and_bias_opes_table_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(BiasTermsF64),
+                                                     ctypes.POINTER(OpesTableTermF64), vp, vp, vp, vp]),
+            "molann_plan_supports_value_and_bias_opes_table_f64": (i32, [vp]),
+            "molann_opes_step_columns_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int32), vp, i64, i64, vp, vp]
+                                             + [ctypes.c_double] * 3 + [i32, vp]),
+            "molann_selftest_bias_opes_table_f64": (i32, [vp, i32, ctypes.POINTER(BiasTermsF64), ctypes.POINTER(OpesTableTermF64), vp, vp]),
+            "molann_selftest_opes_step_columns_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int32), vp, i64, i64,
+                                                            vp, vp] + [ctypes.c_double] * 3 + [i32]),
             "molann_metad_deposit_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64] + [ctypes.c_double] * 3 + [vp, vp, i64, vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -682,6 +716,35 @@ class Plan(object):
 
     value_and_bias_opes = value_and_bias_opes_f64
 
+    def supports_value_and_bias_opes_table_f64(self):
+        """True when `value_and_bias_opes_table_f64` serves this plan: `value_and_bias_f64` serves it (nothing is built)."""
+        return lib().molann_plan_supports_value_and_bias_opes_table_f64(self._handle) == 1
+
+    def value_and_bias_opes_table_f64(self, x, weights, biases, out, energies, grad_x, opes, restraint=None, grid=None):
+        """`value_and_bias_opes_f64` on a kernel table whose live count and normalisation the kernel reads from `state` [4] in device
+        memory, one launch of frames_value_bias_opes_table_f64_kernel: nothing is read back.  opes: (columns, centers, heights, sigma,
+        state, period, scale, epsilon, cutoff) - the table's storage ``[capacity, len(columns)]``, ``[capacity]``, ``[capacity,
+        len(columns)]`` and its state, contiguous float64 on x's device; restraint, grid: None or as `value_and_bias_f64` takes them."""
+        W, B = _layer_pointers(weights, biases)
+        d_out = out.numel() // max(x.shape[0], 1)
+        r = g = None
+        if restraint is not None:
+            center, kappa, period, flat = restraint
+            r = (center, kappa, period, flat, 0 if center.numel() == d_out and center.dim() < 2 else d_out)
+        if grid is not None:
+            cols, table, lower, spacing, periodic = grid
+            g = ((None, table.dim()) if cols is None else cols, table, table.shape, lower, spacing, periodic)
+        cols, centers, heights, sigma, state, period, scale, epsilon, cutoff = opes
+        term, keep_o = opes_table_term_f64(((None, centers.shape[1]) if cols is None else cols, centers, heights, sigma, centers.shape[0], state,
+                                            period, scale, epsilon, cutoff))
+        terms, keep = bias_terms_f64(r, None, g)
+        self._launch("molann_value_and_bias_opes_table_f64", x.data_ptr(), x.shape[0], W, B, ctypes.byref(terms), ctypes.byref(term),
+                     out.data_ptr(), energies.data_ptr(), grad_x.data_ptr())
+        del keep, keep_o
+        return out, energies, grad_x
+
+    value_and_bias_opes_table = value_and_bias_opes_table_f64
+
     def forward_train(self, x, out, features):
         """`forward_packed` that also keeps the features (for `mlp_backward` + `features_backward`)."""
         code = _lib.molann_forward_train_f32(self._handle, x.data_ptr(), x.shape[0], out.data_ptr(), features.data_ptr(),
@@ -741,6 +804,22 @@ def opes_step_f64(centers, sigma, heights, state, run, period, y, V, sigma0, sig
                                       float("inf") if cutoff is None else float(cutoff), 1 if fixed_sigma else 0,
                                       torch.cuda.current_stream().cuda_stream)
     _check(code, "molann_opes_step_f64")
+
+
+def opes_step_columns_f64(centers, sigma, heights, state, run, period, y, columns, V, sigma0, sigma_min, beta, threshold, cutoff=None,
+                          fixed_sigma=False):
+    """`molann_opes_step_columns_f64` on torch's current stream: `opes_step_f64` with walker a's centre read at ``y[a, columns[k]]`` of
+    `y` [W, n_out] (its row stride is passed on) and its bias at `V` ([W], or a column of a wider tensor: its stride is passed on).
+    `columns`: a ctypes array of d int32 (`_i32_array`), made once, or None for the first d outputs.  The tensors' shapes are the
+    caller's to check (`molann_amd.bias.OpesRun` does)."""
+    n_walkers = y.shape[0]
+    code = lib().molann_opes_step_columns_f64(centers.data_ptr(), sigma.data_ptr(), heights.data_ptr(), centers.shape[0], centers.shape[1],
+                                              _address(period), state.data_ptr(), run.data_ptr(), y.data_ptr(),
+                                              y.stride(0) if n_walkers > 1 else y.shape[1], columns, V.data_ptr(),
+                                              V.stride(0) if n_walkers > 1 else 1, n_walkers, sigma0.data_ptr(), _address(sigma_min), float(beta),
+                                              float(threshold), float("inf") if cutoff is None else float(cutoff), 1 if fixed_sigma else 0,
+                                              torch.cuda.current_stream().cuda_stream)
+    _check(code, "molann_opes_step_columns_f64")
 
 
 def metad_grid_arrays(shape, lower, spacing, periodic, sigma, columns):

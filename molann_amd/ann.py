@@ -924,7 +924,7 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
 # value_and_restraint / value_and_hills / value_and_grid / value_and_bias and PreprocessingANN.value_and_metric / value_and_restraint /
 # value_and_hills / value_and_grid / value_and_bias, and value_and_opes and value_and_opes_table of both.  What differs
 # between them, by kind; the checks and the two ways to the kernel are written once below.
-_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID, _BIAS, _OPES, _BIAS_OPES, _OPES_TABLE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+_VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID, _BIAS, _OPES, _BIAS_OPES, _OPES_TABLE, _BIAS_OPES_TABLE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 _HILLS_MAX_D_OUT = 8      # HILLS64_MAX_D_OUT of csrc/molann_value_f64.inc: the kernel's cotangent sums are a register array
 _JACOBIAN_ROUTE = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
 _METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
@@ -952,17 +952,23 @@ _HILLS_AND_OPES_ROUTE = ("`hills` and `opes` in one launch are not served: move 
 _OPES_TABLE_ROUTE = "read the table's state (`OpesTable.read_state`), then `value_and_opes` on `table.record(scale, S / n, epsilon)`, or: " + _OPES_ROUTE
 _OPES_TABLE_FEATURES_ROUTE = ("read the table's state (`OpesTable.read_state`), then `value_and_opes` on `table.record(scale, S / n, epsilon)`, or: "
                               + _OPES_FEATURES_ROUTE)
+# value_and_bias with an `OpesFromTable` (_BIAS_OPES_TABLE, a kernel of its own that reads the table's state): what remains where it refuses
+_BIAS_OPES_TABLE_ROUTE = ("read the table's state (`OpesTable.read_state`), then `value_and_bias(opes=table.record(scale, S / n, epsilon, columns))`, "
+                          "or: " + _BIAS_OPES_ROUTE)
+_BIAS_OPES_TABLE_FEATURES_ROUTE = ("read the table's state (`OpesTable.read_state`), then `value_and_bias(opes=table.record(scale, S / n, epsilon, "
+                                   "columns))`, or: " + _BIAS_OPES_FEATURES_ROUTE)
 _ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint", "value_and_hills", "value_and_grid",
-                    "value_and_bias", "value_and_opes", "value_and_bias", "value_and_opes_table")
+                    "value_and_bias", "value_and_opes", "value_and_bias", "value_and_opes_table", "value_and_bias")
 # the route that remains where the call refuses
 _ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE, _BIAS_ROUTE, _OPES_ROUTE, _BIAS_OPES_ROUTE,
-                     _OPES_TABLE_ROUTE)
+                     _OPES_TABLE_ROUTE, _BIAS_OPES_TABLE_ROUTE)
 _ONE_LAUNCH_FEATURES_ROUTE = (None, None, None, _RESTRAINT_FEATURES_ROUTE, _HILLS_FEATURES_ROUTE, _GRID_FEATURES_ROUTE, _BIAS_FEATURES_ROUTE,
-                              _OPES_FEATURES_ROUTE, _BIAS_OPES_FEATURES_ROUTE, _OPES_TABLE_FEATURES_ROUTE)
+                              _OPES_FEATURES_ROUTE, _BIAS_OPES_FEATURES_ROUTE, _OPES_TABLE_FEATURES_ROUTE, _BIAS_OPES_TABLE_FEATURES_ROUTE)
 _ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)", "(y, bias, dx)", "(y, energies, dx)", "(y, bias, dx)",
-                    "(y, energies, dx)", "(y, bias, dx)")   # what `into` holds
+                    "(y, energies, dx)", "(y, bias, dx)", "(y, energies, dx)")   # what `into` holds
 # the dispatcher operator, in MolANN._fast_state
-_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid", "op_bias", "op_opes", "op_bias_opes", "op_opes_table")
+_ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid", "op_bias", "op_opes", "op_bias_opes", "op_opes_table",
+                  "op_bias_opes_table")
 _BIAS_KINDS = (_RESTRAINT, _HILLS, _GRID)      # the calls that return (y, a scalar per frame, dx)
 
 
@@ -992,7 +998,7 @@ def _check_into_triple(name, x, into, out_dim, kind=_RESTRAINT):
     if any(t.dtype != torch.float64 for t in into):
         raise TypeError("%s: `into` must be float64 like x; got %s" % (name, ", ".join(str(t.dtype) for t in into)))
     n = x.shape[0]
-    per = 3 if kind == _BIAS else 4 if kind == _BIAS_OPES else 1
+    per = 3 if kind == _BIAS else 4 if kind in (_BIAS_OPES, _BIAS_OPES_TABLE) else 1
     counts = (n * out_dim, n * per, x.numel())
     if not all(t.is_contiguous() and t.numel() == c and t.device == x.device for t, c in zip(into, counts)):
         raise ValueError("%s: `into` must be contiguous {[%d, %d], %s, %s} on %s"
@@ -1189,9 +1195,10 @@ def _check_bias_terms(name, restraint, hills, grid, opes=None):
     construction has checked its `columns`), and at least one of them; `hills` and `opes` together: NotImplementedError naming the
     routes that remain."""
     for what, term, cls in (("restraint", restraint, _bias.Restraint), ("hills", hills, _bias.Hills), ("grid", grid, _bias.Grid),
-                            ("opes", opes, _bias.Opes)):
+                            ("opes", opes, (_bias.Opes, _bias.OpesFromTable))):
         if term is not None and not isinstance(term, cls):
-            raise TypeError("%s: `%s` must be None or a molann_amd.bias.%s; got %s" % (name, what, cls.__name__, type(term).__name__))
+            raise TypeError("%s: `%s` must be None or a molann_amd.bias.%s; got %s"
+                            % (name, what, cls.__name__ if isinstance(cls, type) else "Opes or OpesFromTable", type(term).__name__))
     if restraint is None and hills is None and grid is None and opes is None:
         raise ValueError("%s: at least one of `restraint`, `hills` and `grid` must be given" % name)
     if hills is not None and opes is not None:
@@ -1269,6 +1276,32 @@ def _check_bias_opes_args(name, x, out_dim, restraint, grid, opes, into, owner=N
     return (r, g, o) + _check_into_triple(name, x, into, out_dim, _BIAS_OPES)
 
 
+def _check_bias_opes_table_args(name, x, out_dim, restraint, grid, opes, into, owner=None):
+    """The checks of value_and_bias with an `OpesFromTable` after the gate, as `_check_bias_opes_args` makes them, all before any launch
+    and with nothing read back: the column lists against the model, then the restraint and the table by the checks of their single calls,
+    the record's table, scale and epsilon by `_check_opes_table_args` with the term's width ``table.d`` in place of the number of outputs,
+    then `into` with energies [N, 4].  The widths are not looked at: they are the deposits' and live in device memory.  Returns ((center,
+    kappa, period, flat) or None, (columns, table, lower, spacing, periodic) or None, (columns, centers, heights, sigma, state, period,
+    scale, epsilon, cutoff), y, energies, dx)."""
+    if not isinstance(opes.table, _bias.OpesTable):
+        raise TypeError("%s: `opes.table` must be a molann_amd.bias.OpesTable; got %s" % (name, type(opes.table).__name__))
+    width = opes.table.d
+    if opes.columns is not None and len(opes.columns) != width:      # a record changed through `_replace`
+        raise ValueError("%s: `opes.columns` must name one output per column of `opes.table` (%d); got %d" % (name, width, len(opes.columns)))
+    oc = _bias_columns(name, "opes", opes.columns, width, _bias.HILLS_MAX_COLUMNS, out_dim)
+    gc = None
+    if grid is not None:
+        gwidth = grid.table.dim() if isinstance(grid.table, torch.Tensor) and grid.columns is None else 1
+        gc = _bias_columns(name, "grid", grid.columns, gwidth, _bias.GRID_MAX_COLUMNS, out_dim)
+    r = g = None
+    if restraint is not None:
+        r = _check_restraint_args(name, x, out_dim, restraint.center, restraint.kappa, restraint.period, restraint.flat, None, owner=owner)[:4]
+    o = (oc,) + _check_opes_table_args(name, x, len(oc), opes.table, opes.scale, opes.epsilon, None, owner=owner)[:8]
+    if grid is not None:
+        g = (gc,) + _check_grid_args(name, x, len(gc), grid.table, grid.lower, grid.spacing, grid.periodic, None, owner=owner, unit="grid column")[:4]
+    return (r, g, o) + _check_into_triple(name, x, into, out_dim, _BIAS_OPES_TABLE)
+
+
 def _check_grad_out(name, x, out_dim, grad_out):
     if not isinstance(grad_out, torch.Tensor) or grad_out.numel() != x.shape[0] * out_dim or grad_out.device != x.device:
         raise ValueError("%s: grad_out must hold [%d, %d] values on %s" % (name, x.shape[0], out_dim, x.device))
@@ -1329,6 +1362,9 @@ def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=
     elif kind == _BIAS_OPES:
         checked = _check_bias_opes_args(name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:3], checked[3], (checked[4], checked[5]) if checked[3] is not None else None, (n, n_inp, 3)
+    elif kind == _BIAS_OPES_TABLE:
+        checked = _check_bias_opes_table_args(name, x, out_dim, *extra, into, owner=owner)
+        return x, checked[:3], checked[3], (checked[4], checked[5]) if checked[3] is not None else None, (n, n_inp, 3)
     elif kind == _OPES:
         checked = _check_opes_args(name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:8], checked[8], (checked[9], checked[10]) if checked[8] is not None else None, (n, n_inp, 3)
@@ -1360,6 +1396,9 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
         elif kind == _BIAS_OPES:
             if not plan.supports_value_and_bias_opes_f64():
                 raise NotImplementedError("value_and_bias: one frame's rows exceed the LDS of a compute unit for this model; " + _BIAS_OPES_ROUTE)
+        elif kind == _BIAS_OPES_TABLE:
+            if not plan.supports_value_and_bias_opes_table_f64():
+                raise NotImplementedError("value_and_bias: one frame's rows exceed the LDS of a compute unit for this model; " + _BIAS_OPES_TABLE_ROUTE)
         elif kind in _BIAS_KINDS or kind == _BIAS:
             if not (plan.supports_value_and_restraint_f64, plan.supports_value_and_hills_f64, plan.supports_value_and_grid_f64,
                     plan.supports_value_and_bias_f64)[kind - _RESTRAINT]():
@@ -1379,8 +1418,14 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
             second = torch.empty(shape, dtype=torch.float64, device=x.device)
             if kind in _BIAS_KINDS or kind == _OPES or kind == _OPES_TABLE:
                 second = (torch.empty((x.shape[0],), dtype=torch.float64, device=x.device), second)
-            if kind == _BIAS or kind == _BIAS_OPES:
+            if kind == _BIAS or kind == _BIAS_OPES or kind == _BIAS_OPES_TABLE:
                 second = (torch.empty((x.shape[0], 3 if kind == _BIAS else 4), dtype=torch.float64, device=x.device), second)
+        if kind == _BIAS_OPES_TABLE:
+            if x.shape[0] > 0:
+                plan.value_and_bias_opes_table_f64(x, [lin.weight.detach().contiguous() for lin in lins],
+                                                   [lin.bias.detach().contiguous() for lin in lins], y, *second, extra[2], restraint=extra[0],
+                                                   grid=extra[1])
+            return (y,) + tuple(second)
         if kind == _BIAS_OPES:
             if x.shape[0] > 0:
                 plan.value_and_bias_opes_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
@@ -1519,10 +1564,12 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
         `Hills` and `Grid`, as `MolANN.value_and_bias` takes them.  No autograd graph is recorded; ``into=(feat, energies, dx)``
         reuses the caller's buffers.  The same bits on every call.  ``opes``: a `molann_amd.bias.Opes` in the place of ``hills``, as
         `MolANN.value_and_bias` takes it (frames_value_bias_opes_f64_kernel, ``energies`` [N, 4] = ``(E_r, 0, V_g, V_o)``): OPES on two raw
-        dihedral angles of a module with any number of features, with walls and a periodic table next to it."""
+        dihedral angles of a module with any number of features, with walls and a periodic table next to it.  A
+        `molann_amd.bias.OpesFromTable` in its place reads the live count and the norm from the table's state on the device
+        (frames_value_bias_opes_table_f64_kernel), as `MolANN.value_and_bias` takes it."""
         _check_bias_terms("value_and_bias", restraint, hills, grid, opes)
         if opes is not None:
-            return self._bias_on_features(_BIAS_OPES, x, (restraint, grid, opes), into)
+            return self._bias_on_features(_BIAS_OPES_TABLE if isinstance(opes, _bias.OpesFromTable) else _BIAS_OPES, x, (restraint, grid, opes), into)
         return self._bias_on_features(_BIAS, x, (restraint, hills, grid), into)
 
     def value_and_opes(self, x, centers, heights, sigma, scale, norm, epsilon, cutoff=None, period=None, into=None):
@@ -1690,7 +1737,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
             r, h, g = extra
             return tuple(op(x, st["handle"], ref, W, B, *(r or (None,) * 4), *((list(h[0]),) + h[1:] if h else ([], None, None, None, None)),
                             *((list(g[0]),) + g[1:] if g else ([], None, [], [], [])), into))
-        if kind == _BIAS_OPES:
+        if kind == _BIAS_OPES or kind == _BIAS_OPES_TABLE:   # the same places in both operators: the record's fields follow its columns
             r, g, o = extra
             return tuple(op(x, st["handle"], ref, W, B, *(r or (None,) * 4), list(o[0]), *o[1:],
                             *((list(g[0]),) + g[1:] if g else ([], None, [], [], [])), into))
@@ -1808,7 +1855,8 @@ class MolANN(_PlanOwner, torch.nn.Module):
         and > 0 while n >= 1 gives NaN or inf for every frame: it is not guarded (`OpesTable.recompute_sum` restores S).  A NaN frame
         poisons its own outputs only.  No autograd graph is recorded; ``into=(y, bias, dx)`` reuses the caller's buffers.  The same
         bits on every call.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan with at most 8
-        outputs.  Out of scope: `value_and_bias` with ``opes=`` reading the state, float32, a `GraphedForces` wrapper."""
+        outputs (on some of a wider model's outputs, or with walls or a table next to it: `value_and_bias` with
+        ``opes=molann_amd.bias.OpesFromTable(...)``).  Out of scope: float32, a `GraphedForces` wrapper."""
         return self._one_launch_f64(_OPES_TABLE, self._one_launch_state(x, _OPES_TABLE, "float64"), x, (table, scale, epsilon), into)
 
     def value_and_grid(self, x, table, lower, spacing, periodic=None, into=None):
@@ -1873,10 +1921,21 @@ class MolANN(_PlanOwner, torch.nn.Module):
         log(epsilon)`` and no share of dx.  With ``opes`` alone on identity columns ``V_o`` and ``dx`` are `value_and_opes`', bit for
         bit.  ``hills`` and ``opes`` together: NotImplementedError - move the hills onto a table with
         `molann_amd.bias.add_hills_to_grid` and pass it as ``grid``, or make two calls.  Out of scope as well: more than one OPES term,
-        depositing or compressing kernels."""
+        depositing or compressing kernels.
+
+        ``opes`` may also be a `molann_amd.bias.OpesFromTable` ``(table, scale, epsilon, columns=None)``: the same term on an
+        `OpesTable` where it lives, the live count ``n = state[0]`` (held to ``[0, capacity]``) and ``norm = S / n`` read by the kernel
+        from the table's state in device memory as `value_and_opes_table` reads them (`molann_value_and_bias_opes_table_f64`,
+        frames_value_bias_opes_table_f64_kernel, one launch).  Nothing is read back - no ``read_state()``, no widths looked at - so the
+        call queues behind a deposit and is captured in a ``torch.cuda.graph`` while the table grows (`molann_amd.bias.OpesRun` with
+        ``columns``, ``walls`` or ``grid`` is that loop).  ``(y, energies [N, 4], dx)`` and ``into`` as with an `Opes`; for the same n
+        and norm they are the bits of ``opes=table.record(scale, S / n, epsilon, columns)``.  An empty table: ``V_o = scale
+        log(epsilon)`` and no share of dx, nothing of the table read.  ``table.d`` columns on x's device, ``scale`` finite and
+        ``epsilon`` finite and > 0, else ValueError before any launch; ``hills`` next to it: NotImplementedError as above."""
         _check_bias_terms("value_and_bias", restraint, hills, grid, opes)
         if opes is not None:
-            return self._one_launch_f64(_BIAS_OPES, self._one_launch_state(x, _BIAS_OPES, "float64"), x, (restraint, grid, opes), into)
+            kind = _BIAS_OPES_TABLE if isinstance(opes, _bias.OpesFromTable) else _BIAS_OPES
+            return self._one_launch_f64(kind, self._one_launch_state(x, kind, "float64"), x, (restraint, grid, opes), into)
         return self._one_launch_f64(_BIAS, self._one_launch_state(x, _BIAS, "float64"), x, (restraint, hills, grid), into)
 
     def _tangent_present(self, x):
@@ -1936,7 +1995,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
                 st["op_restraint"], st["op_hills"] = torch.ops.molann.value_and_restraint_h, torch.ops.molann.value_and_hills_h
                 st["op_grid"], st["op_bias"] = torch.ops.molann.value_and_grid_h, torch.ops.molann.value_and_bias_h
                 st["op_opes"], st["op_bias_opes"] = torch.ops.molann.value_and_opes_h, torch.ops.molann.value_and_bias_opes_h
-                st["op_opes_table"] = torch.ops.molann.value_and_opes_table_h
+                st["op_opes_table"], st["op_bias_opes_table"] = torch.ops.molann.value_and_opes_table_h, torch.ops.molann.value_and_bias_opes_table_h
                 from . import script
                 st["desc"] = script.make_desc(script.KIND_FORWARD, fl.input_atom_num,
                                               align_idx=al._local_align_atom_indices if al is not None else None,

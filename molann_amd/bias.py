@@ -12,7 +12,9 @@ points; `record` hands the live rows to `value_and_opes` / `value_and_bias` as a
 in plain torch, differentiable by autograd.  An `OpesRun` is the whole loop on the device: `bias` evaluates the model and the bias from the
 table's state (`MolANN.value_and_opes_table`), `deposit` turns those outputs into the step's kernels and deposits them - two launches
 per step, nothing read back, capturable in a graph.  With walls or a table next to it, or on some of a wider model's outputs, the kernel table
-goes into `MolANN.value_and_bias` as an `Opes` record.
+goes into `MolANN.value_and_bias` as an `OpesFromTable` record, whose kernel reads the table's state on the device as well -
+`OpesRun(columns=, walls=, grid=)` is that loop, still two launches per step - or, with the live count and the norm at hand on the host,
+as an `Opes` record.
 
 A metadynamics run on a table is a `MetadRun`, the same loop for hills: `bias` is `value_and_grid` (or `value_and_bias` with walls or on
 some of a wider model's outputs) on the table as it is, `deposit` adds the step's hills to the table on the device with well-tempered
@@ -25,7 +27,8 @@ import operator
 
 import torch
 
-__all__ = ["grid_points", "add_hills_to_grid", "opes_kernel_sum", "Restraint", "Hills", "Grid", "Opes", "OpesTable", "OpesRun", "MetadRun"]
+__all__ = ["grid_points", "add_hills_to_grid", "opes_kernel_sum", "Restraint", "Hills", "Grid", "Opes", "OpesTable", "OpesFromTable", "OpesRun",
+           "MetadRun"]
 
 HILLS_MAX_COLUMNS = 8     # HILLS_MAX_D of csrc/molann_math.h
 GRID_MAX_COLUMNS = 3      # GRID_MAX_D of csrc/molann_math.h
@@ -298,6 +301,24 @@ class OpesTable(object):
         return Opes(self.centers[:n], self.heights[:n], self.sigma[:n], scale, norm, epsilon, self.cutoff, self.period, columns)
 
 
+class OpesFromTable(collections.namedtuple("OpesFromTable", "table scale epsilon columns")):
+    """The OPES term of `MolANN.value_and_bias` read from an `OpesTable` where it lives: the kernel forms the live count and the
+    normalisation ``S / n`` from ``table.state`` in device memory (`molann_value_and_bias_opes_table_f64`), so nothing is read back and
+    the launch can be captured in a graph while the table grows - where `OpesTable.record` needs ``n`` and ``norm`` on the host.  The
+    kernels act on the outputs ``columns`` (``table.d`` distinct indices in any order; None: the first ``table.d``); ``scale``,
+    ``epsilon`` Python floats; the table's ``cutoff`` and ``period`` are used.  Immutable; the table is held, not copied."""
+    __slots__ = ()
+
+    def __new__(cls, table, scale, epsilon, columns=None):
+        if not isinstance(table, OpesTable):
+            raise TypeError("OpesFromTable: `table` must be an OpesTable; got %s" % type(table).__name__)
+        columns = _columns("OpesFromTable", columns, HILLS_MAX_COLUMNS, "form the kernel sum on `model(x)[:, columns]` with `opes_kernel_sum`, "
+                           "its logarithm and its derivative with torch, scatter it into a cotangent, then `value_and_vjp`")
+        if columns is not None and len(columns) != table.d:
+            raise ValueError("OpesFromTable: `columns` must name one output per column of `table` (%d); got %d" % (table.d, len(columns)))
+        return super().__new__(cls, table, scale, epsilon, columns)
+
+
 def _positive(name, what, v, allow_inf=False):
     """A scalar of OpesRun's constructor: a Python number (TypeError), finite - or +inf where allowed - and > 0 (ValueError)."""
     if isinstance(v, bool) or not isinstance(v, (int, float)):
@@ -319,19 +340,39 @@ class OpesRun(object):
     ``w prod_k(sigma0_k / sigma_k)``, and the deposit of the W kernels into ``table`` as `OpesTable.deposit` makes it.  ``run`` [8] on
     the table's device holds ``(counter, sum_w, sum_w2, neff, sigma_scale, rct, 0, 0)``.
 
-    ``model``: a `MolANN` (or `PreprocessingANN`) whose outputs are the table's ``d`` columns; ``table``: an `OpesTable` (its
+    With ``columns``, ``walls`` or ``grid`` the run has `MetadRun`'s surface: ``bias(x)`` is `MolANN.value_and_bias` with
+    ``restraint=walls, grid=grid, opes=OpesFromTable(table, scale, epsilon, columns)`` (frames_value_bias_opes_table_f64_kernel: the
+    state is read on the device there too) and returns ``(y, energies, dx)``, and ``deposit(y, energies)`` is
+    `molann_opes_step_columns_f64`, which reads the walkers' centres at ``y[:, columns]`` and their OPES bias at ``energies[:, 3]`` where
+    they are - the weights use that bias alone, not the walls or the grid.  Still two launches per step, nothing read back, one graph.
+    With all three None nothing changes, bit for bit.
+
+    ``model``: a `MolANN` (or `PreprocessingANN`) whose outputs are the table's ``d`` columns, or a wider one with ``columns``: the
+    ``table.d`` outputs the kernels act on, distinct, in any order; ``walls``: a `Restraint` on all outputs or None; ``grid``: a `Grid`
+    (a static table from an earlier run, on its own columns) or None; ``table``: an `OpesTable` (its
     ``period``, ``cutoff`` and ``threshold`` are used); ``kT`` > 0; ``biasfactor`` > 1 (+inf: ``scale = kT``); ``barrier`` > 0:
     ``scale = kT (1 - 1 / biasfactor)``, ``epsilon = exp(-barrier / scale)``, ``beta = 1 / kT``.  ``sigma0``, ``sigma_min``: [d]
     numbers or tensors, finite and > 0 (checked here, once: on the device a width that is not > 0 makes every kernel of a step
     invalid and refused).  A walker whose bias or outputs are not finite is counted in the table's ``refused`` and changes nothing
     else.  Out of scope: adaptive sigma, explore mode, walkers on several ranks, float32, a `GraphedForces` wrapper."""
 
-    def __init__(self, model, table, kT, biasfactor, barrier, sigma0, sigma_min=None, fixed_sigma=False):
+    def __init__(self, model, table, kT, biasfactor, barrier, sigma0, sigma_min=None, fixed_sigma=False, columns=None, walls=None, grid=None):
+        from . import _capi
         if not callable(getattr(model, "value_and_opes_table", None)):
             raise TypeError("OpesRun: `model` must be a MolANN or a PreprocessingANN (it has no `value_and_opes_table`); got %s"
                             % type(model).__name__)
+        if not (columns is None and walls is None and grid is None) and not callable(getattr(model, "value_and_bias", None)):
+            raise TypeError("OpesRun: with `columns`, `walls` or `grid` the `model` must be a MolANN or a PreprocessingANN (it has no "
+                            "`value_and_bias`); got %s" % type(model).__name__)
         if not isinstance(table, OpesTable):
             raise TypeError("OpesRun: `table` must be an OpesTable; got %s" % type(table).__name__)
+        columns = _columns("OpesRun", columns, HILLS_MAX_COLUMNS, "a kernel table has at most 8 columns")
+        if columns is not None and len(columns) != table.d:
+            raise ValueError("OpesRun: `columns` must name one output per column of `table` (%d); got %d" % (table.d, len(columns)))
+        if walls is not None and not isinstance(walls, Restraint):
+            raise TypeError("OpesRun: `walls` must be a Restraint or None; got %s" % type(walls).__name__)
+        if grid is not None and not isinstance(grid, Grid):
+            raise TypeError("OpesRun: `grid` must be a Grid or None; got %s" % type(grid).__name__)
         kT = _positive("OpesRun", "kT", kT)
         biasfactor = _positive("OpesRun", "biasfactor", biasfactor, allow_inf=True)
         barrier = _positive("OpesRun", "barrier", barrier)
@@ -363,16 +404,26 @@ class OpesRun(object):
         self.sigma0 = rows[0].to(table.centers.device).contiguous()
         self.sigma_min = None if rows[1] is None else rows[1].to(table.centers.device).contiguous()
         self.run = torch.zeros(8, dtype=torch.float64, device=table.centers.device)
+        self.columns, self.walls, self.grid = columns, walls, grid
+        self._plain = columns is None and walls is None and grid is None
+        self._opes = OpesFromTable(table, scale, epsilon, columns)
+        self._column_array = None if columns is None else _capi._i32_array(columns)
 
     def bias(self, x, into=None):
-        """``(y, bias, dx)`` of the walkers ``x`` under the table as it is now: `MolANN.value_and_opes_table`, one launch."""
-        return self.model.value_and_opes_table(x, self.table, self.scale, self.epsilon, into=into)
+        """The walkers ``x`` under the table as it is now, one launch: ``(y, bias, dx)`` of `MolANN.value_and_opes_table`, or - with
+        walls, a grid or columns - ``(y, energies, dx)`` of `MolANN.value_and_bias`, ``energies[:, 3]`` the OPES bias."""
+        if self._plain:
+            return self.model.value_and_opes_table(x, self.table, self.scale, self.epsilon, into=into)
+        return self.model.value_and_bias(x, restraint=self.walls, grid=self.grid, opes=self._opes, into=into)
 
     def deposit(self, y, bias):
-        """The step after `bias`: ``y`` [W, d] and ``bias`` [W] as that call returned them (read only).  One launch on the current
-        stream, nothing read back, returns None."""
+        """The step after `bias`, as that call returned them (read only): ``y`` [W, d] and ``bias`` [W]; with walls, a grid or columns
+        ``y`` [W, n_out] and ``bias`` [W] or the ``energies`` [W, 4], whose column 3 - the OPES bias alone, without the walls and the
+        grid, as OPES_METAD forms its weights - is read in place.  One launch on the current stream, nothing read back, returns None."""
         from . import _capi
         t = self.table
+        if not self._plain:
+            return self._deposit_columns(y, bias)
         if not (isinstance(y, torch.Tensor) and y.dim() == 2):
             raise ValueError("OpesRun.deposit: `y` must be a [W, %d] tensor" % t.d)
         n_walkers = y.shape[0]
@@ -383,6 +434,32 @@ class OpesRun(object):
         with torch.cuda.device(t.centers.device):
             _capi.opes_step_f64(t.centers, t.sigma, t.heights, t.state, self.run, t.period, y, bias, self.sigma0, self.sigma_min, self.beta,
                                 t.threshold, t.cutoff, self.fixed_sigma)
+        return None
+
+    def _deposit_columns(self, y, bias):
+        """`deposit` of a run with walls, a grid or columns: `molann_opes_step_columns_f64` on the strided outputs."""
+        from . import _capi
+        t = self.table
+        widest = t.d - 1 if self.columns is None else max(self.columns)
+        for what, v in (("y", y), ("bias", bias)):
+            if not isinstance(v, torch.Tensor):
+                raise TypeError("OpesRun.deposit: `%s` must be a tensor on %s; got %s" % (what, t.centers.device, type(v).__name__))
+            if v.dtype != torch.float64:
+                raise TypeError("OpesRun.deposit: `%s` must be float64; got %s" % (what, v.dtype))
+            if v.device != t.centers.device:
+                raise ValueError("OpesRun.deposit: `%s` must be on %s; got %s" % (what, t.centers.device, v.device))
+        if y.dim() != 2 or y.shape[1] <= widest:
+            raise ValueError("OpesRun.deposit: `y` must be [W, more than %d columns]; got %s" % (widest, list(y.shape)))
+        n_walkers = y.shape[0]
+        if tuple(bias.shape) not in ((n_walkers,), (n_walkers, 4)):
+            raise ValueError("OpesRun.deposit: `bias` must be [W] or the energies [W, 4]; got %s" % list(bias.shape))
+        if n_walkers == 0:
+            return None
+        y = y.detach().contiguous()
+        V = bias.detach() if bias.dim() == 1 else bias.detach()[:, 3]
+        with torch.cuda.device(t.centers.device):
+            _capi.opes_step_columns_f64(t.centers, t.sigma, t.heights, t.state, self.run, t.period, y, self._column_array, V, self.sigma0,
+                                        self.sigma_min, self.beta, t.threshold, t.cutoff, self.fixed_sigma)
         return None
 
     def read_run(self):

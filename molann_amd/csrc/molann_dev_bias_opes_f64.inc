@@ -1,7 +1,9 @@
 // molann_dev_bias_opes_f64.inc - part of libmolann_hip.so, included by molann_kernels.hip after molann_dev_bias_f64.inc and
 // molann_dev_opes_f64.inc.  Float64 values, an OPES bias on chosen outputs together with a harmonic restraint (walls) on all of them and a
 // tabulated bias on chosen outputs, and the gradient of their sum in one launch (molann_value_and_bias_opes_f64 launches it).  A kernel
-// instance of its own: frames_value_bias_f64_kernel and frames_value_opes_f64_kernel keep their code.
+// instance of its own: frames_value_bias_f64_kernel and frames_value_opes_f64_kernel keep their code.  The same kernel with n_kernels and
+// norm read from a device-resident table's state instead of the arguments: frames_value_bias_opes_table_f64_kernel of
+// molann_dev_bias_opes_table_f64.inc.
 // Out of scope: hills and OPES in one launch (two table walks and 16 more live accumulators in a kernel that sits at the register file's
 // end at G = 8; the caller moves the hills onto a table with molann_amd.bias.add_hills_to_grid, or makes two calls); more than one OPES
 // term; float32; a GraphedForces replay; depositing or compressing kernels; gradients with respect to tables or parameters.

@@ -2,9 +2,10 @@
 // two halves of an OPES run meet: frames_value_opes_table_f64_kernel evaluates the bias on a device-resident table whose live count and
 // normalisation it reads from the table's state (molann_value_and_opes_table_f64 launches it), and opes_step_f64_kernel turns the outputs
 // and biases that launch wrote into this step's kernels - weights, effective sample size, rescaled widths, heights - and deposits them
-// (molann_opes_step_f64).  Neither needs a value from the host, so the pair queues, and is captured in a graph, with no read-back.  Out of
-// scope: value_and_bias(opes=) reading the state (a second instance family; the argument layout here is kept so that it can follow);
-// adaptive sigma, the explore variant, walkers on several ranks; float32; a step on more than one block; a GraphedForces wrapper.
+// (molann_opes_step_f64).  Neither needs a value from the host, so the pair queues, and is captured in a graph, with no read-back.  The
+// same pair for a run with walls, a table or a wider model - value_and_bias(opes=) reading the state, and the step on strided outputs
+// and chosen columns - is molann_dev_bias_opes_table_f64.inc, which keeps this file's argument layout.  Out of scope: adaptive sigma,
+// the explore variant, walkers on several ranks; float32; a step on more than one block; a GraphedForces wrapper.
 namespace {
 
 // =============================================================================================

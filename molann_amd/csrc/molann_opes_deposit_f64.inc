@@ -2,7 +2,9 @@
 // molann_dev_opes_deposit_f64.inc (see include/molann_hip.h): molann_opes_deposit_f64 and molann_opes_kernel_sum_f64 check their
 // arguments and enqueue one launch each - no plan, no workspace, no event - and molann_selftest_opes_deposit_f64 runs the deposit on host
 // arrays through the same steps and the same per-kernel functions, with the device's order of every sum.  molann_opes_step_f64 (a whole
-// OPES step: opes_step_f64_kernel of molann_dev_opes_table_f64.inc) and its twin molann_selftest_opes_step_f64 follow the same pattern.
+// OPES step: opes_step_f64_kernel of molann_dev_opes_table_f64.inc) and its twin molann_selftest_opes_step_f64 follow the same pattern, and so
+// do molann_opes_step_columns_f64 (the step on strided outputs and chosen columns: opes_step_columns_f64_kernel of
+// molann_dev_bias_opes_table_f64.inc) and molann_selftest_opes_step_columns_f64.
 namespace {
 
 // the device's block on the host: the same strided partials, the same butterfly, the same order of the four waves
@@ -102,6 +104,52 @@ struct OpesStepHost : OpesDepositHost {
     }
 };
 
+// opes_step_columns_f64_kernel's executor on the host (OpesStepColumnsDev): OpesStepHost with walker a's centre gathered from
+// y[a * y_stride + col[k]] and its bias read at V[a * v_stride]
+struct OpesStepColumnsHost : OpesStepHost {       // its fields; new_centers is y
+    long y_stride, v_stride;
+    int col[HILLS_MAX_D];
+
+    void gather(long a, double (&yc)[HILLS_MAX_D]) const {
+        const double* row = new_centers + a * y_stride;
+        for (int k = 0; k < HILLS_MAX_D; ++k) yc[k] = k < d ? row[col[k]] : 0.0;
+    }
+    void walker_sums(long n_walkers, double& count, double& sum_w, double& sum_w2) const {
+        double pc[256], pw[256], pw2[256];
+        for (int t = 0; t < 256; ++t) {
+            pc[t] = pw[t] = pw2[t] = 0.0;
+            for (long a = t; a < n_walkers; a += 256) {
+                double w, yc[HILLS_MAX_D];
+                gather(a, yc);
+                if (opes_walker_weight_f64(beta, V[a * v_stride], yc, d, w)) opes_walker_add_f64(w, pc[t], pw[t], pw2[t]);
+            }
+        }
+        count = block_sum(pc);
+        sum_w = block_sum(pw);
+        sum_w2 = block_sum(pw2);
+    }
+    void load_new(long a, double (&c)[HILLS_MAX_D], double (&s)[HILLS_MAX_D], double& h) const {
+        gather(a, c);
+        for (int k = 0; k < HILLS_MAX_D; ++k) s[k] = k < d ? step_sigma[k] : 1.0;
+        h = opes_walker_height_f64(beta, V[a * v_stride], c, d, ratio);
+    }
+};
+
+// what molann_opes_step_columns_f64 and its host twin add to opes_step_arguments, after it: the strides (MOLANN_E_DESC), then the list -
+// d distinct indices in [0, y_stride), NULL for 0..d-1 (MOLANN_E_INDEX); then the list is in `cols`
+inline int opes_step_columns_arguments(int32_t d, int64_t y_stride, const int32_t* columns, int64_t v_stride, int (&cols)[HILLS_MAX_D]) {
+    if (y_stride < d || v_stride < 1) return MOLANN_E_DESC;
+    for (int k = 0; k < HILLS_MAX_D; ++k) cols[k] = 0;
+    for (int32_t j = 0; j < d; ++j) {
+        const int32_t cj = columns ? columns[j] : j;
+        if (cj < 0 || cj >= y_stride) return MOLANN_E_INDEX;
+        for (int32_t i = 0; i < j; ++i)
+            if (cols[i] == cj) return MOLANN_E_INDEX;
+        cols[j] = cj;
+    }
+    return MOLANN_OK;
+}
+
 // the arguments molann_opes_step_f64 and its host twin share, in molann_opes_deposit_f64's order of refusals
 inline int opes_step_arguments(const double* centers, const double* sigma, const double* heights, int64_t capacity, int32_t d, const double* period,
                                const double* state, const double* run, const double* y, const double* V, int64_t n_walkers, const double* sigma0,
@@ -182,6 +230,39 @@ int molann_selftest_opes_step_f64(double* centers, double* sigma, double* height
                                       cutoff);
     if (e != MOLANN_OK || n_walkers == 0) return e;
     OpesStepHost ex = {{centers, sigma, heights, period, y, nullptr, nullptr, (int)d}, V, beta, 1.0, {1., 1., 1., 1., 1., 1., 1., 1.}};
+    long n = opes_live_count_f64(state[0], (long)capacity);
+    double S = state[1], merges = state[2], refused = state[3];
+    double r[8] = {run[0], run[1], run[2], 0., 0., 0., 0., 0.};
+    opes_step_steps_f64(ex, (long)capacity, (int)d, period, (long)n_walkers, threshold, cutoff, beta, fixed_sigma != 0 ? 1 : 0, sigma0, sigma_min, n, S,
+                        merges, refused, r);
+    state[0] = (double)n; state[1] = S; state[2] = merges; state[3] = refused;
+    for (int i = 0; i < 8; ++i) run[i] = r[i];
+    return MOLANN_OK;
+}
+
+int molann_opes_step_columns_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
+                                 double* run, const double* y, int64_t y_stride, const int32_t* columns, const double* V, int64_t v_stride,
+                                 int64_t n_walkers, const double* sigma0, const double* sigma_min, double beta, double threshold, double cutoff,
+                                 int32_t fixed_sigma, molann_stream_t stream) {
+    int e = opes_step_arguments(centers, sigma, heights, capacity, d, period, state, run, y, V, n_walkers, sigma0, sigma_min, beta, threshold, cutoff);
+    OpesStepColumns cols;
+    if (e == MOLANN_OK) e = opes_step_columns_arguments(d, y_stride, columns, v_stride, cols.col);
+    if (e != MOLANN_OK || n_walkers == 0) return e;
+    hipLaunchKernelGGL(opes_step_columns_f64_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, centers, sigma, heights, (long)capacity, (int)d, period,
+                       state, run, y, (long)y_stride, cols, V, (long)v_stride, (long)n_walkers, sigma0, sigma_min, beta, threshold, cutoff,
+                       fixed_sigma != 0 ? 1 : 0);
+    return (int)hipGetLastError();
+}
+
+int molann_selftest_opes_step_columns_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period,
+                                          double* state, double* run, const double* y, int64_t y_stride, const int32_t* columns, const double* V,
+                                          int64_t v_stride, int64_t n_walkers, const double* sigma0, const double* sigma_min, double beta,
+                                          double threshold, double cutoff, int32_t fixed_sigma) {
+    int e = opes_step_arguments(centers, sigma, heights, capacity, d, period, state, run, y, V, n_walkers, sigma0, sigma_min, beta, threshold, cutoff);
+    OpesStepColumnsHost ex = {{{centers, sigma, heights, period, y, nullptr, nullptr, (int)d}, V, beta, 1.0, {1., 1., 1., 1., 1., 1., 1., 1.}},
+                              (long)y_stride, (long)v_stride, {0, 0, 0, 0, 0, 0, 0, 0}};
+    if (e == MOLANN_OK) e = opes_step_columns_arguments(d, y_stride, columns, v_stride, ex.col);
+    if (e != MOLANN_OK || n_walkers == 0) return e;
     long n = opes_live_count_f64(state[0], (long)capacity);
     double S = state[1], merges = state[2], refused = state[3];
     double r[8] = {run[0], run[1], run[2], 0., 0., 0., 0., 0.};

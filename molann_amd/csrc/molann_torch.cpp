@@ -1339,6 +1339,136 @@ std::vector<at::Tensor> value_and_bias_opes_h_hip(const at::Tensor& x_in, int64_
     return value_and_bias_opes_impl(x_in, *desc_of(handle, "molann::value_and_bias_opes_h"), MOLANN_BIAS_OPES_OP_ARGS);
 }
 
+// {out, energies, grad_x}: value_and_bias_opes on a kernel table whose live count and normalisation the kernel reads from `state` [4] in
+// device memory (molann_value_and_bias_opes_table_f64): centers [capacity, opes columns], heights [capacity], sigma [capacity, opes columns]
+// are the table's storage, checked as value_and_opes_table checks them - contiguous float64 on x's device and read where they are (no copy:
+// a later step writes them); the restraint and the grid as value_and_bias_opes takes them; scale, epsilon and cutoff (inf: none) are host
+// values, checked here as the C entry checks them.  `into`: none or {out, energies, grad_x}.
+std::vector<at::Tensor> value_and_bias_opes_table_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                                       const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                                                       const c10::optional<at::Tensor>& center_in, const c10::optional<at::Tensor>& kappa_in,
+                                                       const c10::optional<at::Tensor>& rperiod_in, const c10::optional<at::Tensor>& flat_in,
+                                                       const std::vector<int64_t>& opes_columns, const at::Tensor& centers_in,
+                                                       const at::Tensor& heights_in, const at::Tensor& sigma_in, const at::Tensor& state_in,
+                                                       const c10::optional<at::Tensor>& operiod_in, double scale, double epsilon, double cutoff,
+                                                       const std::vector<int64_t>& grid_columns, const c10::optional<at::Tensor>& table_in,
+                                                       const std::vector<double>& lower, const std::vector<double>& spacing,
+                                                       const c10::List<bool>& periodic_in, const std::vector<at::Tensor>& into) {
+    const char* const op = "molann::value_and_bias_opes_table";
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_bias_opes_table is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_bias_opes_table: a forward or a features description");
+    TORCH_CHECK_VALUE(std::isfinite(scale) && std::isfinite(epsilon) && epsilon > 0.0 && cutoff > 0.0,
+                      "molann::value_and_bias_opes_table: `scale` must be finite, `epsilon` finite and > 0, `cutoff` > 0 (inf: none); got ", scale, ", ",
+                      epsilon, ", ", cutoff);
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    const bool has_r = kappa_in.has_value() && kappa_in->defined(), has_g = !grid_columns.empty();
+    TORCH_CHECK_VALUE(!opes_columns.empty(), "molann::value_and_bias_opes_table: `opes_columns` must name at least one output");
+    const std::vector<int32_t> oc = bias_columns("opes_columns", opes_columns, 8, cols), gc = bias_columns("grid_columns", grid_columns, 3, cols);
+    const int64_t dop = (int64_t)oc.size(), dg = (int64_t)gc.size();
+    molann_bias_terms_f64 t;
+    molann_opes_table_term_f64 o;
+    memset(&t, 0, sizeof(t));
+    memset(&o, 0, sizeof(o));
+    at::Tensor center, kappa, rperiod, flat, table;
+    if (has_r) {
+        center = bias_tensor("center", center_in, x, true); kappa = bias_tensor("kappa", kappa_in, x, true);
+        rperiod = bias_tensor("restraint_period", rperiod_in, x, false); flat = bias_tensor("flat", flat_in, x, false);
+        const bool per_frame = center.dim() == 2 && center.size(0) == n && center.size(1) == cols;
+        TORCH_CHECK_VALUE(per_frame || (center.dim() == 1 && center.size(0) == cols), "molann::value_and_bias_opes_table: `center` must be [", cols,
+                          "] or [N, out_dim]");
+        TORCH_CHECK_VALUE(kappa.dim() == 1 && kappa.size(0) == cols && (!rperiod.defined() || (rperiod.dim() == 1 && rperiod.size(0) == cols)) &&
+                              (!flat.defined() || (flat.dim() == 1 && flat.size(0) == cols)),
+                          "molann::value_and_bias_opes_table: `kappa`, `restraint_period` and `flat` must be [", cols, "]");
+        t.center = center.data_ptr<double>(); t.center_stride = per_frame ? cols : 0; t.kappa = kappa.data_ptr<double>();
+        t.restraint_period = rperiod.defined() ? rperiod.data_ptr<double>() : nullptr;
+        t.flat = flat.defined() ? flat.data_ptr<double>() : nullptr;
+    }
+    TORCH_CHECK_VALUE(centers_in.dim() == 2 && centers_in.size(0) >= 1 && centers_in.size(1) == dop,
+                      "molann::value_and_bias_opes_table: `centers` must be [capacity >= 1, opes columns]");
+    const int64_t cap = centers_in.size(0);
+    // `written`: the table is read where it lives, so it must be contiguous as it is
+    const at::Tensor centers = opes_tensor(op, "centers", centers_in, x, true, "[capacity, opes columns]", true);
+    const at::Tensor heights = opes_tensor(op, "heights", heights_in, x, heights_in.dim() == 1 && heights_in.size(0) == cap, "[capacity]", true);
+    const at::Tensor sigma = opes_tensor(op, "sigma", sigma_in, x, sigma_in.dim() == 2 && sigma_in.size(0) == cap && sigma_in.size(1) == dop,
+                                         "[capacity, opes columns]", true);
+    const at::Tensor state = opes_tensor(op, "state", state_in, x, state_in.dim() == 1 && state_in.size(0) == 4, "[4]", true);
+    at::Tensor operiod;
+    if (operiod_in.has_value() && operiod_in->defined())
+        operiod = opes_tensor(op, "period", *operiod_in, x, operiod_in->dim() == 1 && operiod_in->size(0) == dop, "[opes columns]", false);
+    o.n_columns = (int32_t)dop; o.columns = oc.data(); o.capacity = cap;
+    o.centers = centers.data_ptr<double>(); o.heights = heights.data_ptr<double>(); o.sigma = sigma.data_ptr<double>();
+    o.state = state.data_ptr<double>(); o.period = operiod.defined() ? operiod.data_ptr<double>() : nullptr;
+    o.scale = scale; o.epsilon = epsilon; o.cutoff = cutoff;
+    int64_t shape[3] = {4, 4, 4};
+    int32_t periodic[3] = {0, 0, 0};
+    if (has_g) {
+        table = bias_tensor("table", table_in, x, true);
+        TORCH_CHECK_VALUE(table.dim() == dg && table_in->is_contiguous(), "molann::value_and_bias_opes_table: `table` must be contiguous with one "
+                          "dimension per grid column (", dg, ")");
+        TORCH_CHECK_VALUE((int64_t)lower.size() == dg && (int64_t)spacing.size() == dg && (periodic_in.size() == 0 || (int64_t)periodic_in.size() == dg),
+                          "molann::value_and_bias_opes_table: `lower`, `spacing` and `periodic` must hold one value per grid column (", dg, ")");
+        for (int64_t k = 0; k < dg; ++k) {
+            shape[k] = table.size(k);
+            TORCH_CHECK_VALUE(shape[k] >= 4, "molann::value_and_bias_opes_table: every dimension of `table` must have at least 4 points (got ", shape[k],
+                              ")");
+            TORCH_CHECK_VALUE(std::isfinite(spacing[k]) && spacing[k] > 0.0 && std::isfinite(lower[k]),
+                              "molann::value_and_bias_opes_table: `spacing` must be finite and > 0 and `lower` finite");
+            periodic[k] = periodic_in.size() > 0 && periodic_in.get(k) ? 1 : 0;
+        }
+        TORCH_CHECK_VALUE(table.numel() < (int64_t(1) << 31), "molann::value_and_bias_opes_table: `table` must hold fewer than 2^31 points");
+        t.n_grid_columns = (int32_t)dg; t.grid_columns = gc.data(); t.table = table.data_ptr<double>();
+        t.shape = shape; t.lower = lower.data(); t.spacing = spacing.data(); t.periodic = periodic;
+    }
+    TORCH_CHECK(into.empty() || into.size() == 3, "molann::value_and_bias_opes_table: `into` must be a triple of tensors (out, energies, grad_x)");
+    at::Tensor out, energies, gx;
+    if (into.empty()) {
+        out = at::empty({n, cols}, x.options()); energies = at::empty({n, 4}, x.options()); gx = at::empty_like(x);
+    } else {
+        out = into[0]; energies = into[1]; gx = into[2];
+        const int64_t counts[3] = {n * cols, 4 * n, x.numel()};
+        for (int i = 0; i < 3; ++i) {
+            TORCH_CHECK_TYPE(into[i].scalar_type() == at::kDouble, "molann::value_and_bias_opes_table: `into` must be float64 like x");
+            TORCH_CHECK_VALUE(into[i].is_contiguous() && into[i].numel() == counts[i] && into[i].device() == x.device(),
+                              "molann::value_and_bias_opes_table: `into` must be contiguous {[N, out_dim], [N, 4], [N, n_inp, 3]} on x's device");
+        }
+    }
+    F64Linears lin;
+    f64_linears(op, *e, x, weights, biases, lin, ": call .double()");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_bias_opes_table_f64(e->plan) == 1,
+                                "molann::value_and_bias_opes_table: one frame's rows exceed the LDS of a compute unit for this model; use run, form "
+                                "the terms on the chosen columns with torch, then value_and_vjp");
+    if (n == 0) return {out, energies, gx};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_bias_opes_table_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), &t, &o, out.data_ptr<double>(),
+                                               energies.data_ptr<double>(), gx.data_ptr<double>(), stream),
+          "molann_value_and_bias_opes_table_f64");
+    return {out, energies, gx};
+}
+#define MOLANN_BIAS_OPES_TABLE_OP_PARAMS                                                                                                             \
+    const at::Tensor &ref_x, std::vector<at::Tensor> weights, std::vector<at::Tensor> biases, const c10::optional<at::Tensor>&center,                \
+        const c10::optional<at::Tensor>&kappa, const c10::optional<at::Tensor>&rperiod, const c10::optional<at::Tensor>&flat,                        \
+        std::vector<int64_t> opes_columns, const at::Tensor &centers, const at::Tensor &heights, const at::Tensor &sigma, const at::Tensor &state,   \
+        const c10::optional<at::Tensor>&operiod, double scale, double epsilon, double cutoff, std::vector<int64_t> grid_columns,                     \
+        const c10::optional<at::Tensor>&table, std::vector<double> lower, std::vector<double> spacing, c10::List<bool> periodic,                     \
+        std::vector<at::Tensor> into
+#define MOLANN_BIAS_OPES_TABLE_OP_ARGS                                                                                                               \
+    ref_x, weights, biases, center, kappa, rperiod, flat, opes_columns, centers, heights, sigma, state, operiod, scale, epsilon, cutoff,             \
+        grid_columns, table, lower, spacing, periodic, into
+std::vector<at::Tensor> value_and_bias_opes_table_hip(const at::Tensor& x_in, std::vector<int64_t> desc, MOLANN_BIAS_OPES_TABLE_OP_PARAMS) {
+    return value_and_bias_opes_table_impl(x_in, desc, MOLANN_BIAS_OPES_TABLE_OP_ARGS);
+}
+std::vector<at::Tensor> value_and_bias_opes_table_h_hip(const at::Tensor& x_in, int64_t handle, MOLANN_BIAS_OPES_TABLE_OP_PARAMS) {
+    return value_and_bias_opes_table_impl(x_in, *desc_of(handle, "molann::value_and_bias_opes_table_h"), MOLANN_BIAS_OPES_TABLE_OP_ARGS);
+}
+
 // The fused forward that also keeps the features: {out, features} - or {out, empty} where the plan has no such twin of its
 // kernel (molann_plan_backward_kind != 1 ... != 2 plans recompute in molann_backward_f32).  float32 fused plans.
 std::vector<at::Tensor> run_train_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -1990,6 +2120,14 @@ TORCH_LIBRARY(molann, m) {
     m.def("value_and_bias_opes(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, Tensor? restraint_period, "
           "Tensor? flat, int[] opes_columns, Tensor centers, Tensor heights, Tensor sigma, Tensor? opes_period, float scale, float norm, float epsilon, "
           "float cutoff, int[] grid_columns, Tensor? table, float[] lower, float[] spacing, bool[] periodic, Tensor[] into) -> Tensor[]");
+    m.def("value_and_bias_opes_table_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, "
+          "Tensor? restraint_period, Tensor? flat, int[] opes_columns, Tensor centers, Tensor heights, Tensor sigma, Tensor state, Tensor? opes_period, "
+          "float scale, float epsilon, float cutoff, int[] grid_columns, Tensor? table, float[] lower, float[] spacing, bool[] periodic, "
+          "Tensor[] into) -> Tensor[]");
+    m.def("value_and_bias_opes_table(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, "
+          "Tensor? restraint_period, Tensor? flat, int[] opes_columns, Tensor centers, Tensor heights, Tensor sigma, Tensor state, Tensor? opes_period, "
+          "float scale, float epsilon, float cutoff, int[] grid_columns, Tensor? table, float[] lower, float[] spacing, bool[] periodic, "
+          "Tensor[] into) -> Tensor[]");
     m.def("opes_deposit(Tensor(a!) centers, Tensor(b!) sigma, Tensor(c!) heights, Tensor(d!) state, Tensor? period, Tensor new_centers, "
           "Tensor new_sigma, Tensor new_heights, float threshold, float cutoff) -> ()");
     m.def("value_and_opes_table_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor centers, Tensor heights, Tensor sigma, "
@@ -2037,6 +2175,8 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_bias_h", value_and_bias_h_hip);
     m.impl("value_and_bias_opes", value_and_bias_opes_hip);
     m.impl("value_and_bias_opes_h", value_and_bias_opes_h_hip);
+    m.impl("value_and_bias_opes_table", value_and_bias_opes_table_hip);
+    m.impl("value_and_bias_opes_table_h", value_and_bias_opes_table_h_hip);
     m.impl("opes_deposit", opes_deposit_hip);
     m.impl("value_and_opes_table", value_and_opes_table_hip);
     m.impl("value_and_opes_table_h", value_and_opes_table_h_hip);

@@ -6,8 +6,9 @@
 // molann_dev_hills_f64.inc), molann_value_and_grid_f64 (frames_value_grid_f64_kernel, molann_dev_grid_f64.inc),
 // molann_value_and_bias_f64 (frames_value_bias_f64_kernel, molann_dev_bias_f64.inc), molann_value_and_opes_f64
 // (frames_value_opes_f64_kernel, molann_dev_opes_f64.inc), molann_value_and_bias_opes_f64 (frames_value_bias_opes_f64_kernel,
-// molann_dev_bias_opes_f64.inc) and molann_value_and_opes_table_f64 (frames_value_opes_table_f64_kernel, molann_dev_opes_table_f64.inc).
-// One argument front end, one launch and one dispatch over the lane group serve the ten; an entry names its kernel, its pointers and
+// molann_dev_bias_opes_f64.inc), molann_value_and_opes_table_f64 (frames_value_opes_table_f64_kernel, molann_dev_opes_table_f64.inc) and
+// molann_value_and_bias_opes_table_f64 (frames_value_bias_opes_table_f64_kernel, molann_dev_bias_opes_table_f64.inc).
+// One argument front end, one launch and one dispatch over the lane group serve the eleven; an entry names its kernel, its pointers and
 // its rows.
 namespace {
 
@@ -97,6 +98,7 @@ inline void f64_entry_rows(const molann_plan* p, GridF64Args& a) { restraint64_r
 inline void f64_entry_rows(const molann_plan* p, BiasF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }
 inline void f64_entry_rows(const molann_plan* p, OpesF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }   // the hills' rows, geometry and cap: F64_HILLS
 inline void f64_entry_rows(const molann_plan* p, BiasOpesF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }   // the bias' rows and geometry: F64_BIAS
+inline void f64_entry_rows(const molann_plan* p, BiasOpesTableF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }   // as BiasOpesF64Args: F64_BIAS
 inline void f64_entry_rows(const molann_plan* p, OpesTableF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }   // as OpesF64Args: F64_HILLS
 
 // geometry for this entry: the forces' rows, the restraint's (the hills' and the grid's too), the bias' or the Jacobian's, and the
@@ -282,6 +284,41 @@ inline int bias_columns_f64(int32_t count, const int32_t* list, int cap, int d_o
     if (count > cap) return MOLANN_E_UNSUPPORTED;
     if (!list && count > d_out) return MOLANN_E_INDEX;
     for (int j = 0; j < cap; ++j) cols[j] = j < count ? (list ? list[j] : j) : 0;
+    return MOLANN_OK;
+}
+
+// one frame of molann_value_and_bias_opes_f64 on the host once its scalars are accepted: the grid, the lists, then the terms in the
+// kernel's order (the two host twins share it)
+inline int host_bias_opes_frame_f64(const double* y, int d_out, const molann_bias_terms_f64* t, const molann_opes_term_f64* o, double* energies,
+                                    double* dy) {
+    const bool has_r = t && t->kappa, has_g = t && t->n_grid_columns > 0;
+    int oc[HILLS_MAX_D], gc[GRID_MAX_D], per[GRID_MAX_D];
+    long gn[GRID_MAX_D];
+    double lo[GRID_MAX_D], gh[GRID_MAX_D];
+    if (!grid_geometry_f64(has_g ? t->n_grid_columns : 0, has_g ? t->shape : nullptr, has_g ? t->lower : nullptr, has_g ? t->spacing : nullptr,
+                           has_g ? t->periodic : nullptr, gn, lo, gh, per))
+        return MOLANN_E_DESC;
+    if (t && t->n_hills_columns != 0) return MOLANN_E_UNSUPPORTED;
+    int rc = bias_columns_f64(o->n_columns, o->columns, HILLS_MAX_D, d_out, oc);
+    if (rc == MOLANN_OK) rc = bias_columns_f64(has_g ? t->n_grid_columns : 0, has_g ? t->grid_columns : nullptr, GRID_MAX_D, d_out, gc);
+    if (rc != MOLANN_OK) return rc;
+    const int n_gc = has_g ? t->n_grid_columns : 0;
+    double ysel[BIAS_SEL] = {}, dvo[HILLS_MAX_D] = {}, dg[GRID_MAX_D] = {};
+    for (int j = 0; j < o->n_columns; ++j) ysel[j] = y[oc[j]];
+    for (int j = 0; j < n_gc; ++j) ysel[HILLS_MAX_D + j] = y[gc[j]];
+    double e = 0., vg = 0.;
+    for (int k = 0; k < d_out; ++k) {
+        dy[k] = 0.;
+        if (has_r)
+            e += restraint_term_f64(y[k], t->center[k], t->kappa[k], t->restraint_period ? t->restraint_period[k] : 0.0, t->flat ? t->flat[k] : 0.0,
+                                    dy[k]);
+    }
+    const double vo = host_opes_f64(ysel, o->n_columns, o->centers, o->heights, o->n_kernels, o->sigma, o->sigma_stride, o->period, o->scale, o->norm,
+                                    o->epsilon, o->cutoff, dvo);
+    if (has_g) vg = host_grid_f64(ysel + HILLS_MAX_D, n_gc, t->table, t->shape, t->lower, t->spacing, t->periodic, dg);
+    for (int j = 0; j < o->n_columns; ++j) dy[oc[j]] += dvo[j];
+    for (int j = 0; j < n_gc; ++j) dy[gc[j]] += dg[j];
+    energies[0] = e; energies[1] = 0.; energies[2] = vg; energies[3] = vo;
     return MOLANN_OK;
 }
 
@@ -516,6 +553,50 @@ int molann_value_and_bias_opes_f64(molann_plan* p, const double* x, int64_t n, c
                             energies, grad_x);
 }
 
+int molann_plan_supports_value_and_bias_opes_table_f64(const molann_plan* p) { return molann_plan_supports_value_and_bias_f64(p); }
+
+int molann_value_and_bias_opes_table_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b,
+                                         const molann_bias_terms_f64* t, const molann_opes_table_term_f64* o, double* out, double* energies,
+                                         double* grad_x, molann_stream_t stream) {
+    if (p && !o) return MOLANN_E_NULL;
+    // the host arrays of a present table are required pointers, as molann_value_and_bias_f64 has them
+    if (p && n > 0 && t && t->n_grid_columns > 0 && (!t->shape || !t->lower || !t->spacing)) return MOLANN_E_NULL;
+    F64Call<BiasOpesTableF64Args> c;
+    // An absent restraint or table has none of its pointers looked at (x stands in for them below).  The kernel table has storage whatever
+    // its live count, which only the device knows: its three pointers and the state are required, as molann_value_and_opes_table_f64 has
+    // them.  The hills' pointers of `t` are never looked at: hills are refused below.
+    const bool has_r = t && t->kappa, has_g = t && t->n_grid_columns > 0;
+    const int e = f64_entry_arguments(p, F64_BIAS, n,
+                                      {x, out, energies, grad_x, has_r ? t->center : x, o ? o->centers : x, o ? o->heights : x, o ? o->sigma : x,
+                                       o ? o->state : x, has_g ? t->table : x},
+                                      {has_r ? t->kappa : nullptr, has_r ? t->restraint_period : nullptr, has_r ? t->flat : nullptr,
+                                       o ? o->period : nullptr},      // kappa is there where the restraint is: its alignment is what is left to check
+                                      W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    BiasOpesTableF64Args& a = c.a;
+    if (o->n_columns <= 0 || (t && t->n_grid_columns < 0)) return MOLANN_E_DESC;
+    if (has_r && t->center_stride != 0 && t->center_stride != a.d_out) return MOLANN_E_DESC;
+    if (o->capacity < 1) return MOLANN_E_DESC;
+    if (!opes_table_scalars_f64(o->scale, o->epsilon, o->cutoff)) return MOLANN_E_DESC;
+    if (!grid_geometry_f64(has_g ? t->n_grid_columns : 0, has_g ? t->shape : nullptr, has_g ? t->lower : nullptr, has_g ? t->spacing : nullptr,
+                           has_g ? t->periodic : nullptr, a.n, a.lower, a.h, a.periodic))
+        return MOLANN_E_DESC;
+    if (t && t->n_hills_columns != 0) return MOLANN_E_UNSUPPORTED;   // hills and OPES in one launch: out of scope
+    int rc = bias_columns_f64(o->n_columns, o->columns, HILLS_MAX_D, a.d_out, a.oc);
+    if (rc == MOLANN_OK) rc = bias_columns_f64(has_g ? t->n_grid_columns : 0, has_g ? t->grid_columns : nullptr, GRID_MAX_D, a.d_out, a.gc);
+    if (rc != MOLANN_OK) return rc;
+    a.has_restraint = has_r ? 1 : 0;
+    a.n_oc = o->n_columns; a.n_gc = has_g ? t->n_grid_columns : 0;
+    a.center_stride = has_r ? (long)t->center_stride : 0;
+    a.capacity = (long)o->capacity;
+    a.scale = o->scale; a.epsilon = o->epsilon; a.cutoff = o->cutoff;
+    const double* none = nullptr;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_bias_opes_table_f64_kernel, c.g.G), "frames_value_bias_opes_table_f64_kernel",
+                            "bias + opes from the table's state", p, c, stream, x, has_r ? t->center : none, has_r ? t->kappa : none,
+                            has_r ? t->restraint_period : none, has_r ? t->flat : none, o->centers, o->heights, o->sigma, o->state, o->period,
+                            has_g ? t->table : none, out, energies, grad_x);
+}
+
 double molann_selftest_act_derivative_f64(int act, double z) { return act_derivative_f64(act, z); }
 
 double molann_selftest_restraint_f64(double y, double z, double kappa, double period, double flat, double* dy) {
@@ -603,34 +684,25 @@ int molann_selftest_bias_opes_f64(const double* y, int d_out, const molann_bias_
     if (d_out < 1 || o->n_columns <= 0 || o->n_kernels < 0 || (t && t->n_grid_columns < 0)) return MOLANN_E_DESC;
     if (o->sigma_stride != 0 && o->sigma_stride != o->n_columns) return MOLANN_E_DESC;
     if (!opes_scalars_f64(o->scale, o->norm, o->epsilon, o->cutoff)) return MOLANN_E_DESC;
-    int oc[HILLS_MAX_D], gc[GRID_MAX_D], per[GRID_MAX_D];
-    long gn[GRID_MAX_D];
-    double lo[GRID_MAX_D], gh[GRID_MAX_D];
-    if (!grid_geometry_f64(has_g ? t->n_grid_columns : 0, has_g ? t->shape : nullptr, has_g ? t->lower : nullptr, has_g ? t->spacing : nullptr,
-                           has_g ? t->periodic : nullptr, gn, lo, gh, per))
-        return MOLANN_E_DESC;
-    if (t && t->n_hills_columns != 0) return MOLANN_E_UNSUPPORTED;
-    int rc = bias_columns_f64(o->n_columns, o->columns, HILLS_MAX_D, d_out, oc);
-    if (rc == MOLANN_OK) rc = bias_columns_f64(has_g ? t->n_grid_columns : 0, has_g ? t->grid_columns : nullptr, GRID_MAX_D, d_out, gc);
-    if (rc != MOLANN_OK) return rc;
-    const int n_gc = has_g ? t->n_grid_columns : 0;
-    double ysel[BIAS_SEL] = {}, dvo[HILLS_MAX_D] = {}, dg[GRID_MAX_D] = {};
-    for (int j = 0; j < o->n_columns; ++j) ysel[j] = y[oc[j]];
-    for (int j = 0; j < n_gc; ++j) ysel[HILLS_MAX_D + j] = y[gc[j]];
-    double e = 0., vg = 0.;
-    for (int k = 0; k < d_out; ++k) {
-        dy[k] = 0.;
-        if (has_r)
-            e += restraint_term_f64(y[k], t->center[k], t->kappa[k], t->restraint_period ? t->restraint_period[k] : 0.0, t->flat ? t->flat[k] : 0.0,
-                                    dy[k]);
-    }
-    const double vo = host_opes_f64(ysel, o->n_columns, o->centers, o->heights, o->n_kernels, o->sigma, o->sigma_stride, o->period, o->scale, o->norm,
-                                    o->epsilon, o->cutoff, dvo);
-    if (has_g) vg = host_grid_f64(ysel + HILLS_MAX_D, n_gc, t->table, t->shape, t->lower, t->spacing, t->periodic, dg);
-    for (int j = 0; j < o->n_columns; ++j) dy[oc[j]] += dvo[j];
-    for (int j = 0; j < n_gc; ++j) dy[gc[j]] += dg[j];
-    energies[0] = e; energies[1] = 0.; energies[2] = vg; energies[3] = vo;
-    return MOLANN_OK;
+    return host_bias_opes_frame_f64(y, d_out, t, o, energies, dy);
+}
+
+int molann_selftest_bias_opes_table_f64(const double* y, int d_out, const molann_bias_terms_f64* t, const molann_opes_table_term_f64* o,
+                                        double* energies, double* dy) {
+    if (!y || !o || !energies || !dy) return MOLANN_E_NULL;
+    const bool has_r = t && t->kappa, has_g = t && t->n_grid_columns > 0;
+    if ((has_r && !t->center) || !o->centers || !o->heights || !o->sigma || !o->state ||
+        (has_g && (!t->table || !t->shape || !t->lower || !t->spacing)))
+        return MOLANN_E_NULL;
+    if (d_out < 1 || o->n_columns <= 0 || (t && t->n_grid_columns < 0)) return MOLANN_E_DESC;
+    if (o->capacity < 1) return MOLANN_E_DESC;
+    if (!opes_table_scalars_f64(o->scale, o->epsilon, o->cutoff)) return MOLANN_E_DESC;
+    // n and norm as frames_value_bias_opes_table_f64_kernel forms them, a row of widths per kernel; the norm goes on as it comes
+    const long n = opes_live_count_f64(o->state[0], (long)o->capacity);
+    const double norm = n > 0 ? opes_table_norm_f64(o->state[1], n) : 1.0;
+    const molann_opes_term_f64 term = {o->n_columns, o->columns, o->centers, o->heights, (int64_t)n, o->sigma, (int64_t)o->n_columns, o->period,
+                                       o->scale, norm, o->epsilon, o->cutoff};
+    return host_bias_opes_frame_f64(y, d_out, t, &term, energies, dy);
 }
 
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* a, double* jac36) {
