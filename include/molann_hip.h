@@ -603,8 +603,8 @@ int molann_plan_supports_value_and_opes_table_f64(const molann_plan* plan);
  * n_walkers > 0: MOLANN_E_NULL; a pointer that is not 8-byte aligned (period and sigma_min too): MOLANN_E_ALIGNMENT; d outside 1..8,
  * capacity < 1, n_walkers < 0, a beta that is not finite and > 0, a threshold that is not finite or < 0, a cutoff that is NaN or not > 0:
  * MOLANN_E_DESC.  n_walkers == 0: MOLANN_OK, nothing launched.  The call only enqueues on `stream` (no workspace, no event, nothing
- * allocated): capturable, and a bias launch and this one queue back to back with nothing read back.  Out of scope: adaptive sigma, the
- * explore variant, walkers on several ranks; more than one block; float32. */
+ * allocated): capturable, and a bias launch and this one queue back to back with nothing read back.  Adaptive sigma and the explore
+ * variant: molann_opes_step_modes_f64.  Out of scope: walkers on several ranks; more than one block; float32. */
 int molann_opes_step_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
                          double* run, const double* y, const double* V, int64_t n_walkers, const double* sigma0, const double* sigma_min,
                          double beta, double threshold, double cutoff, int32_t fixed_sigma, molann_stream_t stream);
@@ -655,6 +655,42 @@ int molann_opes_step_columns_f64(double* centers, double* sigma, double* heights
                                  double* run, const double* y, int64_t y_stride, const int32_t* columns, const double* V, int64_t v_stride,
                                  int64_t n_walkers, const double* sigma0, const double* sigma_min, double beta, double threshold, double cutoff,
                                  int32_t fixed_sigma, molann_stream_t stream);
+
+/* molann_opes_step_columns_f64 in OPES_METAD's other two modes, in ONE launch of opes_step_modes_f64_kernel (one block of 256 threads,
+ * ahead of time): widths measured from the run itself (SIGMA=ADAPTIVE) where `adapt` is not NULL, and the explore variant
+ * (OPES_METAD_EXPLORE) where bit 1 of `flags` is set.  flags: bit 0 fixed_sigma, bit 1 explore, bit 2 observe only; other bits are
+ * ignored.  adapt[n_walkers, 3, d]: a DEVICE array of (mean, M2, sigma0) rows per walker, zeros before the first call, kept by the
+ * caller between the calls; run[6] is the number of observations and run[7] is 0 until the first deposit has fixed sigma0, then 1
+ * (both stay 0 without adapt).  `sigma0` is read only where adapt is NULL and may be NULL otherwise.  wrap_k(v) = v - P rint(v / P)
+ * where period[k] = P > 0.  In order, k ascending, nothing contracted:
+ *   1. with adapt: c = run[6] + 1, tau = min(c, adaptive_stride); for every walker whose d chosen outputs are finite and every k:
+ *      diff = wrap_k(y_ak - mean_ak), mean_ak += diff / tau, M2_ak += diff wrap_k(y_ak - mean_ak) with the new mean (the mean is not
+ *      wrapped back); any other walker keeps its row; run[6] = c.  Each (walker, column) pair is independent of every other: no
+ *      reduction, the same bits on every run, and on the host.
+ *   2. observe only, or a deposit with run[7] == 0 and c < adaptive_stride (nothing is deposited before the first stride has passed):
+ *      the call ends here; the table, state and run[0..5] keep their bits.  With observe only V is not read, but must be a pointer
+ *      molann_opes_step_columns_f64 accepts (y will do).
+ *   3. the sums and scalars of molann_opes_step_f64; the explore variant takes `counter`, not neff, for sigma_scale (neff and rct are
+ *      formed from the weights all the same).
+ *   4. without adapt: molann_opes_step_f64's widths.  With adapt, factor = biasfactor (1 in the explore variant): on the first deposit
+ *      (run[7] == 0), for every walker and k, M2_ak *= biasfactor - the samples so far were unbiased, the later ones come from the
+ *      flattened distribution - and sigma0_ak = sqrt((M2_ak / c) / factor) raised to sigma_min_k, and run[7] = 1; on every deposit
+ *      s_ak = sqrt((M2_ak / c) / factor), times sigma_scale unless fixed_sigma, raised to sigma_min_k once, at the end, and
+ *      ratio_a = prod_k (sigma0_ak / s_ak).
+ *   5. height_a = w_a ratio_a, or ratio_a alone in the explore variant (every kernel weighs 1: S / n does not change with that
+ *      scale); NaN for an invalid walker.  A width of 0 - a walker that never moved, no sigma_min - makes its kernel invalid as well.
+ *   6. molann_opes_deposit_f64's steps.
+ * In the explore variant the caller's bias launch uses scale = kT (biasfactor - 1) and epsilon = exp(-barrier / scale), and a sigma0
+ * given without adapt is the target's width, sqrt(biasfactor) times the unbiased one.  Without adapt and without the explore bit the
+ * table, state and run are molann_opes_step_columns_f64's, bit for bit.  Refusals, with nothing enqueued: molann_opes_step_columns_f64's,
+ * in its order (sigma0 may be NULL with adapt); then adapt not 8-byte aligned: MOLANN_E_ALIGNMENT; observe only without adapt,
+ * adaptive_stride < 2 with adapt, a biasfactor that is not finite and > 1 with adapt or in the explore variant: MOLANN_E_DESC.
+ * n_walkers == 0: MOLANN_OK, nothing launched.  Capturable, as molann_opes_step_f64.  Out of scope: walkers on several ranks; more than
+ * one block; float32; a TorchScript operator. */
+int molann_opes_step_modes_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
+                               double* run, const double* y, int64_t y_stride, const int32_t* columns, const double* V, int64_t v_stride,
+                               int64_t n_walkers, const double* sigma0, const double* sigma_min, double* adapt, double beta, double biasfactor,
+                               int64_t adaptive_stride, double threshold, double cutoff, int32_t flags, molann_stream_t stream);
 
 /* The deposit step of a METADYNAMICS run on a table, in ONE launch of metad_deposit_f64_kernel (ahead of time: no hipRTC, no plan): the
  * hills of n_walkers walkers are added, in place, to the table molann_value_and_grid_f64 / molann_value_and_bias_f64 interpolate, with
@@ -816,6 +852,12 @@ int molann_selftest_opes_step_columns_f64(double* centers, double* sigma, double
                                           double* state, double* run, const double* y, int64_t y_stride, const int32_t* columns, const double* V,
                                           int64_t v_stride, int64_t n_walkers, const double* sigma0, const double* sigma_min, double beta,
                                           double threshold, double cutoff, int32_t fixed_sigma);
+/* molann_opes_step_modes_f64 on the host: the same arguments as HOST pointers (adapt too), the same steps through the functions its
+ * kernel calls, the same refusals and the device's order of every sum */
+int molann_selftest_opes_step_modes_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period,
+                                        double* state, double* run, const double* y, int64_t y_stride, const int32_t* columns, const double* V,
+                                        int64_t v_stride, int64_t n_walkers, const double* sigma0, const double* sigma_min, double* adapt,
+                                        double beta, double biasfactor, int64_t adaptive_stride, double threshold, double cutoff, int32_t flags);
 /* the unit-cotangent local Jacobian frames_value_jac_f64_kernel combines: jac36[c][j][xyz] = d(output column c of the item) /
  * d(atom j) for the item's 4 atoms (rows past the item's width are 0); returns the width */
 int molann_selftest_item_jacobian_f64(int type, int use_angle_value, const double* atoms_xyz, double* jac36);

@@ -248,6 +248,10 @@ def lib():
             "molann_selftest_bias_opes_table_f64": (i32, [vp, i32, ctypes.POINTER(BiasTermsF64), ctypes.POINTER(OpesTableTermF64), vp, vp]),
             "molann_selftest_opes_step_columns_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int32), vp, i64, i64,
                                                             vp, vp] + [ctypes.c_double] * 3 + [i32]),
+            "molann_opes_step_modes_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int32), vp, i64, i64, vp, vp, vp,
+                                                 ctypes.c_double, ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32, vp]),
+            "molann_selftest_opes_step_modes_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int32), vp, i64, i64,
+                                                          vp, vp, vp, ctypes.c_double, ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32]),
             "molann_metad_deposit_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64] + [ctypes.c_double] * 3 + [vp, vp, i64, vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -820,6 +824,28 @@ def opes_step_columns_f64(centers, sigma, heights, state, run, period, y, column
                                               float(threshold), float("inf") if cutoff is None else float(cutoff), 1 if fixed_sigma else 0,
                                               torch.cuda.current_stream().cuda_stream)
     _check(code, "molann_opes_step_columns_f64")
+
+
+OPES_FIXED_SIGMA, OPES_EXPLORE, OPES_OBSERVE = 1, 2, 4      # the bits of molann_opes_step_modes_f64's `flags`
+
+
+def opes_step_modes_f64(centers, sigma, heights, state, run, period, y, columns, V, sigma0, sigma_min, adapt, beta, biasfactor, adaptive_stride,
+                        threshold, cutoff=None, fixed_sigma=False, explore=False, observe=False):
+    """`molann_opes_step_modes_f64` on torch's current stream: `opes_step_columns_f64` with widths measured from the run where `adapt`
+    ([W, 3, d] rows of (mean, M2, sigma0), updated in place; `sigma0` may then be None) is given, and the explore variant with
+    `explore`; `observe`: the averages alone (`V` None: not read).  `run[6]` counts the observations, `run[7]` says whether the first
+    deposit has fixed sigma0.  The tensors' shapes are the caller's to check (`molann_amd.bias.OpesRun` does)."""
+    n_walkers = y.shape[0]
+    if V is None:
+        V = y
+    flags = (OPES_FIXED_SIGMA if fixed_sigma else 0) | (OPES_EXPLORE if explore else 0) | (OPES_OBSERVE if observe else 0)
+    code = lib().molann_opes_step_modes_f64(centers.data_ptr(), sigma.data_ptr(), heights.data_ptr(), centers.shape[0], centers.shape[1],
+                                            _address(period), state.data_ptr(), run.data_ptr(), y.data_ptr(),
+                                            y.stride(0) if n_walkers > 1 else y.shape[1], columns, V.data_ptr(),
+                                            V.stride(0) if n_walkers > 1 else 1, n_walkers, _address(sigma0), _address(sigma_min), _address(adapt),
+                                            float(beta), float(biasfactor), int(adaptive_stride), float(threshold),
+                                            float("inf") if cutoff is None else float(cutoff), flags, torch.cuda.current_stream().cuda_stream)
+    _check(code, "molann_opes_step_modes_f64")
 
 
 def metad_grid_arrays(shape, lower, spacing, periodic, sigma, columns):

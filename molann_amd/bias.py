@@ -14,7 +14,8 @@ table's state (`MolANN.value_and_opes_table`), `deposit` turns those outputs int
 per step, nothing read back, capturable in a graph.  With walls or a table next to it, or on some of a wider model's outputs, the kernel table
 goes into `MolANN.value_and_bias` as an `OpesFromTable` record, whose kernel reads the table's state on the device as well -
 `OpesRun(columns=, walls=, grid=)` is that loop, still two launches per step - or, with the live count and the norm at hand on the host,
-as an `Opes` record.
+as an `Opes` record.  `OpesRun(sigma0="adaptive")` measures the kernels' widths from the run itself, per walker, in state that stays on
+the device, and `OpesRun(explore=True)` is the explore variant: the same two launches per step.
 
 A metadynamics run on a table is a `MetadRun`, the same loop for hills: `bias` is `value_and_grid` (or `value_and_bias` with walls or on
 some of a wider model's outputs) on the table as it is, `deposit` adds the step's hills to the table on the device with well-tempered
@@ -330,15 +331,16 @@ def _positive(name, what, v, allow_inf=False):
 
 
 class OpesRun(object):
-    """A whole OPES run (PLUMED's ``OPES_METAD`` with a fixed ``sigma0``; not the explore variant) on the device: two launches per
-    step and nothing read back, so the loop queues ahead of the device and can be captured in one ``torch.cuda.graph``.
+    """A whole OPES run (PLUMED's ``OPES_METAD``, with a fixed or an adaptive ``sigma0``, and its explore variant) on the device: two
+    launches per step and nothing read back, so the loop queues ahead of the device and can be captured in one ``torch.cuda.graph``.
 
     ``bias(x)`` is `MolANN.value_and_opes_table` on the table's current state; ``deposit(y, bias)`` is `molann_opes_step_f64` on the
     outputs that call wrote: per walker ``w = exp(bias / kT)``, the running sums ``counter``, ``sum_w``, ``sum_w2``,
     ``neff = (1 + sum_w)^2 / (1 + sum_w2)``, ``rct = kT log(sum_w / counter)``, the widths ``sigma0 * sigma_scale`` with
     ``sigma_scale = (neff (d + 2) / 4)^(-1 / (d + 4))`` (1 with ``fixed_sigma``) held above ``sigma_min``, the heights
     ``w prod_k(sigma0_k / sigma_k)``, and the deposit of the W kernels into ``table`` as `OpesTable.deposit` makes it.  ``run`` [8] on
-    the table's device holds ``(counter, sum_w, sum_w2, neff, sigma_scale, rct, 0, 0)``.
+    the table's device holds ``(counter, sum_w, sum_w2, neff, sigma_scale, rct, observations, started)``, the last two 0 unless the
+    run is adaptive.
 
     With ``columns``, ``walls`` or ``grid`` the run has `MetadRun`'s surface: ``bias(x)`` is `MolANN.value_and_bias` with
     ``restraint=walls, grid=grid, opes=OpesFromTable(table, scale, epsilon, columns)`` (frames_value_bias_opes_table_f64_kernel: the
@@ -347,6 +349,25 @@ class OpesRun(object):
     they are - the weights use that bias alone, not the walls or the grid.  Still two launches per step, nothing read back, one graph.
     With all three None nothing changes, bit for bit.
 
+    ``sigma0="adaptive"`` (``SIGMA=ADAPTIVE``, OPES_METAD's default: nobody knows the spread of a learned variable in advance) measures
+    the widths from the run, per walker, and needs ``adaptive_stride`` >= 2 and ``walkers`` >= 1.  ``adapt`` [walkers, 3, d] on the
+    table's device holds each walker's ``(mean, M2, sigma0)`` and is allocated here, once.  Every ``deposit`` and every ``observe(y)``
+    - the call for the MD steps between two deposits, one launch, nothing read back - adds an observation: ``c = observations + 1``,
+    ``tau = min(c, adaptive_stride)``, ``diff = y - mean`` (the shorter way round a periodic output), ``mean += diff / tau``,
+    ``M2 += diff (y - mean)``; a walker with an output that is not finite keeps its row.  A ``deposit`` before ``adaptive_stride``
+    observations have passed stops there and deposits nothing.  The first deposit after them multiplies ``M2`` by ``biasfactor`` (the
+    samples so far were unbiased, the later ones come from the flattened distribution) and fixes ``sigma0 = sqrt(M2 / c / biasfactor)``,
+    held above ``sigma_min``; from then on walker a's kernel has the widths ``sqrt(M2_a / c / biasfactor) sigma_scale`` held above
+    ``sigma_min`` and the height ``w_a prod_k(sigma0_ak / sigma_ak)``.  A walker that never moved has a width of 0 and its kernels are
+    refused: ``sigma_min`` is the cure.  Both modes run on `molann_opes_step_modes_f64`.
+
+    ``explore=True`` is ``OPES_METAD_EXPLORE``, what to reach for while the variable is still poor: the table estimates the
+    well-tempered distribution itself, so every kernel weighs 1 (times the widths' ratio), ``sigma_scale`` is formed from ``counter``
+    instead of ``neff``, ``scale = kT (biasfactor - 1)`` and ``epsilon = exp(-barrier / scale)``.  A numeric ``sigma0`` is the width of
+    the unbiased distribution, as without explore: the run stores and uses ``sigma0 sqrt(biasfactor)``, the explore target being
+    broader by that factor; an adaptive run measures the target's width directly (no division by ``biasfactor``).  Each of the two
+    modes needs a finite ``biasfactor``.  ``columns``, ``walls`` and ``grid`` work with both.
+
     ``model``: a `MolANN` (or `PreprocessingANN`) whose outputs are the table's ``d`` columns, or a wider one with ``columns``: the
     ``table.d`` outputs the kernels act on, distinct, in any order; ``walls``: a `Restraint` on all outputs or None; ``grid``: a `Grid`
     (a static table from an earlier run, on its own columns) or None; ``table``: an `OpesTable` (its
@@ -354,9 +375,11 @@ class OpesRun(object):
     ``scale = kT (1 - 1 / biasfactor)``, ``epsilon = exp(-barrier / scale)``, ``beta = 1 / kT``.  ``sigma0``, ``sigma_min``: [d]
     numbers or tensors, finite and > 0 (checked here, once: on the device a width that is not > 0 makes every kernel of a step
     invalid and refused).  A walker whose bias or outputs are not finite is counted in the table's ``refused`` and changes nothing
-    else.  Out of scope: adaptive sigma, explore mode, walkers on several ranks, float32, a `GraphedForces` wrapper."""
+    else.  Out of scope: walkers on several ranks, float32, a step on more than one block, a TorchScript operator for the two modes,
+    PLUMED's restart files, a `GraphedForces` wrapper."""
 
-    def __init__(self, model, table, kT, biasfactor, barrier, sigma0, sigma_min=None, fixed_sigma=False, columns=None, walls=None, grid=None):
+    def __init__(self, model, table, kT, biasfactor, barrier, sigma0, sigma_min=None, fixed_sigma=False, columns=None, walls=None, grid=None,
+                 adaptive_stride=None, walkers=None, explore=False):
         from . import _capi
         if not callable(getattr(model, "value_and_opes_table", None)):
             raise TypeError("OpesRun: `model` must be a MolANN or a PreprocessingANN (it has no `value_and_opes_table`); got %s"
@@ -380,13 +403,32 @@ class OpesRun(object):
             raise ValueError("OpesRun: `biasfactor` must be > 1; got %r" % (biasfactor,))
         if not isinstance(fixed_sigma, (bool, int)):
             raise TypeError("OpesRun: `fixed_sigma` must be a bool; got %s" % type(fixed_sigma).__name__)
-        scale = kT * (1.0 - 1.0 / biasfactor)
+        if not isinstance(explore, (bool, int)):
+            raise TypeError("OpesRun: `explore` must be a bool; got %s" % type(explore).__name__)
+        adaptive, explore = isinstance(sigma0, str) and sigma0 == "adaptive", bool(explore)
+        if (adaptive or explore) and not math.isfinite(biasfactor):
+            raise ValueError("OpesRun: `biasfactor` must be finite with `sigma0=\"adaptive\"` and with `explore`; got %r" % (biasfactor,))
+        for what, v in (("adaptive_stride", adaptive_stride), ("walkers", walkers)):
+            if v is None and not adaptive:
+                continue
+            if v is None:
+                raise TypeError("OpesRun: `sigma0=\"adaptive\"` needs `%s`, an integer" % what)
+            if isinstance(v, bool):
+                raise TypeError("OpesRun: `%s` must be an integer; got a bool" % what)
+            try:
+                v = operator.index(v)
+            except TypeError:
+                raise TypeError("OpesRun: `%s` must be an integer; got %s" % (what, type(v).__name__))
+            if adaptive and v < (2 if what == "adaptive_stride" else 1):
+                raise ValueError("OpesRun: `%s` must be >= %d; got %d" % (what, 2 if what == "adaptive_stride" else 1, v))
+        scale = kT * (biasfactor - 1.0) if explore else kT * (1.0 - 1.0 / biasfactor)
         epsilon = math.exp(-barrier / scale)
         if not epsilon > 0.0:
-            raise ValueError("OpesRun: exp(-barrier / (kT (1 - 1 / biasfactor))) underflows to 0 for barrier %r; lower the barrier" % (barrier,))
+            raise ValueError("OpesRun: exp(-barrier / (kT (%s))) underflows to 0 for barrier %r; lower the barrier"
+                             % ("biasfactor - 1" if explore else "1 - 1 / biasfactor", barrier))
         rows = []
         for what, v in (("sigma0", sigma0), ("sigma_min", sigma_min)):
-            if v is None and what == "sigma_min":
+            if (v is None and what == "sigma_min") or (adaptive and what == "sigma0"):
                 rows.append(None)
                 continue
             try:
@@ -398,12 +440,21 @@ class OpesRun(object):
             if not bool((torch.isfinite(host) & (host > 0)).all()):
                 raise ValueError("OpesRun: `%s` holds widths and must be finite and > 0 everywhere" % what)
             rows.append(host)
+        for what, v in (("adaptive_stride", adaptive_stride), ("walkers", walkers)):
+            if v is not None and not adaptive:
+                raise ValueError("OpesRun: `%s` belongs to `sigma0=\"adaptive\"`; leave it None with given widths" % what)
         self.model, self.table = model, table
         self.kT, self.biasfactor, self.barrier, self.fixed_sigma = kT, biasfactor, barrier, bool(fixed_sigma)
         self.scale, self.epsilon, self.beta = scale, epsilon, 1.0 / kT
-        self.sigma0 = rows[0].to(table.centers.device).contiguous()
+        if explore and not adaptive:
+            rows[0] = rows[0] * math.sqrt(biasfactor)       # the widths given are the unbiased ones; the explore target is broader
+        self.adaptive, self.explore = adaptive, explore
+        self.adaptive_stride = operator.index(adaptive_stride) if adaptive else 0
+        self.walkers = operator.index(walkers) if adaptive else None
+        self.sigma0 = None if adaptive else rows[0].to(table.centers.device).contiguous()
         self.sigma_min = None if rows[1] is None else rows[1].to(table.centers.device).contiguous()
         self.run = torch.zeros(8, dtype=torch.float64, device=table.centers.device)
+        self.adapt = torch.zeros(self.walkers, 3, table.d, dtype=torch.float64, device=table.centers.device) if adaptive else None
         self.columns, self.walls, self.grid = columns, walls, grid
         self._plain = columns is None and walls is None and grid is None
         self._opes = OpesFromTable(table, scale, epsilon, columns)
@@ -419,9 +470,13 @@ class OpesRun(object):
     def deposit(self, y, bias):
         """The step after `bias`, as that call returned them (read only): ``y`` [W, d] and ``bias`` [W]; with walls, a grid or columns
         ``y`` [W, n_out] and ``bias`` [W] or the ``energies`` [W, 4], whose column 3 - the OPES bias alone, without the walls and the
-        grid, as OPES_METAD forms its weights - is read in place.  One launch on the current stream, nothing read back, returns None."""
+        grid, as OPES_METAD forms its weights - is read in place.  One launch on the current stream, nothing read back, returns None.  In
+        an adaptive run ``y`` has ``walkers`` rows, the call is an observation as well, and before ``adaptive_stride`` of them have
+        passed it deposits nothing."""
         from . import _capi
         t = self.table
+        if self.adaptive or self.explore:
+            return self._step_modes("deposit", y, bias, False)
         if not self._plain:
             return self._deposit_columns(y, bias)
         if not (isinstance(y, torch.Tensor) and y.dim() == 2):
@@ -461,6 +516,57 @@ class OpesRun(object):
             _capi.opes_step_columns_f64(t.centers, t.sigma, t.heights, t.state, self.run, t.period, y, self._column_array, V, self.sigma0,
                                         self.sigma_min, self.beta, t.threshold, t.cutoff, self.fixed_sigma)
         return None
+
+    def _step_modes(self, name, y, bias, observe):
+        """`deposit` and `observe` of an adaptive or an explore run: `molann_opes_step_modes_f64` on the outputs where they are; a plain
+        run passes its row stride d and the identity columns."""
+        from . import _capi
+        t = self.table
+        widest = t.d - 1 if self.columns is None else max(self.columns)
+        for what, v in (("y", y),) if observe else (("y", y), ("bias", bias)):
+            if not isinstance(v, torch.Tensor):
+                raise TypeError("OpesRun.%s: `%s` must be a tensor on %s; got %s" % (name, what, t.centers.device, type(v).__name__))
+            if v.dtype != torch.float64:
+                raise TypeError("OpesRun.%s: `%s` must be float64; got %s" % (name, what, v.dtype))
+            if v.device != t.centers.device:
+                raise ValueError("OpesRun.%s: `%s` must be on %s; got %s" % (name, what, t.centers.device, v.device))
+        if y.dim() != 2 or y.shape[1] <= widest or (self._plain and y.shape[1] != t.d):
+            raise ValueError("OpesRun.%s: `y` must be [W, %s]; got %s"
+                             % (name, "%d" % t.d if self._plain else "more than %d columns" % widest, list(y.shape)))
+        n_walkers = y.shape[0]
+        if self.adaptive and n_walkers != self.walkers:
+            raise ValueError("OpesRun.%s: the run keeps the averages of %d walkers; got %d" % (name, self.walkers, n_walkers))
+        V = None
+        if not observe:
+            shapes = ((n_walkers,),) if self._plain else ((n_walkers,), (n_walkers, 4))
+            if tuple(bias.shape) not in shapes:
+                raise ValueError("OpesRun.deposit: `bias` must be [W]%s; got %s" % ("" if self._plain else " or the energies [W, 4]", list(bias.shape)))
+            V = bias.detach() if bias.dim() == 1 else bias.detach()[:, 3]
+        if n_walkers == 0:
+            return None
+        y = y.detach().contiguous()
+        with torch.cuda.device(t.centers.device):
+            _capi.opes_step_modes_f64(t.centers, t.sigma, t.heights, t.state, self.run, t.period, y, self._column_array, V, self.sigma0,
+                                      self.sigma_min, self.adapt, self.beta, self.biasfactor, self.adaptive_stride, t.threshold, t.cutoff,
+                                      self.fixed_sigma, self.explore, observe)
+        return None
+
+    def observe(self, y, energies=None):
+        """An MD step between two deposits of an adaptive run: ``y`` as `bias` returned it joins every walker's running mean and M2 and
+        ``run[6]`` counts it - OPES updates the averages at every step and deposits at every PACE-th.  ``energies`` is accepted for
+        symmetry with `deposit` and ignored.  One launch on the current stream, nothing read back, returns None.  ValueError on a run
+        whose widths are given."""
+        if not self.adaptive:
+            raise ValueError("OpesRun.observe: the run's widths are given (`sigma0` is not \"adaptive\"): there is nothing to observe")
+        return self._step_modes("observe", y, None, True)
+
+    def read_adaptive(self):
+        """The adaptive state as a dict: ``observations`` and ``started`` (whether the first deposit has fixed ``sigma0``) as Python
+        numbers, ``mean``, ``M2`` and ``sigma0`` as [walkers, d] CPU tensors.  A read-back: it waits for the steps queued before it."""
+        if not self.adaptive:
+            raise ValueError("OpesRun.read_adaptive: the run's widths are given (`sigma0` is not \"adaptive\")")
+        run, rows = self.run.tolist(), self.adapt.cpu()
+        return dict(observations=int(run[6]), started=bool(run[7]), mean=rows[:, 0].clone(), M2=rows[:, 1].clone(), sigma0=rows[:, 2].clone())
 
     def read_run(self):
         """``run`` as a dict of Python numbers (``counter``, ``sum_w``, ``sum_w2``, ``neff``, ``sigma_scale``, ``rct``): the one 64-byte

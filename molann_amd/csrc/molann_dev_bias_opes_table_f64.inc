@@ -4,8 +4,8 @@
 // it reads from the table's state (molann_value_and_bias_opes_table_f64 launches it), and opes_step_columns_f64_kernel is
 // opes_step_f64_kernel (molann_dev_opes_table_f64.inc) reading the walkers from the [W, out_dim] outputs and the [W, 4] energies that
 // launch wrote (molann_opes_step_columns_f64).  Instances of their own: the kernels they follow keep their code.
-// Out of scope: hills and OPES in one launch; adaptive sigma, the explore variant, walkers on several ranks; float32; a step on more
-// than one block; a GraphedForces wrapper.
+// The step with adaptive sigma and the explore variant: molann_dev_opes_adaptive_f64.inc.  Out of scope: hills and OPES in one launch;
+// walkers on several ranks; float32; a step on more than one block; a GraphedForces wrapper.
 namespace {
 
 // =============================================================================================

@@ -4,8 +4,9 @@
 // and biases that launch wrote into this step's kernels - weights, effective sample size, rescaled widths, heights - and deposits them
 // (molann_opes_step_f64).  Neither needs a value from the host, so the pair queues, and is captured in a graph, with no read-back.  The
 // same pair for a run with walls, a table or a wider model - value_and_bias(opes=) reading the state, and the step on strided outputs
-// and chosen columns - is molann_dev_bias_opes_table_f64.inc, which keeps this file's argument layout.  Out of scope: adaptive sigma,
-// the explore variant, walkers on several ranks; float32; a step on more than one block; a GraphedForces wrapper.
+// and chosen columns - is molann_dev_bias_opes_table_f64.inc, which keeps this file's argument layout; the step with adaptive sigma and
+// the explore variant is molann_dev_opes_adaptive_f64.inc.  Out of scope: walkers on several ranks; float32; a step on more than one
+// block; a GraphedForces wrapper.
 namespace {
 
 // =============================================================================================

@@ -46,6 +46,7 @@
 
 #include "../../include/molann_hip.h"
 #include "molann_math.h"
+#include "molann_opes_modes.h"
 #include "jit_sources.gen.h"
 
 using namespace molann;
@@ -71,6 +72,7 @@ using namespace molann;
 #include "molann_dev_opes_deposit_f64.inc"
 #include "molann_dev_opes_table_f64.inc"
 #include "molann_dev_bias_opes_table_f64.inc"
+#include "molann_dev_opes_adaptive_f64.inc"
 #include "molann_dev_metad_deposit_f64.inc"
 // Host code (what `make san` instruments: -fno-gpu-sanitize leaves the device code alone):
 #include "molann_host_plan.inc"

@@ -4,7 +4,8 @@
 // arrays through the same steps and the same per-kernel functions, with the device's order of every sum.  molann_opes_step_f64 (a whole
 // OPES step: opes_step_f64_kernel of molann_dev_opes_table_f64.inc) and its twin molann_selftest_opes_step_f64 follow the same pattern, and so
 // do molann_opes_step_columns_f64 (the step on strided outputs and chosen columns: opes_step_columns_f64_kernel of
-// molann_dev_bias_opes_table_f64.inc) and molann_selftest_opes_step_columns_f64.
+// molann_dev_bias_opes_table_f64.inc) and molann_selftest_opes_step_columns_f64, and molann_opes_step_modes_f64 (that step with adaptive
+// widths and the explore variant: opes_step_modes_f64_kernel of molann_dev_opes_adaptive_f64.inc) and molann_selftest_opes_step_modes_f64.
 namespace {
 
 // the device's block on the host: the same strided partials, the same butterfly, the same order of the four waves
@@ -135,6 +136,42 @@ struct OpesStepColumnsHost : OpesStepHost {       // its fields; new_centers is 
     }
 };
 
+// opes_step_modes_f64_kernel's executor on the host (OpesStepModesDev): the pairs in ascending order - each is independent of every
+// other, so the order does not matter - and no barrier
+struct OpesStepModesHost : OpesStepColumnsHost {
+    double* adapt;
+    const double* sigma_min;
+    double width_count, width_factor, width_scale;
+    int fixed_sigma, explore;
+
+    void observe(long n_walkers, double tau) const {
+        for (long a = 0; a < n_walkers; ++a) {
+            double yc[HILLS_MAX_D];
+            gather(a, yc);
+            if (!opes_outputs_finite_f64(yc, d)) continue;
+            double* row = adapt + a * 3 * d;
+            for (int k = 0; k < d; ++k) opes_adapt_observe_f64(yc[k], period ? period[k] : 0.0, tau, row[k], row[d + k]);
+        }
+    }
+    void first_deposit(long n_walkers, double count, double factor, double biasfactor, const double* smin) const {
+        for (long a = 0; a < n_walkers; ++a) {
+            double* row = adapt + a * 3 * d;
+            for (int k = 0; k < d; ++k) opes_adapt_first_f64(count, factor, biasfactor, smin ? smin[k] : 0.0, row[d + k], row[2 * d + k]);
+        }
+    }
+    void load_new(long a, double (&c)[HILLS_MAX_D], double (&s)[HILLS_MAX_D], double& h) const {
+        gather(a, c);
+        double ratio_a = ratio;
+        if (adapt) {
+            const double* row = adapt + a * 3 * d;
+            ratio_a = opes_adaptive_widths_f64(row + d, row + 2 * d, sigma_min, width_count, width_factor, width_scale, fixed_sigma, d, s);
+        } else {
+            for (int k = 0; k < HILLS_MAX_D; ++k) s[k] = k < d ? step_sigma[k] : 1.0;
+        }
+        h = opes_walker_height_modes_f64(beta, V[a * v_stride], c, d, ratio_a, explore);
+    }
+};
+
 // what molann_opes_step_columns_f64 and its host twin add to opes_step_arguments, after it: the strides (MOLANN_E_DESC), then the list -
 // d distinct indices in [0, y_stride), NULL for 0..d-1 (MOLANN_E_INDEX); then the list is in `cols`
 inline int opes_step_columns_arguments(int32_t d, int64_t y_stride, const int32_t* columns, int64_t v_stride, int (&cols)[HILLS_MAX_D]) {
@@ -180,6 +217,25 @@ inline int opes_deposit_arguments(const double* centers, const double* sigma, co
     if (n_new < 0) return MOLANN_E_DESC;
     if (!std::isfinite(threshold) || threshold < 0.0) return MOLANN_E_DESC;
     if (!(cutoff > 0.0)) return MOLANN_E_DESC;
+    return MOLANN_OK;
+}
+
+// what molann_opes_step_modes_f64 and its host twin refuse: opes_step_arguments (sigma0 may be NULL where adapt is given: adapt stands in
+// for it), opes_step_columns_arguments, then adapt's alignment, observe-only without adapt, a stride < 2 with adapt, and in either mode a
+// biasfactor that is not finite and > 1
+inline int opes_step_modes_arguments(const double* centers, const double* sigma, const double* heights, int64_t capacity, int32_t d,
+                                     const double* period, const double* state, const double* run, const double* y, int64_t y_stride,
+                                     const int32_t* columns, const double* V, int64_t v_stride, int64_t n_walkers, const double* sigma0,
+                                     const double* sigma_min, const double* adapt, double beta, double biasfactor, int64_t adaptive_stride,
+                                     double threshold, double cutoff, int32_t flags, int (&cols)[HILLS_MAX_D]) {
+    int e = opes_step_arguments(centers, sigma, heights, capacity, d, period, state, run, y, V, n_walkers, (adapt && !sigma0) ? adapt : sigma0,
+                                sigma_min, beta, threshold, cutoff);
+    if (e == MOLANN_OK) e = opes_step_columns_arguments(d, y_stride, columns, v_stride, cols);
+    if (e != MOLANN_OK) return e;
+    if ((uintptr_t)adapt & 7) return MOLANN_E_ALIGNMENT;
+    if (!adapt && (flags & OPES_FLAG_OBSERVE)) return MOLANN_E_DESC;
+    if (adapt && adaptive_stride < 2) return MOLANN_E_DESC;
+    if ((adapt || (flags & OPES_FLAG_EXPLORE)) && !(std::isfinite(biasfactor) && biasfactor > 1.0)) return MOLANN_E_DESC;
     return MOLANN_OK;
 }
 
@@ -270,6 +326,44 @@ int molann_selftest_opes_step_columns_f64(double* centers, double* sigma, double
                         merges, refused, r);
     state[0] = (double)n; state[1] = S; state[2] = merges; state[3] = refused;
     for (int i = 0; i < 8; ++i) run[i] = r[i];
+    return MOLANN_OK;
+}
+
+int molann_opes_step_modes_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period, double* state,
+                               double* run, const double* y, int64_t y_stride, const int32_t* columns, const double* V, int64_t v_stride,
+                               int64_t n_walkers, const double* sigma0, const double* sigma_min, double* adapt, double beta, double biasfactor,
+                               int64_t adaptive_stride, double threshold, double cutoff, int32_t flags, molann_stream_t stream) {
+    OpesStepColumns cols;
+    const int e = opes_step_modes_arguments(centers, sigma, heights, capacity, d, period, state, run, y, y_stride, columns, V, v_stride, n_walkers,
+                                            sigma0, sigma_min, adapt, beta, biasfactor, adaptive_stride, threshold, cutoff, flags, cols.col);
+    if (e != MOLANN_OK || n_walkers == 0) return e;
+    hipLaunchKernelGGL(opes_step_modes_f64_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, centers, sigma, heights, (long)capacity, (int)d, period,
+                       state, run, y, (long)y_stride, cols, V, (long)v_stride, (long)n_walkers, sigma0, sigma_min, adapt, beta, biasfactor,
+                       (double)adaptive_stride, threshold, cutoff, (int)(flags & 7));
+    return (int)hipGetLastError();
+}
+
+int molann_selftest_opes_step_modes_f64(double* centers, double* sigma, double* heights, int64_t capacity, int32_t d, const double* period,
+                                        double* state, double* run, const double* y, int64_t y_stride, const int32_t* columns, const double* V,
+                                        int64_t v_stride, int64_t n_walkers, const double* sigma0, const double* sigma_min, double* adapt,
+                                        double beta, double biasfactor, int64_t adaptive_stride, double threshold, double cutoff, int32_t flags) {
+    OpesStepModesHost ex = {{{{centers, sigma, heights, period, y, nullptr, nullptr, (int)d}, V, beta, 1.0, {1., 1., 1., 1., 1., 1., 1., 1.}},
+                             (long)y_stride, (long)v_stride, {0, 0, 0, 0, 0, 0, 0, 0}},
+                            adapt, sigma_min, 1.0, 1.0, 1.0, 0, 0};
+    const int e = opes_step_modes_arguments(centers, sigma, heights, capacity, d, period, state, run, y, y_stride, columns, V, v_stride, n_walkers,
+                                            sigma0, sigma_min, adapt, beta, biasfactor, adaptive_stride, threshold, cutoff, flags, ex.col);
+    if (e != MOLANN_OK || n_walkers == 0) return e;
+    long n = opes_live_count_f64(state[0], (long)capacity);
+    double S = state[1], merges = state[2], refused = state[3];
+    double r[8] = {run[0], run[1], run[2], run[3], run[4], run[5], run[6], run[7]};
+    const bool deposited = opes_step_modes_steps_f64(ex, (long)capacity, (int)d, period, (long)n_walkers, threshold, cutoff, beta, (int)(flags & 7),
+                                                     adapt != nullptr, sigma0, sigma_min, biasfactor, (double)adaptive_stride, n, S, merges, refused, r);
+    if (deposited) {
+        state[0] = (double)n; state[1] = S; state[2] = merges; state[3] = refused;
+        for (int i = 0; i < 8; ++i) run[i] = r[i];
+    } else {
+        run[6] = r[6];
+    }
     return MOLANN_OK;
 }
 
