@@ -720,11 +720,35 @@ int molann_opes_step_modes_f64(double* centers, double* sigma, double* heights, 
  * more), a sigma or a height0 that is not finite and > 0, an inv_dT that is not finite and >= 0, a cutoff that is NaN or not > 0, a
  * negative stride, count or capacity, a column outside [0, y_stride): MOLANN_E_DESC.  n_walkers == 0: MOLANN_OK, nothing launched.
  * The call only enqueues on `stream` (no workspace, no event, nothing allocated): thread-safe on distinct tables and capturable.  Out
- * of scope: adaptive widths; the reweighting offset c(t); walkers on several ranks; float32; more than 3 axes. */
+ * of scope: adaptive widths; the reweighting offset c(t) (molann_metad_rct_f64 after this call); walkers on several ranks; float32; more than 3 axes. */
 int molann_metad_deposit_f64(double* table, int32_t d, const int64_t* shape, const double* lower, const double* spacing, const int32_t* periodic,
                              const double* sigma, const int32_t* columns, const double* y, int64_t y_stride, const double* V, int64_t v_stride,
                              int64_t n_walkers, double height0, double inv_dT, double cutoff, double* state, double* log, int64_t log_capacity,
                              molann_stream_t stream);
+
+/* The reweighting offset c(t) of a METADYNAMICS run from its device-resident table (Tiwary-Parrinello reweighting; PLUMED's CALC_RCT,
+ * RCT_USTRIDE, metad.rct): a frame of the run is weighted by exp((V(s, t) - c(t)) / kT).  Two launches, a chain on `stream`
+ * (metad_rct_partial_f64_kernel, metad_rct_combine_f64_kernel; ahead of time: no hipRTC, no plan), with no atomics: a deterministic
+ * reduction, the same bits on every run and for every launch geometry.  table: a DEVICE pointer to n_entries doubles, read flat and
+ * read only - the number of axes does not matter.  With a0 = 1 / kT + inv_dT and aV = inv_dT (inv_dT = 1 / (kT (biasfactor - 1)), what
+ * molann_metad_deposit_f64 takes; 0: plain metadynamics):
+ *   M = max_g V_g,  S0 = sum_g exp(a0 (V_g - M)),  SV = sum_g exp(aV (V_g - M)),  c = M + kT (log S0 - log SV)
+ * = kT log(sum exp(a0 V) / sum exp(aV V)) with no exponent above 0, whatever the table holds.  The table is cut into chunks of 2048
+ * consecutive entries; partials (DEVICE) [partial_rows, 4] gets one row (m_c, s0_c, sV_c, bad_c) per chunk - exactly
+ * molann_metad_rct_chunks(n_entries) rows are written - and the second launch combines the rows.  The order of every sum is fixed
+ * (molann_amd/csrc/molann_metad_rct.h documents it).  rct (DEVICE) [8] = (c, updates, M, a0 M + log S0, aV M + log SV, steps at this update,
+ * bad, 0): `updates` is rct[1] + 1 (not finite or negative reads as 0), `bad` the number of entries that are not finite, which enter
+ * neither the maximum nor the sums; with bad > 0 slots 0, 2, 3 and 4 are NaN.  state (DEVICE, may be NULL): the state[8] of
+ * molann_metad_deposit_f64, of which state[3] = steps is read on the device by both launches (not finite or negative reads as 0): when
+ * steps is no multiple of `stride` neither partials nor rct is written, so one captured graph serves a run with any stride; NULL: the
+ * update always happens and slot 5 is 0.  Refusals, in this order, with nothing enqueued and nothing written: a NULL table, partials or
+ * rct: MOLANN_E_NULL; a table, state, partials or rct that is not 8-byte aligned: MOLANN_E_ALIGNMENT; n_entries < 1 or >= 2^31, a kT that
+ * is not finite and > 0, an inv_dT that is not finite and >= 0, stride < 1, partial_rows < molann_metad_rct_chunks(n_entries):
+ * MOLANN_E_DESC.  The call only enqueues (no workspace of its own, no event, nothing allocated): capturable.  Out of scope: a running
+ * acceleration factor; V - c written per walker; float32; a single-launch reduction. */
+int64_t molann_metad_rct_chunks(int64_t n_entries); /* rows of partials needed: ceil(n_entries / 2048); 0 for n_entries < 1 */
+int molann_metad_rct_f64(const double* table, int64_t n_entries, double kT, double inv_dT, const double* state, int64_t stride, double* partials,
+                         int64_t partial_rows, double* rct, molann_stream_t stream);
 
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
@@ -822,6 +846,10 @@ int molann_selftest_metad_deposit_f64(double* table, int32_t d, const int64_t* s
                                       const int32_t* periodic, const double* sigma, const int32_t* columns, const double* y, int64_t y_stride,
                                       const double* V, int64_t v_stride, int64_t n_walkers, double height0, double inv_dT, double cutoff,
                                       double* state, double* log, int64_t log_capacity);
+/* molann_metad_rct_f64 on the host: the same arguments as HOST pointers, the same refusals, the same chunks, the same tree and the
+ * same functions */
+int molann_selftest_metad_rct_f64(const double* table, int64_t n_entries, double kT, double inv_dT, const double* state, int64_t stride,
+                                  double* partials, int64_t partial_rows, double* rct);
 /* one axis' step of molann_value_and_grid_f64 on the host, through the function its kernel calls: the four table indices, the four
  * weights and the four derivative weights (s w' / spacing) for output value y on an axis of n points; any of the three may be NULL */
 void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]);

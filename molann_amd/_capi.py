@@ -253,6 +253,9 @@ def lib():
             "molann_selftest_opes_step_modes_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int32), vp, i64, i64,
                                                           vp, vp, vp, ctypes.c_double, ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32]),
             "molann_metad_deposit_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64] + [ctypes.c_double] * 3 + [vp, vp, i64, vp]),
+            "molann_metad_rct_chunks": (i64, [i64]),
+            "molann_metad_rct_f64": (i32, [vp, i64, ctypes.c_double, ctypes.c_double, vp, i64, vp, i64, vp, vp]),
+            "molann_selftest_metad_rct_f64": (i32, [vp, i64, ctypes.c_double, ctypes.c_double, vp, i64, vp, i64, vp]),
             "molann_forward_train_f32": (i32, [vp, vp, i64, vp, vp, vp]),
             "molann_features_backward_f64": (i32, [vp, vp, vp, i64, vp, vp]),
             "molann_features_backward_f32": (i32, [vp, vp, vp, i64, vp, vp]),
@@ -869,6 +872,16 @@ def metad_deposit_f64(table, arrays, y, V, height0, inv_dT, cutoff, state, log=N
                                           float("inf") if cutoff is None else float(cutoff), state.data_ptr(), _address(log),
                                           0 if log is None else log.shape[0], torch.cuda.current_stream().cuda_stream)
     _check(code, "molann_metad_deposit_f64")
+
+
+def metad_rct_f64(table, kT, inv_dT, state, stride, partials, rct):
+    """`molann_metad_rct_f64` on torch's current stream: the reweighting offset c(t) of `table` (any shape, read flat) into `rct` [8], through
+    `partials` [at least `molann_metad_rct_chunks(table.numel())`, 4]; two launches, nothing read back.  `state` [8] or None: with a state
+    the device skips the update unless ``state[3]`` is a multiple of `stride`.  Contiguous float64 tensors on one device; their shapes are
+    the caller's to check (`molann_amd.bias.MetadRun` does)."""
+    code = lib().molann_metad_rct_f64(table.data_ptr(), table.numel(), float(kT), float(inv_dT), _address(state), int(stride), partials.data_ptr(),
+                                      partials.shape[0], rct.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    _check(code, "molann_metad_rct_f64")
 
 
 def opes_kernel_sum_f64(points, centers, heights, sigma, period, cutoff, P, dP=None):

@@ -20,7 +20,8 @@ the device, and `OpesRun(explore=True)` is the explore variant: the same two lau
 A metadynamics run on a table is a `MetadRun`, the same loop for hills: `bias` is `value_and_grid` (or `value_and_bias` with walls or on
 some of a wider model's outputs) on the table as it is, `deposit` adds the step's hills to the table on the device with well-tempered
 heights formed from that call's bias (`molann_metad_deposit_f64`) - two launches per step, nothing read back, capturable in a graph -
-and `hills` gives the deposited hills back as a `Hills` record.  `add_hills_to_grid` stays the way to build a table from hills at hand."""
+and `hills` gives the deposited hills back as a `Hills` record; with `rct_stride` the run also keeps the reweighting offset c(t) on the
+device (`molann_metad_rct_f64`, two more launches on the steps that update it).  `add_hills_to_grid` stays the way to build a table from hills at hand."""
 
 import collections
 import math
@@ -595,12 +596,23 @@ class MetadRun(object):
     underflows to 0, is counted in ``refused`` and changes no table entry.  With a cutoff a deposit touches only the tiles of the table
     a hill reaches, so its cost is the hills' footprint, not the table's size; without one every entry takes every walker's term, as in
     `add_hills_to_grid` - the torch route (`value_and_grid`, the heights with torch, `add_hills_to_grid` on the device table) was slower
-    on every shape measured, by the least, 1.3x, for 64 walkers on 128^3 entries without a cutoff.  Out of scope: adaptive
-    widths; the reweighting offset c(t) (a logsumexp over the table: torch on ``table`` when wanted); walkers on several ranks;
-    float32; tables of more than 3 axes."""
+    on every shape measured, by the least, 1.3x, for 64 walkers on 128^3 entries without a cutoff.
+
+    ``rct_stride``: None, or an integer >= 1 (PLUMED's ``CALC_RCT`` with ``RCT_USTRIDE``): the run then keeps the reweighting offset
+    c(t) of Tiwary and Parrinello on the device, so that a frame is weighted by ``exp((V - c) / kT)`` with nothing read back.  ``rct``
+    [8] holds ``(c, updates, M, a0 M + log S0, aV M + log SV, steps at the update, bad, 0)`` with ``M`` the table's maximum,
+    ``S0 = sum exp(a0 (V_g - M))``, ``SV = sum exp(aV (V_g - M))``, ``a0 = 1 / kT + aV``, ``aV = 1 / (kT (biasfactor - 1))`` and
+    ``c = M + kT (log S0 - log SV)``: `molann_metad_rct_f64`, a deterministic reduction over the whole table in two launches that
+    `deposit` enqueues after its own.  Whether a step updates - ``steps`` a multiple of the stride - is decided on the device from
+    ``state``, so one captured graph replays a run with any stride.  ``bad`` counts the table entries that are not finite (``c`` is
+    NaN then).  `update_rct` is the update now, `read_rct` the one read-back, `rbias` ``V - c`` on the device.  The update reads
+    the whole table where a deposit with a cutoff touches a hill's footprint: 16-23 us for the pair alone and 9-15 us on a replayed
+    step (3 us on a step off the stride) on tables of 256^2 to 128^3 entries, against 111-126 us for two ``torch.logsumexp`` on the
+    table; no measured shape was slower than that route.  Out of scope: adaptive widths; a running acceleration
+    factor; walkers on several ranks; float32; tables of more than 3 axes."""
 
     def __init__(self, model, table, lower, spacing, kT, biasfactor, height, sigma, periodic=None, cutoff=None, columns=None, walls=None,
-                 log_capacity=0):
+                 log_capacity=0, rct_stride=None):
         from . import _capi
         if not (callable(getattr(model, "value_and_grid", None)) and callable(getattr(model, "value_and_bias", None))):
             raise TypeError("MetadRun: `model` must be a MolANN or a PreprocessingANN (it has no `value_and_grid`); got %s" % type(model).__name__)
@@ -648,6 +660,15 @@ class MetadRun(object):
         log_capacity = operator.index(log_capacity)
         if log_capacity < 0:
             raise ValueError("MetadRun: `log_capacity` must be >= 0; got %d" % log_capacity)
+        if rct_stride is not None:
+            if isinstance(rct_stride, bool):
+                raise TypeError("MetadRun: `rct_stride` must be None or an integer")
+            try:
+                rct_stride = operator.index(rct_stride)
+            except TypeError:
+                raise TypeError("MetadRun: `rct_stride` must be None or an integer; got %s" % type(rct_stride).__name__)
+            if rct_stride < 1:
+                raise ValueError("MetadRun: `rct_stride` must be None or >= 1; got %d" % rct_stride)
         if table.device.type != "cuda":
             raise ValueError("MetadRun: the table lives in device memory and its kernels are HIP kernels; got device %s" % table.device)
         self.model, self.table, self.walls = model, table.detach(), walls
@@ -658,6 +679,15 @@ class MetadRun(object):
         self.log = torch.zeros(log_capacity, 2 * d + 1, dtype=torch.float64, device=table.device) if log_capacity else None
         self._grid = Grid(self.table, self.lower, self.spacing, self.periodic, self.columns)
         self._arrays = _capi.metad_grid_arrays(table.shape, self.lower, self.spacing, self.periodic, self.sigma, self.columns)
+        self.rct_stride, self.rct, self._rct_partials = rct_stride, None, None
+        if rct_stride is not None:
+            self._allocate_rct()
+
+    def _allocate_rct(self):
+        from . import _capi
+        rows = int(_capi.lib().molann_metad_rct_chunks(self.table.numel()))
+        self.rct = torch.zeros(8, dtype=torch.float64, device=self.table.device)
+        self._rct_partials = torch.zeros(rows, 4, dtype=torch.float64, device=self.table.device)
 
     def bias(self, x, into=None):
         """The walkers ``x`` under the table as it is now, one launch: ``(y, bias, dx)`` of `MolANN.value_and_grid`, or - with walls or
@@ -689,7 +719,43 @@ class MetadRun(object):
         V = bias.detach() if bias.dim() == 1 else bias.detach()[:, 2]
         with torch.cuda.device(self.table.device):
             _capi.metad_deposit_f64(self.table, self._arrays, y, V, self.height, self.inv_dT, self.cutoff, self.state, self.log)
+            if self.rct_stride is not None:
+                _capi.metad_rct_f64(self.table, self.kT, self.inv_dT, self.state, self.rct_stride, self._rct_partials, self.rct)
         return None
+
+    def update_rct(self):
+        """The offset of the table as it is now, whatever the stride - for a table that was loaded rather than grown: two launches on the
+        current stream, nothing read back, returns None.  A run made with ``rct_stride=None`` allocates ``rct`` on first use."""
+        from . import _capi
+        if self.rct is None:
+            self._allocate_rct()
+        with torch.cuda.device(self.table.device):
+            _capi.metad_rct_f64(self.table, self.kT, self.inv_dT, None, 1, self._rct_partials, self.rct)
+        return None
+
+    def read_rct(self):
+        """``rct`` as a dict of Python numbers (``rct``, ``updates``, ``max``, ``log_sum_0``, ``log_sum_V``, ``steps``, ``bad``): the one
+        64-byte read-back (it waits for the steps queued before it)."""
+        if self.rct is None:
+            raise ValueError("MetadRun.read_rct: the run keeps no offset (`rct_stride` is None and `update_rct` was not called)")
+        c, updates, top, log0, logV, steps, bad = self.rct.tolist()[:7]
+        return dict(rct=c, updates=int(updates), max=top, log_sum_0=log0, log_sum_V=logV, steps=int(steps), bad=int(bad))
+
+    def rbias(self, bias):
+        """PLUMED's ``metad.rbias``: ``V - c`` [W] on the device, nothing read back.  ``bias``: [W], or the energies [W, 3] of `bias`
+        whose column 2 is used."""
+        if self.rct is None:
+            raise ValueError("MetadRun.rbias: the run keeps no offset (`rct_stride` is None and `update_rct` was not called)")
+        if not isinstance(bias, torch.Tensor):
+            raise TypeError("MetadRun.rbias: `bias` must be a tensor on %s; got %s" % (self.table.device, type(bias).__name__))
+        if bias.dtype != torch.float64:
+            raise TypeError("MetadRun.rbias: `bias` must be float64; got %s" % bias.dtype)
+        if bias.device != self.table.device:
+            raise ValueError("MetadRun.rbias: `bias` must be on %s; got %s" % (self.table.device, bias.device))
+        if bias.dim() not in (1, 2) or (bias.dim() == 2 and bias.shape[1] != 3):
+            raise ValueError("MetadRun.rbias: `bias` must be [W] or the energies [W, 3]; got %s" % list(bias.shape))
+        V = bias.detach() if bias.dim() == 1 else bias.detach()[:, 2]
+        return V - self.rct[0]
 
     def read_state(self):
         """``state`` as a dict of Python numbers (``hills``, ``refused``, ``sum_heights``, ``steps``, ``logged``): the one 64-byte

@@ -1,8 +1,8 @@
 // molann_dev_metad_deposit_f64.inc - part of libmolann_hip.so, included by molann_kernels.hip after molann_dev_bias_opes_table_f64.inc.  The
 // other half of a metadynamics run on a table, between the steps that molann_value_and_grid_f64 / molann_value_and_bias_f64 serve:
 // metad_deposit_f64_kernel adds a step's hills to the device-resident table in place, with well-tempered heights formed from the bias
-// those launches wrote (molann_metad_deposit_f64 launches it).  Out of scope: adaptive widths; the reweighting offset c(t); float32;
-// tables of more than GRID_MAX_D axes.
+// those launches wrote (molann_metad_deposit_f64 launches it).  The reweighting offset c(t) is the next file's (molann_dev_metad_rct_f64.inc), queued after this
+// launch.  Out of scope: adaptive widths; float32; tables of more than GRID_MAX_D axes.
 namespace {
 
 struct MetadDepositArgs {

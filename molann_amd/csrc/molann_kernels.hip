@@ -47,6 +47,7 @@
 #include "../../include/molann_hip.h"
 #include "molann_math.h"
 #include "molann_opes_modes.h"
+#include "molann_metad_rct.h"
 #include "jit_sources.gen.h"
 
 using namespace molann;
@@ -74,6 +75,7 @@ using namespace molann;
 #include "molann_dev_bias_opes_table_f64.inc"
 #include "molann_dev_opes_adaptive_f64.inc"
 #include "molann_dev_metad_deposit_f64.inc"
+#include "molann_dev_metad_rct_f64.inc"
 // Host code (what `make san` instruments: -fno-gpu-sanitize leaves the device code alone):
 #include "molann_host_plan.inc"
 #include "molann_host_jit.inc"
@@ -85,3 +87,4 @@ using namespace molann;
 #include "molann_value_f64.inc"
 #include "molann_opes_deposit_f64.inc"
 #include "molann_metad_deposit_f64.inc"
+#include "molann_metad_rct_f64.inc"

@@ -1290,6 +1290,33 @@ void metad_step_hip(at::Tensor table_in, at::Tensor state_in, const c10::optiona
           "molann_metad_deposit_f64");
 }
 
+// The reweighting offset c(t) of a metadynamics run (molann_metad_rct_f64): `table` (any shape, contiguous, read flat and read only) is reduced
+// through `partials` [at least molann_metad_rct_chunks(table.numel()), 4] into `rct` [8], in TWO launches on the current stream, a chain; nothing
+// is read back.  `state` [8] or none: with a state the device skips the update unless state[3] is a multiple of `stride`.  The scalars are
+// checked here as the C entry checks them.
+void metad_rct_hip(const at::Tensor& table_in, const c10::optional<at::Tensor>& state_in, at::Tensor partials_in, at::Tensor rct_in, double kT,
+                   double inv_dT, int64_t stride) {
+    const char* const op = "molann::metad_rct";
+    TORCH_CHECK_VALUE(table_in.numel() >= 1 && table_in.numel() < ((int64_t)1 << 31), "molann::metad_rct: `table` must hold 1 to 2^31 - 1 entries");
+    TORCH_CHECK_VALUE(std::isfinite(kT) && kT > 0.0 && std::isfinite(inv_dT) && inv_dT >= 0.0 && stride >= 1,
+                      "molann::metad_rct: `kT` must be finite and > 0, `inv_dT` finite and >= 0, `stride` >= 1; got ", kT, ", ", inv_dT, ", ", stride);
+    TORCH_CHECK_VALUE(table_in.is_contiguous(), "molann::metad_rct: `table` is read where it is and must be contiguous");
+    const at::Tensor table = opes_tensor(op, "table", table_in, table_in, true, "[n_0, ...]", false);
+    const int64_t rows = molann_metad_rct_chunks(table.numel());
+    at::Tensor state;
+    if (state_in.has_value() && state_in->defined())
+        state = opes_tensor(op, "state", *state_in, table, state_in->dim() == 1 && state_in->size(0) == 8, "[8]", true);
+    const at::Tensor partials =
+        opes_tensor(op, "partials", partials_in, table, partials_in.dim() == 2 && partials_in.size(0) >= rows && partials_in.size(1) == 4,
+                    "[at least ceil(table.numel() / 2048), 4]", true);
+    const at::Tensor rct = opes_tensor(op, "rct", rct_in, table, rct_in.dim() == 1 && rct_in.size(0) == 8, "[8]", true);
+    const c10::DeviceGuard guard(table.device());
+    hipStream_t stream = c10::hip::getCurrentHIPStream(table.get_device()).stream();
+    check(molann_metad_rct_f64(table.data_ptr<double>(), table.numel(), kT, inv_dT, state.defined() ? state.data_ptr<double>() : nullptr, stride,
+                               partials.data_ptr<double>(), partials.size(0), rct.data_ptr<double>(), stream),
+          "molann_metad_rct_f64");
+}
+
 // {P} or {P, dP}: the kernel density of an OPES table at points [M, d] and, with `with_grad`, its derivative [M, d] in ONE launch
 // (molann_opes_kernel_sum_f64).  The table as value_and_opes takes it.
 std::vector<at::Tensor> opes_kernel_sum_hip(const at::Tensor& points_in, const at::Tensor& centers_in, const at::Tensor& heights_in,
@@ -2138,6 +2165,7 @@ TORCH_LIBRARY(molann, m) {
           "Tensor sigma0, Tensor? sigma_min, float beta, float threshold, float cutoff, bool fixed_sigma) -> ()");
     m.def("metad_step(Tensor(a!) table, Tensor(b!) state, Tensor(c!)? log, float[] lower, float[] spacing, bool[] periodic, float[] sigma, "
           "int[] columns, Tensor y, Tensor V, float height0, float inv_dT, float cutoff) -> ()");
+    m.def("metad_rct(Tensor table, Tensor? state, Tensor(a!) partials, Tensor(b!) rct, float kT, float inv_dT, int stride) -> ()");
     m.def("opes_kernel_sum(Tensor points, Tensor centers, Tensor heights, Tensor sigma, Tensor? period, float cutoff, bool with_grad) -> Tensor[]");
     m.def("supports_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_backward);
     m.def("supports_mlp_backward(Tensor x, int[] desc, Tensor ref_x) -> int", supports_mlp_backward);
@@ -2182,6 +2210,7 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_opes_table_h", value_and_opes_table_h_hip);
     m.impl("opes_step", opes_step_hip);
     m.impl("metad_step", metad_step_hip);
+    m.impl("metad_rct", metad_rct_hip);
     m.impl("opes_kernel_sum", opes_kernel_sum_hip);
 }
 
