@@ -6,8 +6,11 @@ namespace {
 // frames_value_grid_f64_kernel<G>: x[N, n_inp, 3] -> y[N, d_out] = frames_value_vjp_f64_kernel's y, bit for bit,
 // bias[N] = V(y), the cubic-convolution (Catmull-Rom) interpolant of a table on a regular grid over the d_out <= GRID_MAX_D outputs
 // (grid_axis_f64 / grid_stencil_term_f64 of molann_math.h), and gx[N, n_inp, 3] = dV/dx = J(x)^T dV/dy, everything in double.  The cost
-// of a frame does not depend on what the table was made from: 4^d_out loads.  Lanes, grid-stride loop, rows and steps as
-// frames_value_hills_f64_kernel (a frame's LDS rows are cot[d_out], then frames_value_vjp_f64_kernel's where there is a head):
+// of a frame does not depend on what the table was made from: 4^d_out loads.  Lanes, grid-stride loop, rows and steps are those of
+// frame_value_term_loop_f64 (molann_dev_vjp_f64.inc), written out: this is the one kernel of the family that keeps a loop of its own.
+// Called through the shared loop it computes the same bits but runs 1-3.5 % slower at every batch size (the geometry's scalar registers
+// are spilled differently around the stencil; DESIGN.md, "One frame loop for the value-and-bias kernels"), so a change to steps 1-6 is
+// made here as well.  A frame's LDS rows are cot[d_out], then frames_value_vjp_f64_kernel's where there is a head:
 //   1.-3. rotation, features, head forward; the outputs go to cot, not to y.
 //   3g. lanes k, k + G, ... store y[k] = cot[k].  Every lane forms the d_out axis steps from cot (every lane of the group reads the
 //      same LDS word: a broadcast): four indices, four weights and four derivative weights per axis, in registers.  Lane gl takes the

@@ -6,16 +6,14 @@ namespace {
 // frames_value_hills_f64_kernel<G>: x[N, n_inp, 3] -> y[N, d_out] = frames_value_vjp_f64_kernel's y, bit for bit,
 // bias[N] = V(y) = sum_h w_h exp(-1/2 sum_k ((y_k - c_hk) / sigma_hk)^2) over a table of n_hills hills (the difference wrapped by
 // period_k: hill_term_f64 of molann_math.h) and gx[N, n_inp, 3] = dV/dx = J(x)^T dV/dy, everything in double, d_out <= HILLS_MAX_D.
-// The cotangent depends on y, so it is formed where y is: lanes, grid-stride loop, rows and steps as
-// frames_value_restraint_f64_kernel (a frame's LDS rows are cot[d_out], then frames_value_vjp_f64_kernel's where there is a head):
-//   1.-3. rotation, features, head forward; the outputs go to cot, not to y.
+// Lanes, grid-stride loop, rows and steps 1-6 are frame_value_term_loop_f64's (molann_dev_vjp_f64.inc); the term between
+// steps 3 and 4:
 //   3h. lanes k, k + G, ... store y[k] = cot[k].  Lane gl takes hills gl, gl + G, ... in ascending order: y comes from cot (every lane
 //      of the group reads the same LDS word: a broadcast), the hill's row from global memory through the caches (every group of a
 //      block walks the same rows in the same order); V and the d_out cotangent sums stay in registers (a fixed array, unrolled).
 //      One group_sum per accumulator; then cot[k] = dV/dy_k replaces y and the group's lane 0 stores bias[f].  Every sum has a fixed
 //      order: the same bits on every run, whatever N and the frame's slot in its block.  n_hills == 0: bias 0, cot 0, and neither
 //      the walk nor the sums run.  One row of widths for every hill: its 1 / sigma_k are formed once per frame, not per hill.
-//   4.-6. head backward, the rotation's backward and the per-atom gather on cot, as the restraint kernel.
 // sigma: one row for every hill (sigma_stride 0) or a row per hill (d_out); period: null for none.
 // =============================================================================================
 struct HillsF64Args : VjpF64Args {
@@ -53,36 +51,9 @@ __global__ __launch_bounds__(256) void frames_value_hills_f64_kernel(const doubl
                                                                      const int* __restrict__ align_idx, const double* __restrict__ ref64,
                                                                      const ItemDev* __restrict__ items, const int* __restrict__ hv_ptr,
                                                                      const int* __restrict__ hv_list, HillsF64Args a, F64Mlp m) {
-    static_assert(G == 8 || G == 16 || G == 32 || G == 64, "lane group of 8..64");
     static_assert(HILLS_MAX_D <= G, "lane k of a group stores cot[k]");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int gl = threadIdx.x & (G - 1);
-    const int slot = threadIdx.x / G;
-    const long per_block = blockDim.x / G;
-    const long frame_dw = 3l * a.n_inp;
-    const bool has_align = a.n_align > 0;
-    const bool has_head = m.n_layers > 0;
-    // cot first, then the rows of frames_value_vjp_f64_kernel where there is a head (lds_per_frame = d_out without one)
-    double* cot = (double*)smem + (size_t)slot * a.lds_per_frame;
-    double* feat = cot + a.d_out;
-    double* zrows = feat + a.d_feat;
-    double* row0 = zrows + (a.lds_per_frame - a.d_out - a.d_feat - 2 * a.max_w);
-    double* row1 = row0 + a.max_w;
-    for (long f = (long)blockIdx.x * per_block + slot; f < a.n_frames; f += (long)gridDim.x * per_block) {
-        const double* xf = x + f * frame_dw;
-        double* gxf = gx + f * frame_dw;
-        double* of = out + f * (long)a.d_out;
-        // ---- 1. centroid, covariance, rotation
-        double R[9] = {1., 0., 0., 0., 1., 0., 0., 0., 1.};
-        double h[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
-        V3d c = v3d(0., 0., 0.);
-        if (has_align) frame_rotation_f64<G>(xf, align_idx, ref64, a.n_align, gl, c, h, R);
-        // ---- 2. features
-        frame_features_f64<G>(xf, items, a.n_items, gl, has_align, c, R, has_head ? feat : cot);
-        lds_wave_sync();
-        // ---- 3. head forward, its last layer into cot
-        double* zl = zrows;
-        if (has_head) zl = frame_head_forward_f64<G>(m, gl, feat, zrows, row0, row1, cot);
+    frame_value_term_loop_f64<G>(x, out, gx, align_idx, ref64, items, hv_ptr, hv_list, a, m, blockDim.x,
+                                 [&](long f, int gl, double* cot, double* of) __attribute__((always_inline)) {
         // ---- 3h. the hills on the outputs
         for (int k = gl; k < a.d_out; k += G) of[k] = cot[k];
         double acc[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
@@ -92,18 +63,7 @@ __global__ __launch_bounds__(256) void frames_value_hills_f64_kernel(const doubl
         for (int k = 0; k < HILLS_MAX_D; ++k)
             if (gl == k && k < a.d_out) cot[k] = -acc[k];
         if (gl == 0) bias[f] = v;
-        lds_wave_sync();
-        // ---- 4. head backward
-        const double* df = cot;     // dL/dfeat: the cotangent itself without a head
-        if (has_head) df = frame_head_backward_f64<G>(m, gl, cot, zl, row0, row1);
-        // ---- 5. what the items give the rotation's backward
-        double GH[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
-        V3d cen = v3d(0., 0., 0.);
-        if (has_align) frame_rotation_vjp_f64<G>(xf, ref64, items, a.n_items, a.n_align, gl, df, c, h, R, GH, cen);
-        // ---- 6. atoms (lanes): every row once, its terms in plan order
-        frame_atoms_vjp_f64<G>(xf, gxf, ref64, items, hv_ptr, hv_list, a.n_inp, gl, df, has_align, c, R, GH, cen);
-        lds_wave_sync();   // the next frame's rows are this frame's
-    }
+    });
 }
 
 } // namespace

@@ -1,23 +1,22 @@
 // molann_dev_opes_f64.inc - part of libmolann_hip.so, included by molann_kernels.hip after molann_dev_metric_f64.inc.  Float64 values, an
 // OPES bias on them - the logarithm of a kernel density - and its gradient in one launch (molann_value_and_opes_f64 launches it).
 // Depositing, merging and compressing kernels and the sum the normalisation is formed from: molann_dev_opes_deposit_f64.inc.  Out of
-// scope: float32; a GraphedForces replay; neighbour lists; gradients with respect to the table or the parameters.  An OPES term next to walls and a table, on chosen outputs: frames_value_bias_opes_f64_kernel of
-// molann_dev_bias_opes_f64.inc, a kernel instance of its own that calls this file's walk, so that the instances here keep their code.
+// scope: float32; a GraphedForces replay; neighbour lists; gradients with respect to the table or the parameters.  An OPES term next to
+// walls and a table, on chosen outputs: frames_value_bias_opes_f64_kernel of molann_dev_bias_opes_f64.inc, which calls this file's walk;
+// the same term on a device-resident table: molann_dev_opes_table_f64.inc.
 namespace {
 
 // =============================================================================================
 // frames_value_opes_f64_kernel<G>: x[N, n_inp, 3] -> y[N, d_out] = frames_value_vjp_f64_kernel's y, bit for bit,
 // bias[N] = V(y) = scale log(P(y) / norm + epsilon) with P(y) = sum_h w_h (exp(-q_h / 2) - exp(-cutoff^2 / 2)) over the kernels with
 // q_h = sum_k ((y_k - c_hk) / sigma_hk)^2 < cutoff^2 (the difference wrapped by period_k: opes_term_f64 of molann_math.h) and
-// gx[N, n_inp, 3] = dV/dx = J(x)^T dV/dy, everything in double, d_out <= HILLS_MAX_D.  Lanes, grid-stride loop, rows and steps as
-// frames_value_hills_f64_kernel, through the same device functions:
-//   1.-3. rotation, features, head forward; the outputs go to cot, not to y.
+// gx[N, n_inp, 3] = dV/dx = J(x)^T dV/dy, everything in double, d_out <= HILLS_MAX_D.  Lanes, grid-stride loop, rows and steps 1-6 are
+// frame_value_term_loop_f64's (molann_dev_vjp_f64.inc); the term between steps 3 and 4 (frame_opes_value_term_f64):
 //   3h. lanes k, k + G, ... store y[k] = cot[k].  Lane gl takes kernels gl, gl + G, ... in ascending order (frame_opes_walk_f64), P and
 //      the d_out sums stay in registers; one group_sum per accumulator; then opes_transform_f64 in every lane on the group's sums (the
 //      same values in every lane), cot[k] = dV/dy_k from lane k and bias[f] from lane 0.  Every sum has a fixed order: the same bits on
 //      every run, whatever N and the frame's slot in its block; no atomics, no workspace.  n_kernels == 0: P = 0 and zero sums without
 //      the walk or the group sums, so bias = scale log(epsilon) and cot is exactly 0; the table pointers are not read.
-//   4.-6. head backward, the rotation's backward and the per-atom gather on cot, as the hills kernel.
 // sigma: one row for every kernel (sigma_stride 0) or a row per kernel (d_out); period: null for none.  scale, norm, epsilon and cutoff
 // travel by value: the caller changes the normalisation at every deposit.
 // =============================================================================================
@@ -51,6 +50,26 @@ __device__ __forceinline__ double frame_opes_walk_f64(const double* y, const dou
     return p;
 }
 
+// Step 3h, one text for frames_value_opes_f64_kernel and frames_value_opes_table_f64_kernel (molann_dev_opes_table_f64.inc): y is stored,
+// the walk and opes_transform_f64 run on cot, and after a sync lane k stores cot[k] = dV/dy_k and lane 0 the frame's bias.  n_kernels,
+// sigma_stride and norm come by value - from the arguments or from a table's state, which is all the two kernels differ in.
+template <int G>
+__device__ __forceinline__ void frame_opes_value_term_f64(double* cot, double* of, double* bias_f, const double* __restrict__ centers,
+                                                          const double* __restrict__ heights, const double* __restrict__ sigma,
+                                                          const double* __restrict__ period, long n_kernels, long sigma_stride, double cutoff,
+                                                          double scale, double norm, double epsilon, int d, int gl) {
+    for (int k = gl; k < d; k += G) of[k] = cot[k];
+    double acc[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
+    const double p = frame_opes_walk_f64<G>(cot, centers, heights, sigma, period, n_kernels, sigma_stride, cutoff, d, gl, acc);
+    double dv[HILLS_MAX_D];
+    const double v = opes_transform_f64(p, acc, scale, norm, epsilon, d, dv);
+    lds_wave_sync();   // every lane has read y from cot
+#pragma unroll
+    for (int k = 0; k < HILLS_MAX_D; ++k)
+        if (gl == k && k < d) cot[k] = dv[k];
+    if (gl == 0) *bias_f = v;
+}
+
 template <int G>
 __global__ __launch_bounds__(256) void frames_value_opes_f64_kernel(const double* __restrict__ x, const double* __restrict__ centers,
                                                                     const double* __restrict__ heights, const double* __restrict__ sigma,
@@ -59,59 +78,12 @@ __global__ __launch_bounds__(256) void frames_value_opes_f64_kernel(const double
                                                                     const int* __restrict__ align_idx, const double* __restrict__ ref64,
                                                                     const ItemDev* __restrict__ items, const int* __restrict__ hv_ptr,
                                                                     const int* __restrict__ hv_list, OpesF64Args a, F64Mlp m) {
-    static_assert(G == 8 || G == 16 || G == 32 || G == 64, "lane group of 8..64");
     static_assert(HILLS_MAX_D <= G, "lane k of a group stores cot[k]");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int gl = threadIdx.x & (G - 1);
-    const int slot = threadIdx.x / G;
-    const long per_block = blockDim.x / G;
-    const long frame_dw = 3l * a.n_inp;
-    const bool has_align = a.n_align > 0;
-    const bool has_head = m.n_layers > 0;
-    // cot first, then the rows of frames_value_vjp_f64_kernel where there is a head (lds_per_frame = d_out without one)
-    double* cot = (double*)smem + (size_t)slot * a.lds_per_frame;
-    double* feat = cot + a.d_out;
-    double* zrows = feat + a.d_feat;
-    double* row0 = zrows + (a.lds_per_frame - a.d_out - a.d_feat - 2 * a.max_w);
-    double* row1 = row0 + a.max_w;
-    for (long f = (long)blockIdx.x * per_block + slot; f < a.n_frames; f += (long)gridDim.x * per_block) {
-        const double* xf = x + f * frame_dw;
-        double* gxf = gx + f * frame_dw;
-        double* of = out + f * (long)a.d_out;
-        // ---- 1. centroid, covariance, rotation
-        double R[9] = {1., 0., 0., 0., 1., 0., 0., 0., 1.};
-        double h[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
-        V3d c = v3d(0., 0., 0.);
-        if (has_align) frame_rotation_f64<G>(xf, align_idx, ref64, a.n_align, gl, c, h, R);
-        // ---- 2. features
-        frame_features_f64<G>(xf, items, a.n_items, gl, has_align, c, R, has_head ? feat : cot);
-        lds_wave_sync();
-        // ---- 3. head forward, its last layer into cot
-        double* zl = zrows;
-        if (has_head) zl = frame_head_forward_f64<G>(m, gl, feat, zrows, row0, row1, cot);
-        // ---- 3h. the kernel density on the outputs, its logarithm
-        for (int k = gl; k < a.d_out; k += G) of[k] = cot[k];
-        double acc[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
-        const double p = frame_opes_walk_f64<G>(cot, centers, heights, sigma, period, a.n_kernels, a.sigma_stride, a.cutoff, a.d_out, gl, acc);
-        double dv[HILLS_MAX_D];
-        const double v = opes_transform_f64(p, acc, a.scale, a.norm, a.epsilon, a.d_out, dv);
-        lds_wave_sync();   // every lane has read y from cot
-#pragma unroll
-        for (int k = 0; k < HILLS_MAX_D; ++k)
-            if (gl == k && k < a.d_out) cot[k] = dv[k];
-        if (gl == 0) bias[f] = v;
-        lds_wave_sync();
-        // ---- 4. head backward
-        const double* df = cot;     // dL/dfeat: the cotangent itself without a head
-        if (has_head) df = frame_head_backward_f64<G>(m, gl, cot, zl, row0, row1);
-        // ---- 5. what the items give the rotation's backward
-        double GH[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
-        V3d cen = v3d(0., 0., 0.);
-        if (has_align) frame_rotation_vjp_f64<G>(xf, ref64, items, a.n_items, a.n_align, gl, df, c, h, R, GH, cen);
-        // ---- 6. atoms (lanes): every row once, its terms in plan order
-        frame_atoms_vjp_f64<G>(xf, gxf, ref64, items, hv_ptr, hv_list, a.n_inp, gl, df, has_align, c, R, GH, cen);
-        lds_wave_sync();   // the next frame's rows are this frame's
-    }
+    frame_value_term_loop_f64<G>(x, out, gx, align_idx, ref64, items, hv_ptr, hv_list, a, m, blockDim.x,
+                                 [&](long f, int gl, double* cot, double* of) __attribute__((always_inline)) {
+        frame_opes_value_term_f64<G>(cot, of, bias + f, centers, heights, sigma, period, a.n_kernels, a.sigma_stride, a.cutoff, a.scale,
+                                     a.norm, a.epsilon, a.d_out, gl);
+    });
 }
 
 } // namespace

@@ -13,8 +13,8 @@ namespace {
 // frames_value_opes_table_f64_kernel<G>: frames_value_opes_f64_kernel (molann_dev_opes_f64.inc) with n_kernels and norm taken from
 // state[4] = (n, S, merges, refused) in device memory instead of the launch's arguments: once, before the frame loop, every lane forms
 // n = opes_live_count_f64(state[0], capacity) (held to [0, capacity] whatever the bits) and, where n >= 1, norm = S / n
-// (opes_table_norm_f64) - uniform loads and one division.  The walk (frame_opes_walk_f64), the transform (opes_transform_f64), the rows,
-// the steps and the order of every sum are that kernel's, so for the same n and norm the outputs are its bits.  sigma has a row per
+// (opes_table_norm_f64) - uniform loads and one division.  The term (frame_opes_value_term_f64) and the loop around it
+// (frame_value_term_loop_f64) are that kernel's text, so for the same n and norm the outputs are its bits.  sigma has a row per
 // kernel (stride d_out).  n == 0: no walk, no table pointer read, norm not formed, bias = scale log(epsilon), cot exactly 0.  A state
 // whose S is not finite and > 0 while n >= 1 gives NaN or inf for every frame: the state is the caller's.
 // =============================================================================================
@@ -32,63 +32,16 @@ __global__ __launch_bounds__(256) void frames_value_opes_table_f64_kernel(const 
                                                                           const double* __restrict__ ref64, const ItemDev* __restrict__ items,
                                                                           const int* __restrict__ hv_ptr, const int* __restrict__ hv_list,
                                                                           OpesTableF64Args a, F64Mlp m) {
-    static_assert(G == 8 || G == 16 || G == 32 || G == 64, "lane group of 8..64");
     static_assert(HILLS_MAX_D <= G, "lane k of a group stores cot[k]");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int gl = threadIdx.x & (G - 1);
-    const int slot = threadIdx.x / G;
-    const long per_block = blockDim.x / G;
-    const long frame_dw = 3l * a.n_inp;
-    const bool has_align = a.n_align > 0;
-    const bool has_head = m.n_layers > 0;
     // the table's state: the same two values in every lane
     const long n_kernels = opes_live_count_f64(state[0], a.capacity);
     double norm = 1.0;      // n == 0: P = 0 and zero sums, whatever the norm
     if (n_kernels > 0) norm = opes_table_norm_f64(state[1], n_kernels);
-    // cot first, then the rows of frames_value_vjp_f64_kernel where there is a head (lds_per_frame = d_out without one)
-    double* cot = (double*)smem + (size_t)slot * a.lds_per_frame;
-    double* feat = cot + a.d_out;
-    double* zrows = feat + a.d_feat;
-    double* row0 = zrows + (a.lds_per_frame - a.d_out - a.d_feat - 2 * a.max_w);
-    double* row1 = row0 + a.max_w;
-    for (long f = (long)blockIdx.x * per_block + slot; f < a.n_frames; f += (long)gridDim.x * per_block) {
-        const double* xf = x + f * frame_dw;
-        double* gxf = gx + f * frame_dw;
-        double* of = out + f * (long)a.d_out;
-        // ---- 1. centroid, covariance, rotation
-        double R[9] = {1., 0., 0., 0., 1., 0., 0., 0., 1.};
-        double h[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
-        V3d c = v3d(0., 0., 0.);
-        if (has_align) frame_rotation_f64<G>(xf, align_idx, ref64, a.n_align, gl, c, h, R);
-        // ---- 2. features
-        frame_features_f64<G>(xf, items, a.n_items, gl, has_align, c, R, has_head ? feat : cot);
-        lds_wave_sync();
-        // ---- 3. head forward, its last layer into cot
-        double* zl = zrows;
-        if (has_head) zl = frame_head_forward_f64<G>(m, gl, feat, zrows, row0, row1, cot);
-        // ---- 3h. the kernel density on the outputs, its logarithm
-        for (int k = gl; k < a.d_out; k += G) of[k] = cot[k];
-        double acc[HILLS_MAX_D] = {0., 0., 0., 0., 0., 0., 0., 0.};
-        const double p = frame_opes_walk_f64<G>(cot, centers, heights, sigma, period, n_kernels, (long)a.d_out, a.cutoff, a.d_out, gl, acc);
-        double dv[HILLS_MAX_D];
-        const double v = opes_transform_f64(p, acc, a.scale, norm, a.epsilon, a.d_out, dv);
-        lds_wave_sync();   // every lane has read y from cot
-#pragma unroll
-        for (int k = 0; k < HILLS_MAX_D; ++k)
-            if (gl == k && k < a.d_out) cot[k] = dv[k];
-        if (gl == 0) bias[f] = v;
-        lds_wave_sync();
-        // ---- 4. head backward
-        const double* df = cot;     // dL/dfeat: the cotangent itself without a head
-        if (has_head) df = frame_head_backward_f64<G>(m, gl, cot, zl, row0, row1);
-        // ---- 5. what the items give the rotation's backward
-        double GH[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
-        V3d cen = v3d(0., 0., 0.);
-        if (has_align) frame_rotation_vjp_f64<G>(xf, ref64, items, a.n_items, a.n_align, gl, df, c, h, R, GH, cen);
-        // ---- 6. atoms (lanes): every row once, its terms in plan order
-        frame_atoms_vjp_f64<G>(xf, gxf, ref64, items, hv_ptr, hv_list, a.n_inp, gl, df, has_align, c, R, GH, cen);
-        lds_wave_sync();   // the next frame's rows are this frame's
-    }
+    frame_value_term_loop_f64<G>(x, out, gx, align_idx, ref64, items, hv_ptr, hv_list, a, m, blockDim.x,
+                                 [&](long f, int gl, double* cot, double* of) __attribute__((always_inline)) {
+        frame_opes_value_term_f64<G>(cot, of, bias + f, centers, heights, sigma, period, n_kernels, (long)a.d_out, a.cutoff, a.scale, norm,
+                                     a.epsilon, a.d_out, gl);
+    });
 }
 
 // =============================================================================================

@@ -21,7 +21,7 @@ namespace {
 // The lanes of a frame exchange data through LDS only inside their own wave: lds_wave_sync() orders it, there is no block barrier.
 // Steps 1-3 are the device functions frame_rotation_f64 / frame_features_f64 / frame_head_forward_f64 below, shared with
 // frames_value_jac_f64_kernel (molann_dev_jac_f64.inc); steps 4-6 are frame_head_backward_f64 / frame_rotation_vjp_f64 /
-// frame_atoms_vjp_f64, shared with frames_value_restraint_f64_kernel (molann_dev_restraint_f64.inc).
+// frame_atoms_vjp_f64, shared with frame_value_term_loop_f64 at the end of this file: the loop of the value-and-bias kernels.
 // =============================================================================================
 struct VjpF64Args {
     long n_frames;
@@ -123,7 +123,7 @@ __device__ __forceinline__ double* frame_head_forward_f64(const F64Mlp& m, int g
     return zl;
 }
 
-// Steps 4-6 of a frame, shared with frames_value_restraint_f64_kernel (molann_dev_restraint_f64.inc): they take the cotangent row.
+// Steps 4-6 of a frame, shared with frame_value_term_loop_f64 below: they take the cotangent row.
 // ---- 4. head backward for x only: g is the cotangent, zl is past the last hidden layer's pre-activations; returns dL/dfeat
 template <int G>
 __device__ __forceinline__ const double* frame_head_backward_f64(const F64Mlp& m, int gl, const double* g, double* zl, double* row0, double* row1) {
@@ -254,6 +254,74 @@ __global__ __launch_bounds__(256) void frames_value_vjp_f64_kernel(const double*
         // ---- 6. atoms (lanes): every row once, its terms in plan order
         frame_atoms_vjp_f64<G>(xf, gxf, ref64, items, hv_ptr, hv_list, a.n_inp, gl, df, has_align, c, R, GH, cen);
         if (has_head) lds_wave_sync();   // the next frame's rows are this frame's
+    }
+}
+
+// =============================================================================================
+// frame_value_term_loop_f64<G>: the frame loop of every "values + a term on them + forces in one launch" kernel
+// on all of the model's outputs that runs as fast through it as written out: frames_value_{restraint,hills,opes,opes_table}_f64_kernel.
+// (The grid kernel and the three bias kernels on chosen columns keep the same loop written out; DESIGN.md, "One frame loop for the
+// value-and-bias kernels", has the figures.)  The cotangent of such a kernel
+// depends on y, so it is formed where y is: lanes, grid-stride loop and steps as frames_value_vjp_f64_kernel, whose device functions do
+// the work.  A frame's LDS rows are cot[d_out], then that kernel's where there is a head (none without one): lds_per_frame counts them.
+//   1.-3. rotation, features, head forward.  The outputs - the last layer's with a head, the features without one - are written to
+//      cot, not to y: a lane never reads y back from global memory.
+//   term(f, gl, cot, of): reads y from cot, stores it to of (the frame's row of y) and its energies, and leaves the cotangent in
+//      cot.  Between its last read of a word of cot by another lane and a store to that word it calls lds_wave_sync(); the loop syncs
+//      after it.  Its sums have a fixed order, so the bits do not depend on N or on the frame's slot in its block.
+//   4.-6. head backward, the rotation's backward and the per-atom gather on cot: with the same cotangent the bits of
+//      frames_value_vjp_f64_kernel.
+// block MUST be blockDim.x and nothing else: it decides which frames a slot runs.  It is a parameter only because the kernel has to read
+// it: read in here, behind the inlining, it becomes a vector load of 16 bits and a wait on it at the head of every block (half a
+// microsecond on a one-frame batch) where the kernel's own read is a scalar load among its arguments.
+// =============================================================================================
+template <int G, class Term>
+__device__ __forceinline__ void frame_value_term_loop_f64(const double* __restrict__ x, double* __restrict__ out, double* __restrict__ gx,
+                                                          const int* __restrict__ align_idx, const double* __restrict__ ref64,
+                                                          const ItemDev* __restrict__ items, const int* __restrict__ hv_ptr,
+                                                          const int* __restrict__ hv_list, const VjpF64Args& a, const F64Mlp& m,
+                                                          unsigned block, Term term) {
+    static_assert(G == 8 || G == 16 || G == 32 || G == 64, "lane group of 8..64");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int gl = threadIdx.x & (G - 1);
+    const int slot = threadIdx.x / G;
+    const long per_block = block / G;
+    const long frame_dw = 3l * a.n_inp;
+    const bool has_align = a.n_align > 0;
+    const bool has_head = m.n_layers > 0;
+    double* cot = (double*)smem + (size_t)slot * a.lds_per_frame;
+    double* feat = cot + a.d_out;
+    double* zrows = feat + a.d_feat;
+    double* row0 = zrows + (a.lds_per_frame - a.d_out - a.d_feat - 2 * a.max_w);
+    double* row1 = row0 + a.max_w;
+    for (long f = (long)blockIdx.x * per_block + slot; f < a.n_frames; f += (long)gridDim.x * per_block) {
+        const double* xf = x + f * frame_dw;
+        double* gxf = gx + f * frame_dw;
+        double* of = out + f * (long)a.d_out;
+        // ---- 1. centroid, covariance, rotation
+        double R[9] = {1., 0., 0., 0., 1., 0., 0., 0., 1.};
+        double h[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
+        V3d c = v3d(0., 0., 0.);
+        if (has_align) frame_rotation_f64<G>(xf, align_idx, ref64, a.n_align, gl, c, h, R);
+        // ---- 2. features
+        frame_features_f64<G>(xf, items, a.n_items, gl, has_align, c, R, has_head ? feat : cot);
+        lds_wave_sync();
+        // ---- 3. head forward, its last layer into cot
+        double* zl = zrows;
+        if (has_head) zl = frame_head_forward_f64<G>(m, gl, feat, zrows, row0, row1, cot);
+        // ---- the term on the outputs: y and the energies are stored, cot becomes the cotangent
+        term(f, gl, cot, of);
+        lds_wave_sync();
+        // ---- 4. head backward
+        const double* df = cot;     // dL/dfeat: the cotangent itself without a head
+        if (has_head) df = frame_head_backward_f64<G>(m, gl, cot, zl, row0, row1);
+        // ---- 5. what the items give the rotation's backward
+        double GH[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
+        V3d cen = v3d(0., 0., 0.);
+        if (has_align) frame_rotation_vjp_f64<G>(xf, ref64, items, a.n_items, a.n_align, gl, df, c, h, R, GH, cen);
+        // ---- 6. atoms (lanes): every row once, its terms in plan order
+        frame_atoms_vjp_f64<G>(xf, gxf, ref64, items, hv_ptr, hv_list, a.n_inp, gl, df, has_align, c, R, GH, cen);
+        lds_wave_sync();   // the next frame's rows are this frame's
     }
 }
 
