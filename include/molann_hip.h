@@ -720,7 +720,8 @@ int molann_opes_step_modes_f64(double* centers, double* sigma, double* heights, 
  * more), a sigma or a height0 that is not finite and > 0, an inv_dT that is not finite and >= 0, a cutoff that is NaN or not > 0, a
  * negative stride, count or capacity, a column outside [0, y_stride): MOLANN_E_DESC.  n_walkers == 0: MOLANN_OK, nothing launched.
  * The call only enqueues on `stream` (no workspace, no event, nothing allocated): thread-safe on distinct tables and capturable.  Out
- * of scope: adaptive widths; the reweighting offset c(t) (molann_metad_rct_f64 after this call); walkers on several ranks; float32; more than 3 axes. */
+ * of scope: adaptive widths (molann_metad_widths_f64 and molann_metad_deposit_cov_f64 below); the reweighting offset c(t)
+ * (molann_metad_rct_f64 after this call); walkers on several ranks; float32; more than 3 axes. */
 int molann_metad_deposit_f64(double* table, int32_t d, const int64_t* shape, const double* lower, const double* spacing, const int32_t* periodic,
                              const double* sigma, const int32_t* columns, const double* y, int64_t y_stride, const double* V, int64_t v_stride,
                              int64_t n_walkers, double height0, double inv_dT, double cutoff, double* state, double* log, int64_t log_capacity,
@@ -749,6 +750,58 @@ int molann_metad_deposit_f64(double* table, int32_t d, const int64_t* shape, con
 int64_t molann_metad_rct_chunks(int64_t n_entries); /* rows of partials needed: ceil(n_entries / 2048); 0 for n_entries < 1 */
 int molann_metad_rct_f64(const double* table, int64_t n_entries, double kT, double inv_dT, const double* state, int64_t stride, double* partials,
                          int64_t partial_rows, double* rct, molann_stream_t stream);
+
+/* ADAPTIVE, CORRELATED HILLS of a metadynamics run (the adaptive Gaussians of Branduardi, Bussi and Parrinello; PLUMED's METAD
+ * ADAPTIVE=DIFF / GEOM): a hill is a multivariate Gaussian h exp(-1/2 delta^T C^-1 delta) with a full covariance matrix C.  A matrix is
+ * stored as its row-major upper triangle, T = d (d + 1) / 2 doubles (c00 c01 c02 c11 c12 c22 for d = 3).  Two calls, ONE launch each
+ * (metad_widths_f64_kernel, metad_deposit_cov_f64_kernel; ahead of time: no hipRTC, no plan); molann_amd/csrc/molann_metad_cov.h holds
+ * the arithmetic, which the host twins share.
+ *
+ * molann_metad_widths_f64 keeps the walkers' running statistics and writes the step's covariances.  shape, lower, spacing, periodic
+ * (may be NULL), sigma[d], sigma_min[d] (may be NULL: 0), sigma_max[d] (may be NULL: +inf) and columns[d] (may be NULL: 0..d-1) are HOST
+ * arrays of the grid molann_metad_deposit_f64 takes, read during the call.  mode 1 (DIFF): walker a's row of adapt (DEVICE)
+ * [n_walkers, 1 + d + T] = (n_a, mean, cov) takes one observation of y[a y_stride + columns[k]] (DEVICE, read only) with
+ * decay = 1 / window: a y that is not finite leaves the row's bits and is counted in adapt_state[2]; n_a == 0: mean = y, cov = 0,
+ * n_a = 1; otherwise delta_k = y_k - mean_k (wrapped to delta - P rint(delta / P) on a periodic axis), mean_k += decay delta_k (then
+ * mean_k -= P floor((mean_k - lower_k) / P) on a periodic axis), cov_ij += decay (delta_i delta_j - cov_ij), n_a += 1.  The hill's
+ * covariance is cov once n_a >= window and diag(sigma_k^2) before.  mode 2 (GEOM): nothing is observed (adapt and y may be NULL) and
+ * C_ij = sigma_i sigma_j metric[a metric_stride + columns[i] metric_ld + columns[j]] (DEVICE, read only: the J J^T of
+ * molann_value_and_metric_f64, read in place).  Then the limits, k ascending: target = clamp(C_kk, sigma_min_k^2, sigma_max_k^2); where
+ * target != C_kk, row and column k are multiplied by sqrt(target / C_kk) and C_kk = target exactly (C_kk not > 0: the off-diagonal
+ * entries of k become 0).  With emit != 0 the result goes to cov_out[a cov_stride + ...] (DEVICE); with emit == 0 the call only
+ * observes - the call for the MD steps between two deposits - and cov_out is not touched.  adapt_state[8] (DEVICE) = (observations,
+ * emits, skipped, 0...), counts in doubles updated by one thread (entries 3..7 are not touched).  Refusals, in this order, with
+ * nothing enqueued: a NULL adapt_state, shape, lower, spacing or sigma, a NULL y or adapt in mode 1, metric in mode 2, cov_out with
+ * emit, where n_walkers > 0: MOLANN_E_NULL; an adapt, adapt_state, cov_out, y or metric that is not 8-byte aligned:
+ * MOLANN_E_ALIGNMENT; d outside 1..3: MOLANN_E_UNSUPPORTED; another mode, a grid molann_value_and_grid_f64 refuses, a sigma that is not
+ * finite and > 0, a sigma_min that is not finite and >= 0, a sigma_max below sigma_min, window < 1 in mode 1, a negative stride or
+ * count, cov_stride < T with emit, a column outside [0, y_stride) (mode 1) or [0, metric_ld) (mode 2), a metric_stride that is neither
+ * 0 nor at least metric_ld^2: MOLANN_E_DESC.  n_walkers == 0: MOLANN_OK, nothing launched.
+ *
+ * molann_metad_deposit_cov_f64 is molann_metad_deposit_f64 with walker a's covariance cov[a cov_stride + ...] (DEVICE, read only;
+ * cov_stride 0: one matrix for all) in the place of sigma: the same table, grid arrays, y, V, heights, state slots, order of additions
+ * (walker order, no atomics, the same bits on every run) and tiles.  C = L L^T with pivots p_k = C_kk - sum_{j<k} L_kj^2; the matrix is
+ * usable when every entry is finite and every p_k > 1e-12 C_kk.  A walker is valid when molann_metad_deposit_f64's conditions hold and
+ * its matrix is usable; any other changes no entry and is counted in state[1].  Every grid point gets table[g] += h_a exp(-(0.5 q)),
+ * q = |L^-1 delta|^2 by forward substitution (no inverse is formed), where q <= cutoff^2.  A tile is skipped for a hill only when a
+ * single axis's bound delta_k^2 / C_kk over the tile exceeds cutoff^2 (1 + 1e-12) - q >= delta_k^2 / C_kk by Cauchy-Schwarz; the bounds
+ * are not summed - and every entry decides by its own q, so skipping changes no result; a tile no hill reaches is neither read nor
+ * written.  log (DEVICE, may be NULL) [log_capacity, d + T + 1] gets one row (centre_k..., C in its triangle, height) per valid walker.
+ * Refusals, in this order, with nothing enqueued: a NULL table, state, y, V, cov, shape, lower or spacing where n_walkers > 0:
+ * MOLANN_E_NULL; a table, state, y, V, cov or log that is not 8-byte aligned: MOLANN_E_ALIGNMENT; d outside 1..3: MOLANN_E_UNSUPPORTED;
+ * what molann_metad_deposit_f64 answers with MOLANN_E_DESC (but for sigma), or a cov_stride that is neither 0 nor at least T:
+ * MOLANN_E_DESC.  n_walkers == 0: MOLANN_OK, nothing launched.  Both calls only enqueue on `stream` (no workspace, no event, nothing
+ * allocated): capturable.  The deposit never reads adapt: every block of it would race the one writer, so the covariances go through
+ * cov_out.  Out of scope: a frame kernel that fuses the bias with the metric; heights renormalised by the determinant; walkers on
+ * several ranks; float32; more than 3 axes. */
+int molann_metad_widths_f64(int32_t d, const int64_t* shape, const double* lower, const double* spacing, const int32_t* periodic, const double* sigma,
+                            const double* sigma_min, const double* sigma_max, const int32_t* columns, const double* y, int64_t y_stride,
+                            const double* metric, int64_t metric_stride, int64_t metric_ld, int64_t n_walkers, int32_t mode, int64_t window, int32_t emit,
+                            double* adapt, double* adapt_state, double* cov_out, int64_t cov_stride, molann_stream_t stream);
+int molann_metad_deposit_cov_f64(double* table, int32_t d, const int64_t* shape, const double* lower, const double* spacing, const int32_t* periodic,
+                                 const int32_t* columns, const double* y, int64_t y_stride, const double* V, int64_t v_stride, const double* cov,
+                                 int64_t cov_stride, int64_t n_walkers, double height0, double inv_dT, double cutoff, double* state, double* log,
+                                 int64_t log_capacity, molann_stream_t stream);
 
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
@@ -850,6 +903,16 @@ int molann_selftest_metad_deposit_f64(double* table, int32_t d, const int64_t* s
  * same functions */
 int molann_selftest_metad_rct_f64(const double* table, int64_t n_entries, double kT, double inv_dT, const double* state, int64_t stride,
                                   double* partials, int64_t partial_rows, double* rct);
+/* molann_metad_widths_f64 and molann_metad_deposit_cov_f64 on the host: the same arguments as HOST pointers, the same refusals, the
+ * same tiles, and per walker and per entry the functions their kernels call */
+int molann_selftest_metad_widths_f64(int32_t d, const int64_t* shape, const double* lower, const double* spacing, const int32_t* periodic,
+                                     const double* sigma, const double* sigma_min, const double* sigma_max, const int32_t* columns, const double* y,
+                                     int64_t y_stride, const double* metric, int64_t metric_stride, int64_t metric_ld, int64_t n_walkers, int32_t mode,
+                                     int64_t window, int32_t emit, double* adapt, double* adapt_state, double* cov_out, int64_t cov_stride);
+int molann_selftest_metad_deposit_cov_f64(double* table, int32_t d, const int64_t* shape, const double* lower, const double* spacing,
+                                          const int32_t* periodic, const int32_t* columns, const double* y, int64_t y_stride, const double* V,
+                                          int64_t v_stride, const double* cov, int64_t cov_stride, int64_t n_walkers, double height0, double inv_dT,
+                                          double cutoff, double* state, double* log, int64_t log_capacity);
 /* one axis' step of molann_value_and_grid_f64 on the host, through the function its kernel calls: the four table indices, the four
  * weights and the four derivative weights (s w' / spacing) for output value y on an axis of n points; any of the three may be NULL */
 void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]);

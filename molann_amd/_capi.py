@@ -253,6 +253,12 @@ def lib():
             "molann_selftest_opes_step_modes_f64": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int32), vp, i64, i64,
                                                           vp, vp, vp, ctypes.c_double, ctypes.c_double, i64, ctypes.c_double, ctypes.c_double, i32]),
             "molann_metad_deposit_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64] + [ctypes.c_double] * 3 + [vp, vp, i64, vp]),
+            "molann_metad_widths_f64": (i32, [i32] + [vp] * 9 + [i64, vp, i64, i64, i64, i32, i64, i32, vp, vp, vp, i64, vp]),
+            "molann_selftest_metad_widths_f64": (i32, [i32] + [vp] * 9 + [i64, vp, i64, i64, i64, i32, i64, i32, vp, vp, vp, i64]),
+            "molann_metad_deposit_cov_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64] + [ctypes.c_double] * 3
+                                             + [vp, vp, i64, vp]),
+            "molann_selftest_metad_deposit_cov_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64] + [ctypes.c_double] * 3
+                                                      + [vp, vp, i64]),
             "molann_metad_rct_chunks": (i64, [i64]),
             "molann_metad_rct_f64": (i32, [vp, i64, ctypes.c_double, ctypes.c_double, vp, i64, vp, i64, vp, vp]),
             "molann_selftest_metad_rct_f64": (i32, [vp, i64, ctypes.c_double, ctypes.c_double, vp, i64, vp, i64, vp]),
@@ -872,6 +878,43 @@ def metad_deposit_f64(table, arrays, y, V, height0, inv_dT, cutoff, state, log=N
                                           float("inf") if cutoff is None else float(cutoff), state.data_ptr(), _address(log),
                                           0 if log is None else log.shape[0], torch.cuda.current_stream().cuda_stream)
     _check(code, "molann_metad_deposit_f64")
+
+
+METAD_COV_DIFF, METAD_COV_GEOM = 1, 2
+
+
+def metad_limit_arrays(sigma_min, sigma_max, d):
+    """``(sigma_min, sigma_max)`` of `molann_metad_widths_f64` as ctypes arrays; None stays None (NULL: 0, +inf)."""
+    F = lambda v: None if v is None else (ctypes.c_double * d)(*[float(c) for c in v])  # noqa: E731
+    return F(sigma_min), F(sigma_max)
+
+
+def metad_widths_f64(arrays, limits, mode, window, emit, adapt, adapt_state, cov, y=None, metric=None):
+    """`molann_metad_widths_f64` on torch's current stream, one launch, nothing read back.  `mode` METAD_COV_DIFF: the rows of `adapt`
+    [W, 1 + d + T] take one observation of `y` [W, n_out]; METAD_COV_GEOM: the covariances come from `metric` [W, n_out, n_out]
+    (contiguous).  With `emit` the walkers' hill covariances go to `cov` [W, T]; `adapt_state` [8] counts.  `arrays`:
+    `metad_grid_arrays`, `limits`: `metad_limit_arrays`, made once.  float64 tensors on one device, contiguous; their shapes are the
+    caller's to check (`molann_amd.bias.MetadRun` does)."""
+    shape, lower, spacing, periodic, sigma, columns = arrays
+    n_walkers = cov.shape[0]
+    n_out = 0 if metric is None else metric.shape[-1]
+    code = lib().molann_metad_widths_f64(len(shape), shape, lower, spacing, periodic, sigma, limits[0], limits[1], columns, _address(y),
+                                         0 if y is None else y.stride(0), _address(metric), n_out * n_out, n_out, n_walkers, int(mode), int(window),
+                                         1 if emit else 0, _address(adapt), adapt_state.data_ptr(), cov.data_ptr(), cov.stride(0),
+                                         torch.cuda.current_stream().cuda_stream)
+    _check(code, "molann_metad_widths_f64")
+
+
+def metad_deposit_cov_f64(table, arrays, y, V, cov, height0, inv_dT, cutoff, state, log=None):
+    """`molann_metad_deposit_cov_f64` on torch's current stream: `metad_deposit_f64` with walker a's hill a multivariate Gaussian of
+    covariance `cov[a]` ([W, T] upper triangles, or columns of a wider tensor: its stride is passed on); `log` is [capacity, d + T + 1]
+    or None.  One launch, nothing read back.  The `sigma` of `arrays` is not read."""
+    shape, lower, spacing, periodic, _, columns = arrays
+    code = lib().molann_metad_deposit_cov_f64(table.data_ptr(), len(shape), shape, lower, spacing, periodic, columns, y.data_ptr(), y.stride(0),
+                                              V.data_ptr(), V.stride(0), cov.data_ptr(), cov.stride(0), y.shape[0], float(height0), float(inv_dT),
+                                              float("inf") if cutoff is None else float(cutoff), state.data_ptr(), _address(log),
+                                              0 if log is None else log.shape[0], torch.cuda.current_stream().cuda_stream)
+    _check(code, "molann_metad_deposit_cov_f64")
 
 
 def metad_rct_f64(table, kT, inv_dT, state, stride, partials, rct):

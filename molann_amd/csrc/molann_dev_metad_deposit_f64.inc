@@ -2,7 +2,7 @@
 // other half of a metadynamics run on a table, between the steps that molann_value_and_grid_f64 / molann_value_and_bias_f64 serve:
 // metad_deposit_f64_kernel adds a step's hills to the device-resident table in place, with well-tempered heights formed from the bias
 // those launches wrote (molann_metad_deposit_f64 launches it).  The reweighting offset c(t) is the next file's (molann_dev_metad_rct_f64.inc), queued after this
-// launch.  Out of scope: adaptive widths; float32; tables of more than GRID_MAX_D axes.
+// launch.  Adaptive, correlated hills are molann_dev_metad_cov_f64.inc's.  Out of scope: float32; tables of more than GRID_MAX_D axes.
 namespace {
 
 struct MetadDepositArgs {

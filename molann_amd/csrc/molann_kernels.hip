@@ -48,6 +48,7 @@
 #include "molann_math.h"
 #include "molann_opes_modes.h"
 #include "molann_metad_rct.h"
+#include "molann_metad_cov.h"
 #include "jit_sources.gen.h"
 
 using namespace molann;
@@ -76,6 +77,7 @@ using namespace molann;
 #include "molann_dev_opes_adaptive_f64.inc"
 #include "molann_dev_metad_deposit_f64.inc"
 #include "molann_dev_metad_rct_f64.inc"
+#include "molann_dev_metad_cov_f64.inc"
 // Host code (what `make san` instruments: -fno-gpu-sanitize leaves the device code alone):
 #include "molann_host_plan.inc"
 #include "molann_host_jit.inc"
@@ -88,3 +90,4 @@ using namespace molann;
 #include "molann_opes_deposit_f64.inc"
 #include "molann_metad_deposit_f64.inc"
 #include "molann_metad_rct_f64.inc"
+#include "molann_metad_cov_f64.inc"
