@@ -803,6 +803,63 @@ int molann_metad_deposit_cov_f64(double* table, int32_t d, const int64_t* shape,
                                  int64_t cov_stride, int64_t n_walkers, double height0, double inv_dT, double cutoff, double* state, double* log,
                                  int64_t log_capacity, molann_stream_t stream);
 
+/* PARALLEL-BIAS METADYNAMICS (Pfaendtner and Bonomi, JCTC 2015; PLUMED's PBMETAD) on 1 <= K <= 8 chosen outputs: K one-dimensional
+ * tables, one per output, joined by a soft minimum, so that memory and the cost of a step grow linearly in K where a table over K
+ * outputs has n^K entries.  Two calls, each ONE launch (ahead of time: no hipRTC); a run alternates them with nothing read back.
+ *
+ * molann_value_and_pbmetad_f64 (frames_value_pbmetad_f64_kernel): out[N, out_dim] = molann_value_and_vjp_f64's out, bit for bit;
+ * energies[N, energies_stride >= 2 + K] = (E_r, V_PB, V_0 .. V_{K-1}); grad_x[N, n_inp, 3] = d(E_r + V_PB) / dx.  With
+ * y_k = out[columns[k]] (columns: a HOST array of K distinct indices in any order, NULL for 0..K-1):
+ *   V_k  = table k's Catmull-Rom interpolant at y_k, molann_value_and_grid_f64's on one axis: shape[k] >= 4 points at
+ *          lower[k] + i spacing[k], periodic with period shape[k] spacing[k] where periodic[k] != 0 (periodic may be NULL: none).  The
+ *          K tables lie back to back in ONE buffer `table` (DEVICE) of sum_k shape[k] < 2^31 doubles, table k at sum_{j<k} shape[j];
+ *          shape, lower, spacing, periodic: HOST arrays of K entries, read during the call;
+ *   m = min_k V_k, e_k = exp(-(V_k - m) / kT), S = ((e_0 + e_1) + ...), w_k = e_k / S, V_PB = m - kT log S, dV_PB/dy_k = w_k V_k'.
+ *          K = 1: V_PB = V_0 and the cotangent V_0', bit for bit.  A V_k that is not finite makes that frame's V_PB and grad_x NaN and
+ *          changes no other frame;
+ *   E_r: molann_value_and_restraint_f64's energy on ALL out_dim outputs; absent when kappa == NULL: exactly 0, its pointers not read.
+ * Every sum has a fixed order: the same bits on every run, whatever n_frames.  Plans: molann_value_and_bias_f64's.  Refusals, in this
+ * order, nothing being written: a NULL plan, terms, x, out, energies, grad_x, table, shape, lower, spacing or center of a present
+ * restraint: MOLANN_E_NULL; a pointer that is not 8-byte aligned: MOLANN_E_ALIGNMENT; MOLANN_E_STAGE / MOLANN_E_UNSUPPORTED as
+ * molann_value_and_bias_f64; n_columns < 1: MOLANN_E_DESC, > 8: MOLANN_E_UNSUPPORTED; a column repeated or outside [0, out_dim):
+ * MOLANN_E_INDEX; an axis molann_value_and_grid_f64 refuses, a kT that is not finite and > 0, 2^31 entries or more, an energies_stride
+ * below 2 + K, a center_stride other than 0 or out_dim: MOLANN_E_DESC.  n_frames < 0: MOLANN_E_DESC; n_frames == 0: nothing is read or
+ * launched.  The call only enqueues on `stream` (no workspace, no atomics, no event): thread-safe and capturable.
+ *
+ * molann_pbmetad_deposit_f64 (pbmetad_deposit_f64_kernel): the hills of n_walkers walkers are added, in place, to the K tables.
+ * Walker a's centre on axis k is y[a y_stride + columns[k]] and its bias V[a v_stride + k] (DEVICE, read only; v_stride >= K), so
+ * columns 2.. of the energies above are read where they are.  Per walker a, ascending: w_ak as above from (V_a0 .. V_a,K-1);
+ * h_ak = height0 exp(-V_ak inv_dT) w_ak (inv_dT = 1 / (kT (biasfactor - 1)); 0: h_ak = height0 w_ak); the walker is valid when every
+ * V_ak, centre and h_ak is finite - any other changes no table and is counted in state[1]; then
+ * T_k[g] = T_k[g] + h_ak exp(-1/2 (delta / sigma_k)^2) where h_ak > 0 and (delta / sigma_k)^2 <= cutoff^2 (+inf: everywhere), delta
+ * and its periodic wrap being molann_metad_deposit_f64's.  An h_ak that underflows to exactly 0 leaves table k's bits; the walker still
+ * counts as a hill.  An entry is written by one thread, which adds the walkers' terms in their order: no atomics, the same bits on
+ * every run, and two queued deposits give the bits of one deposit of the concatenated walkers; with K = 1 the bits of
+ * molann_metad_deposit_f64.  A tile of 256 entries that no hill reaches is neither read nor written.  state[8] (DEVICE) = (hills,
+ * refused, sum_heights = sum_a sum_k h_ak, steps, logged, 0, 0, 0); log (DEVICE, may be NULL) [log_capacity, 2 K] gets one row
+ * (centre_0.., h_0..) per valid walker, by molann_metad_deposit_f64's overflow rule.  Refusals: molann_metad_deposit_f64's, in its
+ * order, per axis (n_axes outside 1..8: MOLANN_E_UNSUPPORTED; 2^31 entries or more in all, a kT that is not finite and > 0, a v_stride
+ * below K: MOLANN_E_DESC), then a repeated column: MOLANN_E_INDEX.  n_walkers == 0: MOLANN_OK, nothing launched.  The call only
+ * enqueues on `stream`: capturable.  Out of scope: c(t); adaptive widths; per-axis heights or bias factors; partitioned families;
+ * walkers on several ranks; float32. */
+typedef struct molann_pbmetad_terms_f64 {
+    /* restraint on all outputs; absent when kappa == NULL */
+    const double* center; int64_t center_stride; const double *kappa, *restraint_period, *flat;
+    /* the K tables */
+    int32_t n_columns; const int32_t* columns;
+    const double* table; const int64_t* shape; const double *lower, *spacing; const int32_t* periodic;
+    double kT;
+} molann_pbmetad_terms_f64;
+int molann_value_and_pbmetad_f64(molann_plan* plan, const double* x, int64_t n_frames, const double* const* W, const double* const* b,
+                                 const molann_pbmetad_terms_f64* terms, double* out, double* energies, int64_t energies_stride, double* grad_x,
+                                 molann_stream_t stream);
+/* 1 when molann_value_and_pbmetad_f64 serves the plan (molann_value_and_bias_f64 serves it), 0 otherwise. */
+int molann_plan_supports_value_and_pbmetad_f64(const molann_plan* plan);
+int molann_pbmetad_deposit_f64(double* table, int32_t n_axes, const int64_t* shape, const double* lower, const double* spacing,
+                               const int32_t* periodic, const double* sigma, const int32_t* columns, const double* y, int64_t y_stride,
+                               const double* V, int64_t v_stride, int64_t n_walkers, double height0, double inv_dT, double kT, double cutoff,
+                               double* state, double* log, int64_t log_capacity, molann_stream_t stream);
+
 /* molann_forward_packed_f32 that also writes features[N, feature_dim] (what molann_features_f32 would give), for a
  * backward through molann_mlp_backward_f32 + molann_features_backward_f32 without the recompute.  Plans whose MLP
  * is fused into the lane kernel, and large-frame plans with a head within the fused MLP's limits (the features are written
@@ -913,6 +970,16 @@ int molann_selftest_metad_deposit_cov_f64(double* table, int32_t d, const int64_
                                           const int32_t* periodic, const int32_t* columns, const double* y, int64_t y_stride, const double* V,
                                           int64_t v_stride, const double* cov, int64_t cov_stride, int64_t n_walkers, double height0, double inv_dT,
                                           double cutoff, double* state, double* log, int64_t log_capacity);
+/* one frame of molann_value_and_pbmetad_f64 on the host, through the functions its kernel calls and in one lane's order (every pointer
+ * of `terms` a HOST pointer here; center is one row): energies[2 + K] = (E_r, V_PB, V_0 ..), dy[d_out] = the cotangent.  Returns
+ * MOLANN_OK, or the code molann_value_and_pbmetad_f64 gives the same terms (nothing written then) */
+int molann_selftest_pbmetad_f64(const double* y, int d_out, const molann_pbmetad_terms_f64* terms, double* energies, double* dy);
+/* molann_pbmetad_deposit_f64 on the host: the same arguments as HOST pointers, the same refusals, the same tiles, and per entry the
+ * walkers' terms in their order through the functions its kernel calls */
+int molann_selftest_pbmetad_deposit_f64(double* table, int32_t n_axes, const int64_t* shape, const double* lower, const double* spacing,
+                                        const int32_t* periodic, const double* sigma, const int32_t* columns, const double* y, int64_t y_stride,
+                                        const double* V, int64_t v_stride, int64_t n_walkers, double height0, double inv_dT, double kT,
+                                        double cutoff, double* state, double* log, int64_t log_capacity);
 /* one axis' step of molann_value_and_grid_f64 on the host, through the function its kernel calls: the four table indices, the four
  * weights and the four derivative weights (s w' / spacing) for output value y on an axis of n points; any of the three may be NULL */
 void molann_selftest_grid_axis_f64(double y, int64_t n, double lower, double spacing, int32_t periodic, int64_t idx[4], double w[4], double dw[4]);

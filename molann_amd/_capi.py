@@ -118,6 +118,53 @@ def bias_terms_f64(restraint=None, hills=None, grid=None, ptr=lambda t: t.data_p
     return t, keep
 
 
+class PbmetadTermsF64(ctypes.Structure):
+    """molann_pbmetad_terms_f64 of include/molann_hip.h: the terms of `molann_value_and_pbmetad_f64`."""
+    _fields_ = [("center", ctypes.c_void_p), ("center_stride", ctypes.c_int64), ("kappa", ctypes.c_void_p),
+                ("restraint_period", ctypes.c_void_p), ("flat", ctypes.c_void_p),
+                ("n_columns", ctypes.c_int32), ("columns", ctypes.POINTER(ctypes.c_int32)),
+                ("table", ctypes.c_void_p), ("shape", ctypes.POINTER(ctypes.c_int64)), ("lower", ctypes.POINTER(ctypes.c_double)),
+                ("spacing", ctypes.POINTER(ctypes.c_double)), ("periodic", ctypes.POINTER(ctypes.c_int32)), ("kT", ctypes.c_double)]
+
+
+def pbmetad_terms_f64(tables, restraint=None, ptr=lambda t: t.data_ptr()):
+    """A `PbmetadTermsF64` and the host arrays it points into (keep both alive for the call).  tables: (columns, table, shape, lower,
+    spacing, periodic, kT) - columns None is the identity list and needs the count in its place: (None, K); shape, lower, spacing or
+    periodic None stays NULL; restraint: None or (center, kappa, period, flat, center_stride).  Tensors give their addresses through
+    `ptr`."""
+    t, keep = PbmetadTermsF64(), []
+
+    def host(ctype, values):
+        if values is None:
+            return None
+        arr = (ctype * max(len(values), 1))(*values)
+        keep.append(arr)
+        return arr
+
+    if restraint is not None:
+        center, kappa, period, flat, stride = restraint
+        t.center, t.center_stride, t.kappa, t.restraint_period, t.flat = (None if center is None else ptr(center), stride, None if kappa is None else ptr(kappa),
+                                                                          None if period is None else ptr(period), None if flat is None else ptr(flat))
+    cols, table, shape, lower, spacing, periodic, kT = tables
+    if isinstance(cols, tuple) and len(cols) == 2 and cols[0] is None:
+        t.n_columns = int(cols[1])
+    else:
+        t.n_columns = len(cols)
+        arr = host(ctypes.c_int32, [int(c) for c in cols])
+        if arr is not None:
+            t.columns = arr
+    t.table = None if table is None else ptr(table)
+    for name, ctype, values in (("shape", ctypes.c_int64, None if shape is None else [int(v) for v in shape]),
+                                ("lower", ctypes.c_double, None if lower is None else [float(v) for v in lower]),
+                                ("spacing", ctypes.c_double, None if spacing is None else [float(v) for v in spacing]),
+                                ("periodic", ctypes.c_int32, None if periodic is None else [1 if v else 0 for v in periodic])):
+        arr = host(ctype, values)
+        if arr is not None:
+            setattr(t, name, arr)
+    t.kT = float(kT)
+    return t, keep
+
+
 class OpesTermF64(ctypes.Structure):
     """molann_opes_term_f64 of include/molann_hip.h: the OPES term of `molann_value_and_bias_opes_f64`."""
     _fields_ = [("n_columns", ctypes.c_int32), ("columns", ctypes.POINTER(ctypes.c_int32)),
@@ -259,6 +306,13 @@ def lib():
                                              + [vp, vp, i64, vp]),
             "molann_selftest_metad_deposit_cov_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64] + [ctypes.c_double] * 3
                                                       + [vp, vp, i64]),
+            "molann_value_and_pbmetad_f64": (i32, [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(PbmetadTermsF64), vp, vp, i64,
+                                             vp, vp]),
+            "molann_plan_supports_value_and_pbmetad_f64": (i32, [vp]),
+            "molann_selftest_pbmetad_f64": (i32, [vp, i32, ctypes.POINTER(PbmetadTermsF64), vp, vp]),
+            "molann_pbmetad_deposit_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64] + [ctypes.c_double] * 4 + [vp, vp, i64, vp]),
+            "molann_selftest_pbmetad_deposit_f64": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64] + [ctypes.c_double] * 4
+                                                    + [vp, vp, i64]),
             "molann_metad_rct_chunks": (i64, [i64]),
             "molann_metad_rct_f64": (i32, [vp, i64, ctypes.c_double, ctypes.c_double, vp, i64, vp, i64, vp, vp]),
             "molann_selftest_metad_rct_f64": (i32, [vp, i64, ctypes.c_double, ctypes.c_double, vp, i64, vp, i64, vp]),
@@ -695,6 +749,29 @@ class Plan(object):
         del keep
         return out, energies, grad_x
 
+    def supports_value_and_pbmetad_f64(self):
+        """True when `value_and_pbmetad_f64` serves this plan: `value_and_bias_f64` serves it (nothing is built)."""
+        return lib().molann_plan_supports_value_and_pbmetad_f64(self._handle) == 1
+
+    def value_and_pbmetad_f64(self, x, weights, biases, out, energies, grad_x, tables, restraint=None):
+        """out[N, d_out], energies[N, 2 + K] = (restraint, V_PB, V_0 ..) and grad_x[N, n_inp, 3] = d(restraint + V_PB) / d x in float64,
+        one launch of frames_value_pbmetad_f64_kernel.  `weights` / `biases` as `value_and_vjp_f64` takes them.  tables: (columns, table,
+        shape, lower, spacing, periodic, kT) - the K one-dimensional tables back to back in `table` on x's device, the rest host values
+        read during the call; restraint: None or (center, kappa, period, flat) as `value_and_restraint_f64`, on all outputs.  The
+        energies' row stride is passed on, so a slice of a wider tensor serves."""
+        W, B = _layer_pointers(weights, biases)
+        d_out = out.numel() // max(x.shape[0], 1)
+        r = None
+        if restraint is not None:
+            center, kappa, period, flat = restraint
+            r = (center, kappa, period, flat, 0 if center.numel() == d_out and center.dim() < 2 else d_out)
+        terms, keep = pbmetad_terms_f64(tables, r)
+        stride = energies.stride(0) if energies.dim() == 2 and energies.shape[0] > 1 else energies.shape[-1]
+        self._launch("molann_value_and_pbmetad_f64", x.data_ptr(), x.shape[0], W, B, ctypes.byref(terms), out.data_ptr(), energies.data_ptr(),
+                     stride, grad_x.data_ptr())
+        del keep
+        return out, energies, grad_x
+
     def supports_value_and_bias_opes_f64(self):
         """True when `value_and_bias_opes_f64` serves this plan: `value_and_bias_f64` serves it (nothing is built)."""
         return lib().molann_plan_supports_value_and_bias_opes_f64(self._handle) == 1
@@ -878,6 +955,22 @@ def metad_deposit_f64(table, arrays, y, V, height0, inv_dT, cutoff, state, log=N
                                           float("inf") if cutoff is None else float(cutoff), state.data_ptr(), _address(log),
                                           0 if log is None else log.shape[0], torch.cuda.current_stream().cuda_stream)
     _check(code, "molann_metad_deposit_f64")
+
+
+def pbmetad_deposit_f64(table, arrays, y, V, height0, inv_dT, kT, cutoff, state, log=None):
+    """`molann_pbmetad_deposit_f64` on torch's current stream: the hills of the walkers `y` [W, n_out] (centres in the columns the arrays
+    name) with per-axis biases `V` ([W, K], or columns of a wider tensor: its row stride is passed on) are added to the K one-dimensional
+    tables back to back in `table`, every height weighted by its axis' share of the soft minimum at `kT`; `state` [8] and `log`
+    ([capacity, 2 K] or None) are updated, in one launch; nothing is read back.  `arrays`: `metad_grid_arrays` over the K axes, made
+    once.  float64 tensors on one device, `table`, `state`, `log` contiguous; `cutoff` None is +inf.  The tensors' shapes are the
+    caller's to check (`molann_amd.bias.PBMetadRun` does)."""
+    shape, lower, spacing, periodic, sigma, columns = arrays
+    code = lib().molann_pbmetad_deposit_f64(table.data_ptr(), len(shape), shape, lower, spacing, periodic, sigma, columns, y.data_ptr(),
+                                            y.stride(0) if y.shape[0] > 1 else y.shape[1], V.data_ptr(),
+                                            V.stride(0) if V.shape[0] > 1 else max(V.shape[1], len(shape)), y.shape[0], float(height0),
+                                            float(inv_dT), float(kT), float("inf") if cutoff is None else float(cutoff), state.data_ptr(),
+                                            _address(log), 0 if log is None else log.shape[0], torch.cuda.current_stream().cuda_stream)
+    _check(code, "molann_pbmetad_deposit_f64")
 
 
 METAD_COV_DIFF, METAD_COV_GEOM = 1, 2

@@ -925,6 +925,7 @@ def _run_features(feature_owner, x, align_layer, plan_owner=None):
 # value_and_hills / value_and_grid / value_and_bias, and value_and_opes and value_and_opes_table of both.  What differs
 # between them, by kind; the checks and the two ways to the kernel are written once below.
 _VJP, _JACOBIAN, _METRIC, _RESTRAINT, _HILLS, _GRID, _BIAS, _OPES, _BIAS_OPES, _OPES_TABLE, _BIAS_OPES_TABLE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+_PBMETAD = 11             # value_and_pbmetad: K one-dimensional tables joined by a soft minimum (a kernel of its own)
 _HILLS_MAX_D_OUT = 8      # HILLS64_MAX_D_OUT of csrc/molann_value_f64.inc: the kernel's cotangent sums are a register array
 _JACOBIAN_ROUTE = "use value_and_vjp on x.expand(d_out, -1, -1) with torch.eye(d_out) as cotangent"
 _METRIC_ROUTE = 'use value_and_jacobian and torch.einsum("fkai,a,flai->fkl", jac, w, jac)'
@@ -957,18 +958,24 @@ _BIAS_OPES_TABLE_ROUTE = ("read the table's state (`OpesTable.read_state`), then
                           "or: " + _BIAS_OPES_ROUTE)
 _BIAS_OPES_TABLE_FEATURES_ROUTE = ("read the table's state (`OpesTable.read_state`), then `value_and_bias(opes=table.record(scale, S / n, epsilon, "
                                    "columns))`, or: " + _BIAS_OPES_FEATURES_ROUTE)
+# value_and_pbmetad (_PBMETAD): what remains where it refuses
+_PBMETAD_ROUTE = ("use `model(x)`, interpolate the K tables and their derivatives on `y[:, columns]` with torch, form the soft minimum "
+                  "`-kT logsumexp(-V / kT)` and its weights, scatter `w_k V_k'` into a cotangent, then `value_and_vjp`")
+_PBMETAD_FEATURES_ROUTE = ("use `module(x)` on an x that requires grad, interpolate the K tables with torch, form the soft minimum "
+                           "`-kT logsumexp(-V / kT)` and take torch.autograd.grad")
 _ONE_LAUNCH_NAME = ("value_and_vjp", "value_and_jacobian", "value_and_metric", "value_and_restraint", "value_and_hills", "value_and_grid",
-                    "value_and_bias", "value_and_opes", "value_and_bias", "value_and_opes_table", "value_and_bias")
+                    "value_and_bias", "value_and_opes", "value_and_bias", "value_and_opes_table", "value_and_bias", "value_and_pbmetad")
 # the route that remains where the call refuses
 _ONE_LAUNCH_ROUTE = (None, _JACOBIAN_ROUTE, _METRIC_ROUTE, _RESTRAINT_ROUTE, _HILLS_ROUTE, _GRID_ROUTE, _BIAS_ROUTE, _OPES_ROUTE, _BIAS_OPES_ROUTE,
-                     _OPES_TABLE_ROUTE, _BIAS_OPES_TABLE_ROUTE)
+                     _OPES_TABLE_ROUTE, _BIAS_OPES_TABLE_ROUTE, _PBMETAD_ROUTE)
 _ONE_LAUNCH_FEATURES_ROUTE = (None, None, None, _RESTRAINT_FEATURES_ROUTE, _HILLS_FEATURES_ROUTE, _GRID_FEATURES_ROUTE, _BIAS_FEATURES_ROUTE,
-                              _OPES_FEATURES_ROUTE, _BIAS_OPES_FEATURES_ROUTE, _OPES_TABLE_FEATURES_ROUTE, _BIAS_OPES_TABLE_FEATURES_ROUTE)
+                              _OPES_FEATURES_ROUTE, _BIAS_OPES_FEATURES_ROUTE, _OPES_TABLE_FEATURES_ROUTE, _BIAS_OPES_TABLE_FEATURES_ROUTE,
+                              _PBMETAD_FEATURES_ROUTE)
 _ONE_LAUNCH_PAIR = ("(y, dx)", "(y, jac)", "(y, M)", "(y, energy, dx)", "(y, bias, dx)", "(y, bias, dx)", "(y, energies, dx)", "(y, bias, dx)",
-                    "(y, energies, dx)", "(y, bias, dx)", "(y, energies, dx)")   # what `into` holds
+                    "(y, energies, dx)", "(y, bias, dx)", "(y, energies, dx)", "(y, energies, dx)")   # what `into` holds
 # the dispatcher operator, in MolANN._fast_state
 _ONE_LAUNCH_OP = ("op_vjp", "op_jacobian", "op_metric", "op_restraint", "op_hills", "op_grid", "op_bias", "op_opes", "op_bias_opes", "op_opes_table",
-                  "op_bias_opes_table")
+                  "op_bias_opes_table", "op_pbmetad")
 _BIAS_KINDS = (_RESTRAINT, _HILLS, _GRID)      # the calls that return (y, a scalar per frame, dx)
 
 
@@ -988,7 +995,7 @@ def _check_into(name, x, into, dtype, out_dim, second_shape, pair):
     return y, second
 
 
-def _check_into_triple(name, x, into, out_dim, kind=_RESTRAINT):
+def _check_into_triple(name, x, into, out_dim, kind=_RESTRAINT, width=None):
     """`into` of value_and_restraint, value_and_hills and value_and_grid, before any launch, with `_check_into`'s checks: a triple of contiguous float64 tensors on x's
     device that hold [N, out_dim], [N] ([N, 3] for value_and_bias, [N, 4] with an OPES term) and x's elements.  Returns the triple, (None, None, None) for None."""
     if into is None:
@@ -998,7 +1005,7 @@ def _check_into_triple(name, x, into, out_dim, kind=_RESTRAINT):
     if any(t.dtype != torch.float64 for t in into):
         raise TypeError("%s: `into` must be float64 like x; got %s" % (name, ", ".join(str(t.dtype) for t in into)))
     n = x.shape[0]
-    per = 3 if kind == _BIAS else 4 if kind in (_BIAS_OPES, _BIAS_OPES_TABLE) else 1
+    per = 3 if kind == _BIAS else 4 if kind in (_BIAS_OPES, _BIAS_OPES_TABLE) else width if kind == _PBMETAD else 1
     counts = (n * out_dim, n * per, x.numel())
     if not all(t.is_contiguous() and t.numel() == c and t.device == x.device for t, c in zip(into, counts)):
         raise ValueError("%s: `into` must be contiguous {[%d, %d], %s, %s} on %s"
@@ -1302,6 +1309,45 @@ def _check_bias_opes_table_args(name, x, out_dim, restraint, grid, opes, into, o
     return (r, g, o) + _check_into_triple(name, x, into, out_dim, _BIAS_OPES_TABLE)
 
 
+def _check_pbmetad_args(name, x, out_dim, tables, kT, restraint, into, owner=None):
+    """The checks of value_and_pbmetad after the gate, all before any launch on x's device and with nothing read back: the record (whose
+    construction has checked its shapes and its `columns`) against the model and x's device, kT, the restraint by the check of its
+    single call, then `into` with energies [N, 2 + K].  Returns ((center, kappa, period, flat) or None, (columns, table, shape, lower,
+    spacing, periodic, kT), y, energies, dx)."""
+    if not isinstance(tables, _bias.PBTables):
+        raise TypeError("%s: `tables` must be a molann_amd.bias.PBTables; got %s" % (name, type(tables).__name__))
+    if restraint is not None and not isinstance(restraint, _bias.Restraint):
+        raise TypeError("%s: `restraint` must be None or a molann_amd.bias.Restraint; got %s" % (name, type(restraint).__name__))
+    if isinstance(kT, bool) or not isinstance(kT, (int, float)):
+        raise TypeError("%s: `kT` must be a Python float; got %s" % (name, type(kT).__name__))
+    kT = float(kT)
+    if not (kT > 0.0 and math.isfinite(kT)):
+        raise ValueError("%s: `kT` must be finite and > 0; got %r" % (name, kT))
+    K = len(tables.shape)
+    cols = tables.columns
+    if cols is None:
+        if K > out_dim:
+            raise IndexError("%s: `tables` has %d axes but the model has %d outputs" % (name, K, out_dim))
+        cols = tuple(range(K))
+    elif len(cols) != K:      # a record changed through `_replace`
+        raise ValueError("%s: `tables.columns` must name one output per table (%d); got %d" % (name, K, len(cols)))
+    elif any(c >= out_dim for c in cols):
+        raise IndexError("%s: `tables.columns` must lie in [0, %d); got %s" % (name, out_dim, list(cols)))
+    table = tables.table
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float64:
+        raise TypeError("%s: `tables.table` must be a float64 tensor" % name)
+    if table.device != x.device:
+        raise ValueError("%s: `tables.table` must be on %s; got %s" % (name, x.device, table.device))
+    if table.dim() != 1 or table.numel() != sum(tables.shape) or not table.is_contiguous():
+        raise ValueError("%s: `tables.table` must be contiguous [sum(shape) = %d]; got %s" % (name, sum(tables.shape), list(table.shape)))
+    periodic = [False] * K if tables.periodic is None else [bool(p) for p in tables.periodic]
+    r = None
+    if restraint is not None:
+        r = _check_restraint_args(name, x, out_dim, restraint.center, restraint.kappa, restraint.period, restraint.flat, None, owner=owner)[:4]
+    t = (cols, table.detach(), [int(n) for n in tables.shape], [float(v) for v in tables.lower], [float(v) for v in tables.spacing], periodic, kT)
+    return (r, t) + _check_into_triple(name, x, into, out_dim, _PBMETAD, width=2 + K)
+
+
 def _check_grad_out(name, x, out_dim, grad_out):
     if not isinstance(grad_out, torch.Tensor) or grad_out.numel() != x.shape[0] * out_dim or grad_out.device != x.device:
         raise ValueError("%s: grad_out must hold [%d, %d] values on %s" % (name, x.shape[0], out_dim, x.device))
@@ -1365,6 +1411,9 @@ def _one_launch_arguments(kind, x, extra, into, n_inp, out_dim, lins, al, owner=
     elif kind == _BIAS_OPES_TABLE:
         checked = _check_bias_opes_table_args(name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:3], checked[3], (checked[4], checked[5]) if checked[3] is not None else None, (n, n_inp, 3)
+    elif kind == _PBMETAD:
+        checked = _check_pbmetad_args(name, x, out_dim, *extra, into, owner=owner)
+        return x, checked[:2], checked[2], (checked[3], checked[4]) if checked[2] is not None else None, (n, n_inp, 3)
     elif kind == _OPES:
         checked = _check_opes_args(name, x, out_dim, *extra, into, owner=owner)
         return x, checked[:8], checked[8], (checked[9], checked[10]) if checked[8] is not None else None, (n, n_inp, 3)
@@ -1399,6 +1448,9 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
         elif kind == _BIAS_OPES_TABLE:
             if not plan.supports_value_and_bias_opes_table_f64():
                 raise NotImplementedError("value_and_bias: one frame's rows exceed the LDS of a compute unit for this model; " + _BIAS_OPES_TABLE_ROUTE)
+        elif kind == _PBMETAD:
+            if not plan.supports_value_and_pbmetad_f64():
+                raise NotImplementedError("value_and_pbmetad: one frame's rows exceed the LDS of a compute unit for this model; " + _PBMETAD_ROUTE)
         elif kind in _BIAS_KINDS or kind == _BIAS:
             if not (plan.supports_value_and_restraint_f64, plan.supports_value_and_hills_f64, plan.supports_value_and_grid_f64,
                     plan.supports_value_and_bias_f64)[kind - _RESTRAINT]():
@@ -1420,6 +1472,13 @@ def _one_launch_ctypes(kind, entry, x, extra, y, second, shape, out_dim, lins, a
                 second = (torch.empty((x.shape[0],), dtype=torch.float64, device=x.device), second)
             if kind == _BIAS or kind == _BIAS_OPES or kind == _BIAS_OPES_TABLE:
                 second = (torch.empty((x.shape[0], 3 if kind == _BIAS else 4), dtype=torch.float64, device=x.device), second)
+            if kind == _PBMETAD:
+                second = (torch.empty((x.shape[0], 2 + len(extra[1][0])), dtype=torch.float64, device=x.device), second)
+        if kind == _PBMETAD:
+            if x.shape[0] > 0:
+                plan.value_and_pbmetad_f64(x, [lin.weight.detach().contiguous() for lin in lins], [lin.bias.detach().contiguous() for lin in lins],
+                                           y, *second, extra[1], restraint=extra[0])
+            return (y,) + tuple(second)
         if kind == _BIAS_OPES_TABLE:
             if x.shape[0] > 0:
                 plan.value_and_bias_opes_table_f64(x, [lin.weight.detach().contiguous() for lin in lins],
@@ -1589,6 +1648,14 @@ class PreprocessingANN(_PlanOwner, torch.nn.Module):
         in device memory, so nothing is read back.  The arguments as `MolANN.value_and_opes_table` takes them; ``table.d`` features."""
         return self._bias_on_features(_OPES_TABLE, x, (table, scale, epsilon), into)
 
+    def value_and_pbmetad(self, x, tables, kT, restraint=None, into=None):
+        """``(feat, energies, dx)``: `MolANN.value_and_pbmetad` on the features themselves, float64, in ONE kernel launch
+        (`molann_value_and_pbmetad_f64`, frames_value_pbmetad_f64_kernel, on this module's float64 feature plan; no head): a
+        parallel-bias metadynamics bias on up to 8 chosen features, one 1-D table each.  Raw dihedral angles: ``use_angle_value=True``,
+        ``lower = -pi``, ``spacing = 2 pi / n`` and ``periodic = True`` per axis.  The arguments as `MolANN.value_and_pbmetad` takes
+        them.  No autograd graph is recorded; ``into=(feat, energies, dx)`` reuses the caller's buffers.  The same bits on every call."""
+        return self._bias_on_features(_PBMETAD, x, (tables, kT, restraint), into)
+
     def _bias_on_features(self, kind, x, extra, into):
         """value_and_restraint / value_and_hills / value_and_grid / value_and_bias / value_and_opes / value_and_opes_table of this module: the gate, the checks and the ctypes plan of the features."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and self._fusable()):
@@ -1737,6 +1804,9 @@ class MolANN(_PlanOwner, torch.nn.Module):
             r, h, g = extra
             return tuple(op(x, st["handle"], ref, W, B, *(r or (None,) * 4), *((list(h[0]),) + h[1:] if h else ([], None, None, None, None)),
                             *((list(g[0]),) + g[1:] if g else ([], None, [], [], [])), into))
+        if kind == _PBMETAD:
+            r, t = extra
+            return tuple(op(x, st["handle"], ref, W, B, *(r or (None,) * 4), list(t[0]), *t[1:], into))
         if kind == _BIAS_OPES or kind == _BIAS_OPES_TABLE:   # the same places in both operators: the record's fields follow its columns
             r, g, o = extra
             return tuple(op(x, st["handle"], ref, W, B, *(r or (None,) * 4), list(o[0]), *o[1:],
@@ -1938,6 +2008,25 @@ class MolANN(_PlanOwner, torch.nn.Module):
             return self._one_launch_f64(kind, self._one_launch_state(x, kind, "float64"), x, (restraint, grid, opes), into)
         return self._one_launch_f64(_BIAS, self._one_launch_state(x, _BIAS, "float64"), x, (restraint, hills, grid), into)
 
+    def value_and_pbmetad(self, x, tables, kT, restraint=None, into=None):
+        """``(y, energies, dx)`` with ``y = self(x)`` [N, d_out], a PARALLEL-BIAS METADYNAMICS bias on K <= 8 chosen outputs (Pfaendtner
+        and Bonomi, JCTC 2015; PLUMED's ``PBMETAD``) and ``dx`` [N, n_inp, 3] the gradient of its sum with the walls, float64, in ONE
+        kernel launch (`molann_value_and_pbmetad_f64`, frames_value_pbmetad_f64_kernel).  ``tables``: a `molann_amd.bias.PBTables`
+        ``(table, shape, lower, spacing, periodic=None, columns=None)`` - K one-dimensional tables back to back in one float64 tensor
+        on x's device, table k on output ``columns[k]`` (None: the first K).  ``energies`` [N, 2 + K] ``= (E_r, V_PB, V_0 .. V_{K-1})``:
+        ``V_k`` is table k's cubic-convolution interpolant (`value_and_grid`'s on one axis: periodic or held at the edge's value outside
+        its range), ``V_PB = m - kT log sum_k exp(-(V_k - m) / kT)`` with ``m = min_k V_k`` - the soft minimum
+        ``-kT log sum_k exp(-V_k / kT)`` - and ``dx = J^T (dE_r/dy + w_k V_k')`` with ``w_k`` the axes' shares of that sum.  Memory and
+        cost grow linearly in K, where a table over K outputs has n^K entries and `value_and_grid` serves 3.  ``kT``: a Python float
+        > 0.  ``restraint``: None or a `molann_amd.bias.Restraint` on all outputs (walls), ``E_r`` exactly 0 without one.  With K = 1
+        ``V_PB`` and ``dx`` are the single table's, bit for bit.  ``y`` is `value_and_vjp`'s, bit for bit.  A frame whose ``V_k`` is not
+        finite gets NaN and no other frame does.  Every sum has a fixed order: the same bits on every call, whatever N.  Nothing is read
+        back, so the call queues behind a deposit and is captured in a ``torch.cuda.graph`` while the tables grow
+        (`molann_amd.bias.PBMetadRun` is that loop).  No autograd graph is recorded; ``into=(y, energies, dx)`` reuses the caller's
+        buffers.  `model.double()` and a float64 x on a HIP device; a model served by one fused plan.  Out of scope: float32, c(t),
+        per-axis kT, gradients with respect to the tables."""
+        return self._one_launch_f64(_PBMETAD, self._one_launch_state(x, _PBMETAD, "float64"), x, (tables, kT, restraint), into)
+
     def _tangent_present(self, x):
         if _has_tangent(x):
             return True
@@ -1996,6 +2085,7 @@ class MolANN(_PlanOwner, torch.nn.Module):
                 st["op_grid"], st["op_bias"] = torch.ops.molann.value_and_grid_h, torch.ops.molann.value_and_bias_h
                 st["op_opes"], st["op_bias_opes"] = torch.ops.molann.value_and_opes_h, torch.ops.molann.value_and_bias_opes_h
                 st["op_opes_table"], st["op_bias_opes_table"] = torch.ops.molann.value_and_opes_table_h, torch.ops.molann.value_and_bias_opes_table_h
+                st["op_pbmetad"] = torch.ops.molann.value_and_pbmetad_h
                 from . import script
                 st["desc"] = script.make_desc(script.KIND_FORWARD, fl.input_atom_num,
                                               align_idx=al._local_align_atom_indices if al is not None else None,

@@ -34,7 +34,7 @@ import operator
 import torch
 
 __all__ = ["grid_points", "add_hills_to_grid", "opes_kernel_sum", "Restraint", "Hills", "Grid", "Opes", "OpesTable", "OpesFromTable", "OpesRun",
-           "MetadRun", "CovHills", "add_cov_hills_to_grid"]
+           "MetadRun", "CovHills", "add_cov_hills_to_grid", "PBTables", "PBMetadRun"]
 
 HILLS_MAX_COLUMNS = 8     # HILLS_MAX_D of csrc/molann_math.h
 GRID_MAX_COLUMNS = 3      # GRID_MAX_D of csrc/molann_math.h
@@ -111,6 +111,56 @@ class Opes(collections.namedtuple("Opes", "centers heights sigma scale norm epsi
         columns = _columns("Opes", columns, HILLS_MAX_COLUMNS, "form the kernel sum on `model(x)[:, columns]` with `opes_kernel_sum`, its "
                            "logarithm and its derivative with torch, scatter it into a cotangent, then `value_and_vjp`")
         return super().__new__(cls, centers, heights, sigma, scale, norm, epsilon, cutoff, period, columns)
+
+
+class PBTables(collections.namedtuple("PBTables", "table shape lower spacing periodic columns")):
+    """The K one-dimensional tables of a parallel-bias metadynamics bias (`MolANN.value_and_pbmetad`) on the outputs ``columns`` (distinct
+    indices in any order, at most 8; None: the first K): ``table`` a float64 tensor of ``sum(shape)`` values, table k - ``shape[k]`` >= 4
+    points at ``lower[k] + i spacing[k]``, periodic with period ``shape[k] spacing[k]`` where ``periodic[k]`` - starting at
+    ``sum(shape[:k])``.  Immutable; the table is held, not copied, and read at launch as it is."""
+    __slots__ = ()
+
+    def __new__(cls, table, shape, lower, spacing, periodic=None, columns=None):
+        columns = _columns("PBTables", columns, HILLS_MAX_COLUMNS, "a parallel bias has at most 8 axes")
+        if isinstance(shape, torch.Tensor):
+            shape = shape.tolist()
+        try:
+            shape = tuple(operator.index(n) for n in shape)
+        except TypeError:
+            raise TypeError("PBTables: `shape` must be a sequence of integers, one per table; got %s" % type(shape).__name__)
+        K = len(shape)
+        if not 1 <= K <= HILLS_MAX_COLUMNS:
+            raise (ValueError if K < 1 else NotImplementedError)("PBTables: 1 to %d tables are served; got %d" % (HILLS_MAX_COLUMNS, K))
+        if min(shape) < 4 or sum(shape) >= 2 ** 31:
+            raise ValueError("PBTables: every table needs at least 4 points and all of them fewer than 2^31; got %s" % list(shape))
+        rows = []
+        for what, v in (("lower", lower), ("spacing", spacing)):
+            try:
+                v = tuple(float(c) for c in (v.tolist() if isinstance(v, torch.Tensor) else v))
+            except (TypeError, ValueError):
+                raise TypeError("PBTables: `%s` must be a sequence of %d numbers; got %s" % (what, K, type(v).__name__))
+            if len(v) != K:
+                raise ValueError("PBTables: `%s` must have one entry per table (%d); got %d" % (what, K, len(v)))
+            if not all(math.isfinite(c) and (c > 0.0 or what == "lower") for c in v):
+                raise ValueError("PBTables: `%s` must be finite%s everywhere; got %s" % (what, "" if what == "lower" else " and > 0", list(v)))
+            rows.append(v)
+        if periodic is not None:
+            periodic = tuple(bool(p) for p in periodic)
+            if len(periodic) != K:
+                raise ValueError("PBTables: `periodic` must be None or one bool per table (%d); got %d" % (K, len(periodic)))
+        if columns is not None and len(columns) != K:
+            raise ValueError("PBTables: `columns` must name one output per table (%d); got %d" % (K, len(columns)))
+        if not isinstance(table, torch.Tensor):
+            raise TypeError("PBTables: `table` must be a tensor; got %s" % type(table).__name__)
+        if table.dtype != torch.float64:
+            raise TypeError("PBTables: `table` must be float64; got %s" % table.dtype)
+        if table.dim() != 1 or table.numel() != sum(shape) or not table.is_contiguous():
+            raise ValueError("PBTables: `table` must be contiguous [sum(shape) = %d]; got %s" % (sum(shape), list(table.shape)))
+        return super().__new__(cls, table, shape, rows[0], rows[1], periodic, columns)
+
+    def views(self):
+        """The K tables as views of ``table``, nothing copied."""
+        return tuple(self.table[sum(self.shape[:k]):sum(self.shape[:k + 1])] for k in range(len(self.shape)))
 
 
 def grid_points(shape, lower, spacing, device=None):
@@ -712,7 +762,8 @@ class MetadRun(object):
     `add_cov_hills_to_grid`) was 5.7-15.9x slower than either on every shape measured - none was slower than it.
 
     Out of scope: a frame kernel that fuses `value_and_grid` with the metric; heights renormalised by the determinant; a running
-    acceleration factor; a TorchScript operator for the adaptive step; walkers on several ranks; float32; tables of more than 3 axes."""
+    acceleration factor; a TorchScript operator for the adaptive step; walkers on several ranks; float32; tables of more than 3 axes
+    (`PBMetadRun` biases up to 8 outputs with one 1-D table each, joined by a soft minimum)."""
 
     adaptive = None     # the fixed widths, unless the constructor is told otherwise
 
@@ -1023,3 +1074,174 @@ class MetadRun(object):
         adapt = self.adapt.cpu()
         return dict(observations=int(observations), emits=int(emits), skipped=int(skipped), n=adapt[:, 0].clone(), mean=adapt[:, 1:1 + d].clone(),
                     cov=adapt[:, 1 + d:].clone(), last=self.cov.cpu())
+
+
+class PBMetadRun(object):
+    """A whole parallel-bias metadynamics run (Pfaendtner and Bonomi, JCTC 2015; PLUMED's ``PBMETAD`` with grids and a fixed ``SIGMA``)
+    on the device, on up to 8 outputs: K one-dimensional tables, one per biased output, joined by a soft minimum, so that memory and the
+    cost of a step grow linearly in K where a table over K outputs (`MetadRun`) has n^K entries and at most 3 axes.  Two launches per
+    step and nothing read back, so the loop queues ahead of the device and can be captured in one ``torch.cuda.graph``.
+
+    ``bias(x)`` is `MolANN.value_and_pbmetad` on the tables as they are: ``(y, energies, dx)`` with ``energies`` [N, 2 + K] =
+    ``(E_walls, V_PB, V_0 .. V_{K-1})``, ``V_k`` table k's cubic-convolution interpolant at output ``columns[k]``,
+    ``V_PB = -kT log sum_k exp(-V_k / kT)`` formed from the minimum, and ``dx`` the gradient of ``E_walls + V_PB``.  ``deposit(y,
+    energies)`` is `molann_pbmetad_deposit_f64` on what that call wrote (columns 2.. are read in place): walker a adds ``h_ak
+    exp(-1/2 ((g - y_ak) / sigma_k)^2)`` to every entry of table k within ``cutoff`` widths (None: everywhere), ``h_ak = height
+    exp(-V_ak / (kT (biasfactor - 1))) w_ak`` with ``w_ak = exp(-V_ak / kT) / sum_j exp(-V_aj / kT)``, in walker order and with no
+    atomics: the same bits on every run.  ``state`` [8] holds ``(hills, refused, sum_heights, steps, logged, 0, 0, 0)`` with
+    ``sum_heights`` over walkers and axes; with ``log_capacity`` > 0 the first that many walkers are kept in ``log`` [log_capacity,
+    2 K] as rows ``(centre_0.., h_0..)``: `hills`.
+
+    ``model``: a `MolANN` (or `PreprocessingANN`) in float64; ``shape``: K point counts >= 4; ``lower``, ``spacing``, ``sigma``: one
+    float per axis; ``periodic``: one bool per axis or None; ``kT`` > 0; ``biasfactor`` > 1 (+inf: every height is ``height w_ak``);
+    ``height`` > 0; ``cutoff``: None or > 0, in widths; ``columns``: None (the first K outputs) or the K outputs the axes bias;
+    ``walls``: a `Restraint` on all outputs or None; ``table``: None (zeros on the model's device) or a contiguous float64 tensor of
+    ``sum(shape)`` values on a CUDA / HIP device, held, not copied, and updated in place.  Everything is checked here, once.  A walker
+    with a bias, an output or a height that is not finite is counted in ``refused`` and changes no table; a height that underflows to
+    exactly 0 adds nothing to its axis and the walker still counts.
+
+    Out of scope: c(t) and ``rbias``; adaptive widths; per-axis heights or bias factors; partitioned families; walkers on several
+    ranks; float32; a TorchScript operator for the deposit."""
+
+    def __init__(self, model, shape, lower, spacing, kT, biasfactor, height, sigma, periodic=None, cutoff=None, columns=None, walls=None,
+                 log_capacity=0, table=None):
+        from . import _capi
+        if not callable(getattr(model, "value_and_pbmetad", None)):
+            raise TypeError("PBMetadRun: `model` must be a MolANN or a PreprocessingANN (it has no `value_and_pbmetad`); got %s" % type(model).__name__)
+        if isinstance(shape, torch.Tensor):
+            shape = shape.tolist()
+        try:
+            shape = tuple(operator.index(n) for n in shape)
+        except TypeError:
+            raise TypeError("PBMetadRun: `shape` must be a sequence of integers, one per axis; got %s" % type(shape).__name__)
+        K = len(shape)
+        if K < 1:
+            raise ValueError("PBMetadRun: `shape` must name at least one axis")
+        if K > HILLS_MAX_COLUMNS:
+            raise NotImplementedError("PBMetadRun: a parallel bias has at most %d axes; got %d" % (HILLS_MAX_COLUMNS, K))
+        if min(shape) < 4 or sum(shape) >= 2 ** 31:
+            raise ValueError("PBMetadRun: every axis needs at least 4 points and all of them fewer than 2^31; got %s" % list(shape))
+        kT = _positive("PBMetadRun", "kT", kT)
+        biasfactor = _positive("PBMetadRun", "biasfactor", biasfactor, allow_inf=True)
+        height = _positive("PBMetadRun", "height", height)
+        if not biasfactor > 1.0:
+            raise ValueError("PBMetadRun: `biasfactor` must be > 1; got %r" % (biasfactor,))
+        if cutoff is not None:
+            cutoff = _positive("PBMetadRun", "cutoff", cutoff, allow_inf=True)
+            cutoff = None if cutoff == math.inf else cutoff
+        rows = []
+        for what, v in (("lower", lower), ("spacing", spacing), ("sigma", sigma)):
+            try:
+                v = [float(c) for c in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+            except (TypeError, ValueError):
+                raise TypeError("PBMetadRun: `%s` must be a sequence of %d numbers; got %s" % (what, K, type(v).__name__))
+            if len(v) != K:
+                raise ValueError("PBMetadRun: `%s` must have one entry per axis (%d); got %d" % (what, K, len(v)))
+            if not all(math.isfinite(c) and (c > 0.0 or what == "lower") for c in v):
+                raise ValueError("PBMetadRun: `%s` must be finite%s everywhere; got %s" % (what, "" if what == "lower" else " and > 0", v))
+            rows.append(v)
+        if periodic is not None:
+            periodic = [bool(p) for p in periodic]
+            if len(periodic) != K:
+                raise ValueError("PBMetadRun: `periodic` must be None or one bool per axis (%d); got %d" % (K, len(periodic)))
+        columns = _columns("PBMetadRun", columns, HILLS_MAX_COLUMNS, "a parallel bias has at most 8 axes")
+        if columns is not None and len(columns) != K:
+            raise ValueError("PBMetadRun: `columns` must name one output per axis (%d); got %d" % (K, len(columns)))
+        if walls is not None and not isinstance(walls, Restraint):
+            raise TypeError("PBMetadRun: `walls` must be a Restraint or None; got %s" % type(walls).__name__)
+        if isinstance(log_capacity, bool):
+            raise TypeError("PBMetadRun: `log_capacity` must be an integer")
+        log_capacity = operator.index(log_capacity)
+        if log_capacity < 0:
+            raise ValueError("PBMetadRun: `log_capacity` must be >= 0; got %d" % log_capacity)
+        if table is None:
+            device = next((t.device for t in list(model.parameters()) + list(model.buffers())), torch.device("cpu"))
+            if device.type != "cuda":
+                raise ValueError("PBMetadRun: the tables live in device memory and their kernels are HIP kernels; the model is on %s" % device)
+            table = torch.zeros(sum(shape), dtype=torch.float64, device=device)
+        else:
+            if not isinstance(table, torch.Tensor):
+                raise TypeError("PBMetadRun: `table` must be None or a tensor; got %s" % type(table).__name__)
+            if table.dtype != torch.float64:
+                raise TypeError("PBMetadRun: `table` must be float64; got %s" % table.dtype)
+            if table.dim() != 1 or table.numel() != sum(shape):
+                raise ValueError("PBMetadRun: `table` must be [sum(shape) = %d]; got %s" % (sum(shape), list(table.shape)))
+            if not table.is_contiguous() or table.requires_grad:
+                raise ValueError("PBMetadRun: `table` is updated in place: it must be contiguous and must not require grad")
+            if table.device.type != "cuda":
+                raise ValueError("PBMetadRun: the tables live in device memory and their kernels are HIP kernels; got device %s" % table.device)
+        self.model, self.table, self.walls = model, table.detach(), walls
+        self.shape, self.lower, self.spacing, self.sigma, self.periodic, self.columns = shape, rows[0], rows[1], rows[2], periodic, columns
+        self.kT, self.biasfactor, self.height, self.cutoff = kT, biasfactor, height, cutoff
+        self.inv_dT = 0.0 if biasfactor == math.inf else 1.0 / (kT * (biasfactor - 1.0))
+        self.state = torch.zeros(8, dtype=torch.float64, device=table.device)
+        self.log = torch.zeros(log_capacity, 2 * K, dtype=torch.float64, device=table.device) if log_capacity else None
+        self._records = PBTables(self.table, shape, self.lower, self.spacing, periodic, columns)
+        self._arrays = _capi.metad_grid_arrays(shape, self.lower, self.spacing, self.periodic, self.sigma, self.columns)
+
+    @property
+    def tables(self):
+        """The K tables as views of ``table``, nothing copied."""
+        return self._records.views()
+
+    def records(self):
+        """The `PBTables` of the run, as `MolANN.value_and_pbmetad` takes it."""
+        return self._records
+
+    def bias(self, x, into=None):
+        """The walkers ``x`` under the tables as they are now, one launch: ``(y, energies, dx)`` of `MolANN.value_and_pbmetad`."""
+        return self.model.value_and_pbmetad(x, self._records, self.kT, restraint=self.walls, into=into)
+
+    def deposit(self, y, energies):
+        """The step after `bias`: ``y`` [W, n_out] and ``energies`` [W, 2 + K] as that call returned them (read only; columns 2.. are
+        read in place).  One launch on the current stream, nothing read back, returns None."""
+        from . import _capi
+        K = len(self.shape)
+        widest = K - 1 if self.columns is None else max(self.columns)
+        for what, t in (("y", y), ("energies", energies)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("PBMetadRun.deposit: `%s` must be a tensor on %s; got %s" % (what, self.table.device, type(t).__name__))
+            if t.dtype != torch.float64:
+                raise TypeError("PBMetadRun.deposit: `%s` must be float64; got %s" % (what, t.dtype))
+            if t.device != self.table.device:
+                raise ValueError("PBMetadRun.deposit: `%s` must be on %s; got %s" % (what, self.table.device, t.device))
+        if y.dim() != 2 or y.shape[1] <= widest:
+            raise ValueError("PBMetadRun.deposit: `y` must be [W, more than %d columns]; got %s" % (widest, list(y.shape)))
+        n_walkers = y.shape[0]
+        if tuple(energies.shape) != (n_walkers, 2 + K) or energies.stride(1) != 1:
+            raise ValueError("PBMetadRun.deposit: `energies` must be the [W, %d] of `bias` with unit stride along a row; got %s"
+                             % (2 + K, list(energies.shape)))
+        if n_walkers == 0:
+            return None
+        y = y.detach()
+        y = y if y.stride(1) == 1 else y.contiguous()
+        with torch.cuda.device(self.table.device):
+            _capi.pbmetad_deposit_f64(self.table, self._arrays, y, energies.detach()[:, 2:], self.height, self.inv_dT, self.kT, self.cutoff,
+                                      self.state, self.log)
+        return None
+
+    def read_state(self):
+        """``state`` as a dict of Python numbers (``hills``, ``refused``, ``sum_heights``, ``steps``, ``logged``): the one 64-byte
+        read-back (it waits for the steps queued before it)."""
+        hills, refused, sum_heights, steps, logged = self.state.tolist()[:5]
+        return dict(hills=int(hills), refused=int(refused), sum_heights=sum_heights, steps=int(steps), logged=int(logged))
+
+    def hills(self, k, n=None):
+        """The logged hills of axis ``k`` as a `Hills` record on one column - views of ``log[:n]``, nothing copied - for
+        `add_hills_to_grid(run.tables[k], [lower[k]], [spacing[k]], [periodic[k]], h.centers, h.heights, h.sigma)`, the restart route.
+        ``n``: the logged count where the caller has it; None reads the state."""
+        K = len(self.shape)
+        if self.log is None:
+            raise ValueError("PBMetadRun.hills: the run keeps no log (`log_capacity` is 0)")
+        if isinstance(k, bool):
+            raise TypeError("PBMetadRun.hills: `k` must be an integer")
+        k = operator.index(k)
+        if not 0 <= k < K:
+            raise IndexError("PBMetadRun.hills: `k` must be 0..%d; got %d" % (K - 1, k))
+        n = self.read_state()["logged"] if n is None else operator.index(n)
+        if not 0 <= n <= self.log.shape[0]:
+            raise ValueError("PBMetadRun.hills: `n` must be 0..%d; got %d" % (self.log.shape[0], n))
+        period = None
+        if self.periodic is not None and self.periodic[k]:
+            period = torch.tensor([self.shape[k] * self.spacing[k]], dtype=torch.float64, device=self.table.device)
+        return Hills(self.log[:n, k:k + 1], self.log[:n, K + k], [self.sigma[k]], period, (k if self.columns is None else self.columns[k],))

@@ -292,6 +292,9 @@ __device__ __forceinline__ void frame_value_term_loop_f64(const double* __restri
     double* cot = (double*)smem + (size_t)slot * a.lds_per_frame;
     double* feat = cot + a.d_out;
     double* zrows = feat + a.d_feat;
+    // row0 and row1 are the LAST 2 max_w doubles of a frame's rows, whatever lds_per_frame counts: a kernel whose rows hold more than this
+    // loop uses (frames_value_pbmetad_f64_kernel on bias64_rows: BIAS_SEL more) finds its own words just below them, at
+    // cot + lds_per_frame - 2 max_w - extra, above the hidden layers' rows.  Moving the two rows breaks that kernel.
     double* row0 = zrows + (a.lds_per_frame - a.d_out - a.d_feat - 2 * a.max_w);
     double* row1 = row0 + a.max_w;
     for (long f = (long)blockIdx.x * per_block + slot; f < a.n_frames; f += (long)gridDim.x * per_block) {

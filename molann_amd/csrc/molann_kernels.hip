@@ -49,6 +49,7 @@
 #include "molann_opes_modes.h"
 #include "molann_metad_rct.h"
 #include "molann_metad_cov.h"
+#include "molann_pbmetad.h"
 #include "jit_sources.gen.h"
 
 using namespace molann;
@@ -78,6 +79,8 @@ using namespace molann;
 #include "molann_dev_metad_deposit_f64.inc"
 #include "molann_dev_metad_rct_f64.inc"
 #include "molann_dev_metad_cov_f64.inc"
+#include "molann_dev_pbmetad_f64.inc"
+#include "molann_dev_pbmetad_deposit_f64.inc"
 // Host code (what `make san` instruments: -fno-gpu-sanitize leaves the device code alone):
 #include "molann_host_plan.inc"
 #include "molann_host_jit.inc"
@@ -91,3 +94,4 @@ using namespace molann;
 #include "molann_metad_deposit_f64.inc"
 #include "molann_metad_rct_f64.inc"
 #include "molann_metad_cov_f64.inc"
+#include "molann_pbmetad_deposit_f64.inc"

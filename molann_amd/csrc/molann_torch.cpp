@@ -1496,6 +1496,106 @@ std::vector<at::Tensor> value_and_bias_opes_table_h_hip(const at::Tensor& x_in, 
     return value_and_bias_opes_table_impl(x_in, *desc_of(handle, "molann::value_and_bias_opes_table_h"), MOLANN_BIAS_OPES_TABLE_OP_ARGS);
 }
 
+// {out, energies, grad_x}: values, a parallel-bias metadynamics bias on the outputs `columns` and an optional restraint on all outputs
+// (molann_value_and_pbmetad_f64): `table` holds the K one-dimensional tables back to back, contiguous float64 on x's device and read
+// where it is (no copy: a later deposit writes it); shape, lower, spacing, periodic and kT are host values.  energies [N, 2 + K] =
+// (E_r, V_PB, V_0 ..).  `into`: none or {out, energies, grad_x}.
+std::vector<at::Tensor> value_and_pbmetad_impl(const at::Tensor& x_in, const std::vector<int64_t>& desc, const at::Tensor& ref_x,
+                                               const std::vector<at::Tensor>& weights, const std::vector<at::Tensor>& biases,
+                                               const c10::optional<at::Tensor>& center_in, const c10::optional<at::Tensor>& kappa_in,
+                                               const c10::optional<at::Tensor>& rperiod_in, const c10::optional<at::Tensor>& flat_in,
+                                               const std::vector<int64_t>& columns, const at::Tensor& table_in, const std::vector<int64_t>& shape,
+                                               const std::vector<double>& lower, const std::vector<double>& spacing, const c10::List<bool>& periodic_in,
+                                               double kT, const std::vector<at::Tensor>& into) {
+    const char* const op = "molann::value_and_pbmetad";
+    check_x(x_in, desc);
+    TORCH_CHECK_TYPE(x_in.scalar_type() == at::kDouble, "molann::value_and_pbmetad is float64: call model.double() and pass a float64 x (got ",
+                     x_in.scalar_type(), ")");
+    TORCH_CHECK(desc[1] == KIND_FORWARD || desc[1] == KIND_FEATURES, "molann::value_and_pbmetad: a forward or a features description");
+    TORCH_CHECK_VALUE(std::isfinite(kT) && kT > 0.0, "molann::value_and_pbmetad: `kT` must be finite and > 0; got ", kT);
+    const at::Tensor x = x_in.contiguous();
+    const c10::DeviceGuard guard(x.device());
+    auto e = entry_for(desc, x, ref_x);
+    const int64_t n = x.size(0);
+    const int64_t cols = e->kind == KIND_FORWARD ? e->out_dim : e->feature_dim;
+    const bool has_r = kappa_in.has_value() && kappa_in->defined();
+    TORCH_CHECK_VALUE(!columns.empty(), "molann::value_and_pbmetad: `columns` must name at least one output");
+    const std::vector<int32_t> pc = bias_columns("columns", columns, 8, cols);
+    const int64_t K = (int64_t)pc.size();
+    molann_pbmetad_terms_f64 t;
+    memset(&t, 0, sizeof(t));
+    at::Tensor center, kappa, rperiod, flat;
+    if (has_r) {
+        center = bias_tensor("center", center_in, x, true); kappa = bias_tensor("kappa", kappa_in, x, true);
+        rperiod = bias_tensor("restraint_period", rperiod_in, x, false); flat = bias_tensor("flat", flat_in, x, false);
+        const bool per_frame = center.dim() == 2 && center.size(0) == n && center.size(1) == cols;
+        TORCH_CHECK_VALUE(per_frame || (center.dim() == 1 && center.size(0) == cols), "molann::value_and_pbmetad: `center` must be [", cols,
+                          "] or [N, out_dim]");
+        TORCH_CHECK_VALUE(kappa.dim() == 1 && kappa.size(0) == cols && (!rperiod.defined() || (rperiod.dim() == 1 && rperiod.size(0) == cols)) &&
+                              (!flat.defined() || (flat.dim() == 1 && flat.size(0) == cols)),
+                          "molann::value_and_pbmetad: `kappa`, `restraint_period` and `flat` must be [", cols, "]");
+        t.center = center.data_ptr<double>(); t.center_stride = per_frame ? cols : 0; t.kappa = kappa.data_ptr<double>();
+        t.restraint_period = rperiod.defined() ? rperiod.data_ptr<double>() : nullptr;
+        t.flat = flat.defined() ? flat.data_ptr<double>() : nullptr;
+    }
+    TORCH_CHECK_VALUE((int64_t)shape.size() == K && (int64_t)lower.size() == K && (int64_t)spacing.size() == K &&
+                          (periodic_in.size() == 0 || (int64_t)periodic_in.size() == K),
+                      "molann::value_and_pbmetad: `shape`, `lower`, `spacing` and `periodic` must hold one value per column (", K, ")");
+    int32_t periodic[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t entries = 0;
+    for (int64_t k = 0; k < K; ++k) {
+        TORCH_CHECK_VALUE(shape[k] >= 4 && shape[k] < (int64_t(1) << 31), "molann::value_and_pbmetad: every table must have at least 4 points (got ",
+                          shape[k], ")");
+        TORCH_CHECK_VALUE(std::isfinite(spacing[k]) && spacing[k] > 0.0 && std::isfinite(lower[k]),
+                          "molann::value_and_pbmetad: `spacing` must be finite and > 0 and `lower` finite");
+        periodic[k] = periodic_in.size() > 0 && periodic_in.get(k) ? 1 : 0;
+        entries += shape[k];
+    }
+    TORCH_CHECK_VALUE(entries < (int64_t(1) << 31), "molann::value_and_pbmetad: the tables must hold fewer than 2^31 points");
+    // `written`: the table is read where it lives, so it must be contiguous as it is
+    const at::Tensor table = opes_tensor(op, "table", table_in, x, table_in.numel() == entries, "sum(shape) values", true);
+    t.n_columns = (int32_t)K; t.columns = pc.data(); t.table = table.data_ptr<double>();
+    t.shape = shape.data(); t.lower = lower.data(); t.spacing = spacing.data(); t.periodic = periodic; t.kT = kT;
+    TORCH_CHECK(into.empty() || into.size() == 3, "molann::value_and_pbmetad: `into` must be a triple of tensors (out, energies, grad_x)");
+    at::Tensor out, energies, gx;
+    if (into.empty()) {
+        out = at::empty({n, cols}, x.options()); energies = at::empty({n, 2 + K}, x.options()); gx = at::empty_like(x);
+    } else {
+        out = into[0]; energies = into[1]; gx = into[2];
+        const int64_t counts[3] = {n * cols, (2 + K) * n, x.numel()};
+        for (int i = 0; i < 3; ++i) {
+            TORCH_CHECK_TYPE(into[i].scalar_type() == at::kDouble, "molann::value_and_pbmetad: `into` must be float64 like x");
+            TORCH_CHECK_VALUE(into[i].is_contiguous() && into[i].numel() == counts[i] && into[i].device() == x.device(),
+                              "molann::value_and_pbmetad: `into` must be contiguous {[N, out_dim], [N, 2 + K], [N, n_inp, 3]} on x's device");
+        }
+    }
+    F64Linears lin;
+    f64_linears(op, *e, x, weights, biases, lin, ": call .double()");
+    std::lock_guard<std::mutex> lock(e->mu);
+    TORCH_CHECK_NOT_IMPLEMENTED(molann_plan_supports_value_and_pbmetad_f64(e->plan) == 1,
+                                "molann::value_and_pbmetad: one frame's rows exceed the LDS of a compute unit for this model; use run, form the "
+                                "K interpolants and their soft minimum with torch, then value_and_vjp");
+    if (n == 0) return {out, energies, gx};
+    hipStream_t stream = c10::hip::getCurrentHIPStream(x.get_device()).stream();
+    sync_live(*e, x, ref_x, weights, biases, stream);
+    check(molann_value_and_pbmetad_f64(e->plan, x.data_ptr<double>(), n, lin.W.data(), lin.B.data(), &t, out.data_ptr<double>(),
+                                       energies.data_ptr<double>(), 2 + K, gx.data_ptr<double>(), stream),
+          "molann_value_and_pbmetad_f64");
+    return {out, energies, gx};
+}
+#define MOLANN_PBMETAD_OP_PARAMS                                                                                                                     \
+    const at::Tensor &ref_x, std::vector<at::Tensor> weights, std::vector<at::Tensor> biases, const c10::optional<at::Tensor>&center,                \
+        const c10::optional<at::Tensor>&kappa, const c10::optional<at::Tensor>&rperiod, const c10::optional<at::Tensor>&flat,                        \
+        std::vector<int64_t> columns, const at::Tensor &table, std::vector<int64_t> shape, std::vector<double> lower, std::vector<double> spacing,   \
+        c10::List<bool> periodic, double kT, std::vector<at::Tensor> into
+#define MOLANN_PBMETAD_OP_ARGS ref_x, weights, biases, center, kappa, rperiod, flat, columns, table, shape, lower, spacing, periodic, kT, into
+std::vector<at::Tensor> value_and_pbmetad_hip(const at::Tensor& x_in, std::vector<int64_t> desc, MOLANN_PBMETAD_OP_PARAMS) {
+    return value_and_pbmetad_impl(x_in, desc, MOLANN_PBMETAD_OP_ARGS);
+}
+std::vector<at::Tensor> value_and_pbmetad_h_hip(const at::Tensor& x_in, int64_t handle, MOLANN_PBMETAD_OP_PARAMS) {
+    return value_and_pbmetad_impl(x_in, *desc_of(handle, "molann::value_and_pbmetad_h"), MOLANN_PBMETAD_OP_ARGS);
+}
+
 // The fused forward that also keeps the features: {out, features} - or {out, empty} where the plan has no such twin of its
 // kernel (molann_plan_backward_kind != 1 ... != 2 plans recompute in molann_backward_f32).  float32 fused plans.
 std::vector<at::Tensor> run_train_hip(const at::Tensor& x_in, std::vector<int64_t> desc, const at::Tensor& ref_x, std::vector<at::Tensor> weights,
@@ -2155,6 +2255,12 @@ TORCH_LIBRARY(molann, m) {
           "Tensor? restraint_period, Tensor? flat, int[] opes_columns, Tensor centers, Tensor heights, Tensor sigma, Tensor state, Tensor? opes_period, "
           "float scale, float epsilon, float cutoff, int[] grid_columns, Tensor? table, float[] lower, float[] spacing, bool[] periodic, "
           "Tensor[] into) -> Tensor[]");
+    m.def("value_and_pbmetad_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, "
+          "Tensor? restraint_period, Tensor? flat, int[] columns, Tensor table, int[] shape, float[] lower, float[] spacing, bool[] periodic, float kT, "
+          "Tensor[] into) -> Tensor[]");
+    m.def("value_and_pbmetad(Tensor x, int[] desc, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor? center, Tensor? kappa, "
+          "Tensor? restraint_period, Tensor? flat, int[] columns, Tensor table, int[] shape, float[] lower, float[] spacing, bool[] periodic, float kT, "
+          "Tensor[] into) -> Tensor[]");
     m.def("opes_deposit(Tensor(a!) centers, Tensor(b!) sigma, Tensor(c!) heights, Tensor(d!) state, Tensor? period, Tensor new_centers, "
           "Tensor new_sigma, Tensor new_heights, float threshold, float cutoff) -> ()");
     m.def("value_and_opes_table_h(Tensor x, int handle, Tensor ref_x, Tensor[] weights, Tensor[] biases, Tensor centers, Tensor heights, Tensor sigma, "
@@ -2205,6 +2311,8 @@ TORCH_LIBRARY_IMPL(molann, CUDA, m) { // ROCm builds of torch name the HIP devic
     m.impl("value_and_bias_opes_h", value_and_bias_opes_h_hip);
     m.impl("value_and_bias_opes_table", value_and_bias_opes_table_hip);
     m.impl("value_and_bias_opes_table_h", value_and_bias_opes_table_h_hip);
+    m.impl("value_and_pbmetad", value_and_pbmetad_hip);
+    m.impl("value_and_pbmetad_h", value_and_pbmetad_h_hip);
     m.impl("opes_deposit", opes_deposit_hip);
     m.impl("value_and_opes_table", value_and_opes_table_hip);
     m.impl("value_and_opes_table_h", value_and_opes_table_h_hip);

@@ -99,6 +99,7 @@ inline void f64_entry_rows(const molann_plan* p, BiasF64Args& a) { bias64_rows(p
 inline void f64_entry_rows(const molann_plan* p, OpesF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }   // the hills' rows, geometry and cap: F64_HILLS
 inline void f64_entry_rows(const molann_plan* p, BiasOpesF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }   // the bias' rows and geometry: F64_BIAS
 inline void f64_entry_rows(const molann_plan* p, BiasOpesTableF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }   // as BiasOpesF64Args: F64_BIAS
+inline void f64_entry_rows(const molann_plan* p, PbmetadF64Args& a) { bias64_rows(p, a.max_w, a.lds_per_frame); }   // the bias' rows and geometry: F64_BIAS
 inline void f64_entry_rows(const molann_plan* p, OpesTableF64Args& a) { restraint64_rows(p, a.max_w, a.lds_per_frame); }   // as OpesF64Args: F64_HILLS
 
 // geometry for this entry: the forces' rows, the restraint's (the hills' and the grid's too), the bias' or the Jacobian's, and the
@@ -319,6 +320,39 @@ inline int host_bias_opes_frame_f64(const double* y, int d_out, const molann_bia
     for (int j = 0; j < o->n_columns; ++j) dy[oc[j]] += dvo[j];
     for (int j = 0; j < n_gc; ++j) dy[gc[j]] += dg[j];
     energies[0] = e; energies[1] = 0.; energies[2] = vg; energies[3] = vo;
+    return MOLANN_OK;
+}
+
+// the K axes of molann_value_and_pbmetad_f64 from the caller's host arrays into `a`, in the order of the refusals: K, the columns, each
+// axis as grid_geometry_f64 has one, kT, the entries in all
+struct PbmetadGeom {
+    int K, col[PBMETAD_MAX_K], periodic[PBMETAD_MAX_K];
+    long n[PBMETAD_MAX_K], off[PBMETAD_MAX_K];
+    double lower[PBMETAD_MAX_K], h[PBMETAD_MAX_K];
+};
+inline int pbmetad_geometry_f64(const molann_pbmetad_terms_f64* t, int d_out, PbmetadGeom& g) {
+    if (t->n_columns < 1) return MOLANN_E_DESC;
+    if (t->n_columns > PBMETAD_MAX_K) return MOLANN_E_UNSUPPORTED;
+    g.K = t->n_columns;
+    const int rc = bias_columns_f64(g.K, t->columns, PBMETAD_MAX_K, d_out, g.col);
+    if (rc != MOLANN_OK) return rc;
+    int64_t entries = 0;
+    for (int k = 0; k < PBMETAD_MAX_K; ++k) {
+        g.n[k] = 4; g.off[k] = 0; g.lower[k] = 0.0; g.h[k] = 1.0; g.periodic[k] = 0;
+        if (k >= g.K) continue;
+        long n1[GRID_MAX_D];
+        double lo1[GRID_MAX_D], h1[GRID_MAX_D];
+        int per1[GRID_MAX_D];
+        const int32_t periodic_k = t->periodic ? t->periodic[k] : 0;
+        if (!grid_geometry_f64(1, t->shape + k, t->lower + k, t->spacing + k, &periodic_k, n1, lo1, h1, per1)) return MOLANN_E_DESC;
+        g.n[k] = n1[0]; g.lower[k] = lo1[0]; g.h[k] = h1[0]; g.periodic[k] = per1[0];
+    }
+    if (!std::isfinite(t->kT) || !(t->kT > 0.0)) return MOLANN_E_DESC;
+    for (int k = 0; k < g.K; ++k) {
+        g.off[k] = (long)entries;
+        entries += g.n[k];
+        if (entries >= (int64_t(1) << 31)) return MOLANN_E_DESC;
+    }
     return MOLANN_OK;
 }
 
@@ -597,6 +631,41 @@ int molann_value_and_bias_opes_table_f64(molann_plan* p, const double* x, int64_
                             has_g ? t->table : none, out, energies, grad_x);
 }
 
+int molann_plan_supports_value_and_pbmetad_f64(const molann_plan* p) { return molann_plan_supports_value_and_bias_f64(p); }
+
+int molann_value_and_pbmetad_f64(molann_plan* p, const double* x, int64_t n, const double* const* W, const double* const* b,
+                                 const molann_pbmetad_terms_f64* t, double* out, double* energies, int64_t energies_stride, double* grad_x,
+                                 molann_stream_t stream) {
+    if (p && !t) return MOLANN_E_NULL;
+    // the host arrays of the tables are required pointers like the others: refused with them, before alignment (and, like them, not
+    // looked at where n <= 0)
+    if (p && n > 0 && (!t->shape || !t->lower || !t->spacing)) return MOLANN_E_NULL;
+    F64Call<PbmetadF64Args> c;
+    // an absent restraint has none of its pointers looked at (x stands in for its centre below)
+    const bool has_r = t && t->kappa;
+    const int e = f64_entry_arguments(p, F64_BIAS, n, {x, out, energies, grad_x, t ? t->table : x, has_r ? t->center : x},
+                                      {has_r ? t->restraint_period : nullptr, has_r ? t->flat : nullptr}, W, b, c);
+    if (e != MOLANN_OK || n == 0) return e;
+    PbmetadF64Args& a = c.a;
+    PbmetadGeom g;
+    const int rc = pbmetad_geometry_f64(t, a.d_out, g);
+    if (rc != MOLANN_OK) return rc;
+    if (energies_stride < 2 + g.K) return MOLANN_E_DESC;
+    if (has_r && t->center_stride != 0 && t->center_stride != a.d_out) return MOLANN_E_DESC;
+    a.has_restraint = has_r ? 1 : 0;
+    a.K = g.K;
+    for (int k = 0; k < PBMETAD_MAX_K; ++k) {
+        a.col[k] = g.col[k]; a.periodic[k] = g.periodic[k]; a.n[k] = g.n[k]; a.off[k] = g.off[k]; a.lower[k] = g.lower[k]; a.h[k] = g.h[k];
+    }
+    a.center_stride = has_r ? (long)t->center_stride : 0;
+    a.e_stride = (long)energies_stride;
+    a.kT = t->kT;
+    const double* none = nullptr;
+    return f64_entry_launch(F64_ENTRY_KERNEL(frames_value_pbmetad_f64_kernel, c.g.G), "frames_value_pbmetad_f64_kernel", "parallel bias", p, c, stream,
+                            x, has_r ? t->center : none, has_r ? t->kappa : none, has_r ? t->restraint_period : none, has_r ? t->flat : none,
+                            t->table, out, energies, grad_x);
+}
+
 double molann_selftest_act_derivative_f64(int act, double z) { return act_derivative_f64(act, z); }
 
 double molann_selftest_restraint_f64(double y, double z, double kappa, double period, double flat, double* dy) {
@@ -672,6 +741,31 @@ int molann_selftest_bias_f64(const double* y, int d_out, const molann_bias_terms
     for (int j = 0; j < t->n_hills_columns; ++j) dy[hc[j]] += dh[j];
     for (int j = 0; j < t->n_grid_columns; ++j) dy[gc[j]] += dg[j];
     energies[0] = e; energies[1] = vh; energies[2] = vg;
+    return MOLANN_OK;
+}
+
+int molann_selftest_pbmetad_f64(const double* y, int d_out, const molann_pbmetad_terms_f64* t, double* energies, double* dy) {
+    if (!y || !t || !energies || !dy) return MOLANN_E_NULL;
+    const bool has_r = t->kappa;
+    if (!t->table || !t->shape || !t->lower || !t->spacing || (has_r && !t->center)) return MOLANN_E_NULL;
+    if (d_out < 1) return MOLANN_E_DESC;
+    PbmetadGeom g;
+    const int rc = pbmetad_geometry_f64(t, d_out, g);
+    if (rc != MOLANN_OK) return rc;
+    double e = 0.;
+    for (int k = 0; k < d_out; ++k) {
+        dy[k] = 0.;
+        if (has_r)
+            e += restraint_term_f64(y[k], t->center[k], t->kappa[k], t->restraint_period ? t->restraint_period[k] : 0.0, t->flat ? t->flat[k] : 0.0,
+                                    dy[k]);
+    }
+    double V[PBMETAD_MAX_K] = {}, dV[PBMETAD_MAX_K] = {}, w[PBMETAD_MAX_K];
+    for (int k = 0; k < g.K; ++k)
+        pbmetad_axis_value_f64(y[g.col[k]], t->table + g.off[k], g.n[k], g.lower[k], g.h[k], g.periodic[k] != 0, V[k], dV[k]);
+    const double vpb = pbmetad_softmin_f64(V, g.K, t->kT, w);
+    for (int k = 0; k < g.K; ++k) dy[g.col[k]] = pbmetad_cotangent_f64(dy[g.col[k]], w[k], dV[k]);
+    energies[0] = e; energies[1] = vpb;
+    for (int k = 0; k < g.K; ++k) energies[2 + k] = V[k];
     return MOLANN_OK;
 }
 
